@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the libdsp hot path on MI355X, one JSON line on stdout.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload fir|resample|decimate]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload fir|resample|decimate] [--dump-outputs DIR]
 
 Default line (what the driver records): BASELINE.json configs[1] -- a 256-tap FIR over a
 2^28-sample complex-float32 stream, device-resident in and out, one GPU.  A "step" is one pass
@@ -51,6 +51,15 @@ buffers         plain allocations (torch.empty), whatever the driver hands out: 
                 n_taps-1 samples of overlap), `host_cores` stated.  A reported baseline.
                 `configs0_cpu_only` (fir workload) = BASELINE configs[0], the CPU-only plumbing case:
                 63-tap real filter, 2^20 real float32 samples, fft_len 1024, same port, one thread.
+--dump-outputs  after all timing, what the LAST step of every timed leg (the headline and each other_configs row) wrote to its
+                output buffer, for comparing two builds output for output.  Per leg, named by its key (`_rank<r>` appended at
+                N > 1; `_shard<i>` per device with --single-process): `<key>.npy` float32 [windows, length] -- the whole output as
+                one row if it fits the leg's share of the budget (half of it for the headline, the other half split over the other
+                rows and ranks), else windows of 4096 elements: the first, the last and a seeded choice of the rest --,
+                `<key>_starts.npy` float64, the element offset of each row, and `<key>_length.npy` float64, the number of
+                elements the step wrote.  Elements are floats (I, Q interleaved for complex streams; bytes for the tx10 format).
+                Inputs and the number of calls before the last one are the same from run to run, so the same arguments give the
+                same outputs.
 """
 import argparse
 import json
@@ -66,6 +75,9 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0     # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 TOL = 1e-5                # BASELINE.json north_star
+DUMP_BYTES = 48 << 20     # --dump-outputs: every array of one run, all ranks together, stays under 64 MB
+DUMP_WINDOW = 4096        # elements per sampled window (2048 complex samples)
+DUMP_SEED = 20240917      # which windows are sampled: a function of the output's length only
 
 
 def parse():
@@ -99,7 +111,13 @@ def parse():
     ap.add_argument("--other-steps", type=int, default=20)
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--precondition", type=float, default=0.15, help="seconds of untimed launches before any warm-up")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what every timed leg's last step returned to DIR/<leg key>.npy (float32): all of "
+                         "it, or a fixed seeded sample of windows when it is larger than the leg's share of %d MiB" % (DUMP_BYTES >> 20))
+    a = ap.parse_args()
+    if a.steps < 1 or a.other_steps < 1 or a.warmup < 0:
+        ap.error("--steps and --other-steps must be at least 1, --warmup at least 0")
+    return a
 
 
 # --------------------------------------------------------------------------- self-launch
@@ -399,6 +417,7 @@ def make_fir_leg(ctx, name, taps, n, nch, ch0=0, algo="auto", in_fmt="f32", out_
     def step():
         leg.obj.process_stream(sp, yp, n, stream=stream)
     leg.step = step
+    leg.out_elems = lambda: nch * ((2 * n // 4) * 5 if out_fmt == "tx10" else 2 * n)
     # Stream calls never measure (api_fir.hip: fir_pick_variant is a table look-up; register loads by default).
     # The headline leg asks for the measurement explicitly, untimed, before any warm-up:
     # sfe_dsp_fir_calibrate on rank 0, the choice handed to every rank so that all of them run ONE kernel
@@ -521,6 +540,12 @@ def make_rs_leg(ctx, which, log2n, in_fmt="f32", short_proto=False):
         leg.n_out = leg.obj.process_stream(sp, n, yp, out_cap, rate, stream=stream)
         leg.calls += 1
     leg.step = step
+
+    def reset():
+        leg.obj.reset()
+        leg.k_before = leg.n_out = leg.calls = 0
+    leg.reset = reset
+    leg.out_elems = lambda: 2 * leg.n_out
     step()                    # sizes the launch: outputs per call differ by at most one between calls
     leg.bytes_per_launch = in_bytes * n + 8.0 * leg.n_out
 
@@ -624,6 +649,8 @@ def make_general_rate_leg(ctx, log2n=28, rate=1.77, interpolate=0, decimate=0, r
     def step():
         leg.n_out = leg.obj.process_stream(sp, n, yp, out_cap, rate, stream=stream)
     leg.step = step
+    leg.reset = leg.obj.reset
+    leg.out_elems = lambda: w * leg.n_out
     step()
     leg.bytes_per_launch = (2.0 if u8 else 4.0 * w) * n + 4.0 * w * leg.n_out
 
@@ -654,7 +681,7 @@ def make_general_rate_leg(ctx, log2n=28, rate=1.77, interpolate=0, decimate=0, r
     return leg
 
 
-def group_leg(ctx, taps, total_channels, n_ch, devices, steps, warmup):
+def group_leg(ctx, taps, total_channels, n_ch, devices, steps, warmup, dump=None):
     """ONE process, len(devices) devices: the channel partition made inside the library
     (sfe_dsp_fir_group_*, include/sfe_dsp.h) instead of one rank per GPU.  Launches go to every
     device before anything waits; the time is the wall clock around `steps` group calls and one
@@ -682,6 +709,10 @@ def group_leg(ctx, taps, total_channels, n_ch, devices, steps, warmup):
         grp.process_stream(pin, pout, n_ch)
     grp.sync()
     ms = (time.perf_counter() - t0) * 1e3 / steps
+    if dump:
+        key = "fir256_cf32_2p%d_%dch" % ((total_channels * n_ch).bit_length() - 1, total_channels)
+        for i, y in enumerate(ys):
+            dump_outputs(torch, dump, "%s_shard%d" % (key, i), y, y.numel(), DUMP_BYTES // 2 // len(ys))
     # parity: history = the tail of the same buffer (every call re-reads the same input)
     W, hlen, worst, count = 1 << 13, len(taps) - 1, 0.0, 0
     blk = lambda v: orc.Blkconv(np.ascontiguousarray(taps, dtype=np.float32), 4096).stream(np.ascontiguousarray(v))
@@ -729,7 +760,7 @@ def main_single_process(args):
     total_channels = args.channels or 64
     log2n = args.log2n or 30
     n_ch = (1 << log2n) // total_channels
-    g = group_leg(ctx, synth.taps_cfg2(), total_channels, n_ch, devices, args.steps, args.warmup)
+    g = group_leg(ctx, synth.taps_cfg2(), total_channels, n_ch, devices, args.steps, args.warmup, dump=args.dump_outputs)
     out = {"metric": "complex-float32 MS/s through 256-tap blkconv FIR; % of HBM roofline", "value": g["value"], "unit": "MS/s",
            "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": g["ms"], "higher_is_better": True,
            "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -777,6 +808,35 @@ def precondition(ctx, leg, seconds=0.15):
         for _ in range(8):
             leg.step()
         torch.cuda.synchronize()
+    # a resampler's output depends on how many calls came before (its place in the stream x|x|x...), and this loop's count on
+    # the clock: the handle starts again so that its warm-up and timed steps compute the same outputs in every run
+    if hasattr(leg, "reset"):
+        leg.reset()
+
+
+def sample_output(torch, y, n, budget):
+    """(rows float32 [windows, length], starts float64) of the first n elements of the device buffer y: one row of all of them
+    if they fit in `budget` bytes, else DUMP_WINDOW-element windows -- the first, the last and a seeded choice of the others."""
+    W = DUMP_WINDOW
+    if 4 * n <= budget or n <= W:
+        return y[:n].to(torch.float32).cpu().numpy()[None], np.zeros(1)
+    starts = np.arange(0, n - W + 1, W)
+    if starts[-1] != n - W:
+        starts = np.append(starts, n - W)
+    k = max(2, budget // (4 * W))
+    if len(starts) > k:
+        pick = np.random.default_rng(DUMP_SEED).choice(len(starts) - 2, k - 2, replace=False) + 1
+        starts = starts[np.sort(np.concatenate([[0, len(starts) - 1], pick]))]
+    rows = torch.stack([y[s: s + W] for s in starts.tolist()]).to(torch.float32).cpu().numpy()
+    return rows, starts.astype(np.float64)
+
+
+def dump_outputs(torch, d, name, y, n, budget):
+    rows, starts = sample_output(torch, y, n, budget)
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, name + ".npy"), rows)
+    np.save(os.path.join(d, name + "_starts.npy"), starts)
+    np.save(os.path.join(d, name + "_length.npy"), np.array([n], dtype=np.float64))
 
 
 def checksum(ctx, leg):
@@ -1040,6 +1100,13 @@ def main():
         if held is not None:
             row["parity"]["input_is_the_synthetic_stream"] = bool(held)
             row["parity"]["ok"] = row["parity"]["ok"] and bool(held)
+    if args.dump_outputs:
+        # nothing has been launched on these output buffers since each leg's last timed step (the checks above only read them)
+        sfx = "_rank%d" % rank if world > 1 else ""
+        share = DUMP_BYTES // 2 // world
+        dump_outputs(torch, args.dump_outputs, head.key + sfx, head.y, head.out_elems(), share)
+        for leg in others:
+            dump_outputs(torch, args.dump_outputs, leg.key + sfx, leg.y, leg.out_elems(), share // len(others))
 
     sharded = world > 1 and head.kind == "fir"
     traffic, traffic_stale = pmc_traffic(head.key)

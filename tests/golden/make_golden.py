@@ -131,6 +131,31 @@ def main():
     g1.update({"g2_taps": h, "g2_fft_len": 2048, "g2_x": xs, "g2_y64": y64})
     np.savez_compressed(os.path.join(OUT, "g1_blkconv.npz"), **g1)
     print("G1/G2 blkconv written")
+    g8_random()
+
+
+def g8_random():
+    """G8: random taps / rates / chunk sizes (seed 3), inputs and the reference's outputs, both classes; the last case is a
+    rate below 1 (resample only).  tests/test_oracle.py::test_against_live_reference_random."""
+    rng = np.random.default_rng(3)
+    cases = []
+    for _ in range(12):
+        U = int(rng.integers(1, 6))
+        nt = int(rng.integers(U, 60))
+        B = int(rng.integers(max(nt // U + 2, 8), 300))
+        taps = rng.standard_normal(nt).astype(np.float32)
+        x = rng.standard_normal(5 * B + 17).astype(np.float32)
+        rate = float(np.float32(rng.uniform(1.0, 6.0)))
+        cases.append((taps, x, U, B, rate, int(np.ceil(B / rate)) + 2))
+    cases.append((rng.standard_normal(31).astype(np.float32), rng.standard_normal(1024).astype(np.float32), 4, 128, 0.41, 4 * 128))
+    g8 = {"cases": len(cases)}
+    for t, (taps, x, U, B, rate, ol) in enumerate(cases):
+        g8.update({f"taps_{t}": taps, f"x_{t}": x, f"U_{t}": U, f"B_{t}": B, f"rate_{t}": np.float32(rate), f"out_len_{t}": ol})
+        g8[f"y_res_{t}"], g8[f"n_res_{t}"] = run(orc.RefResample, taps, U, B, x, rate, ol)
+        if rate >= 1.0:
+            g8[f"y_dec_{t}"], g8[f"n_dec_{t}"] = run(orc.RefDecimate, taps, U, B, x, rate, ol)
+    np.savez_compressed(os.path.join(OUT, "g8_reference_random.npz"), **g8)
+    print(f"G8 {len(cases)} random cases written")
 
 
 if __name__ == "__main__":
