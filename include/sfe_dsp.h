@@ -408,6 +408,45 @@ int sfe_dsp_rs_set_state(sfe_rs_t h, const sfe_rs_timestate *state);
 int sfe_dsp_rx_u8_to_f32(const void *d_bytes, void *d_floats, size_t n_bytes, sfe_stream_t stream);
 int sfe_dsp_tx_f32_to_10bit(const void *d_floats, void *d_bytes, size_t n_floats, sfe_stream_t stream);
 
+/* ------------------------------------------------- polyphase filter-bank channelizer
+ * Splits a complex stream into M sub-bands in one pass over it (no reference counterpart: the
+ * first step of a receive chain behind gr-simplefe's source, source_c_impl.cc:121-132).  With a
+ * real prototype low-pass h[0..L), channel k (0 <= k < M) of output instant m is
+ *     y_k[m] = sum_{n<L} h[n] x[mD - n] exp(-j 2 pi k (mD - n) / M)
+ * x shifted down by k/M cycles per sample, filtered by h, every D-th sample kept: a true baseband
+ * signal (channels k >= M/2 are the negative frequencies), no 1/M factor.  x[i] = 0 before the
+ * first sample after create / reset.  Shapes: M a power of two in [4, 1024], D = M (critically
+ * sampled) or M/2 (2x oversampled), 1 <= n_taps <= 32 M; anything else is SFE_EINVAL.
+ * Computed by csrc/chan.hip: branch sums in registers, one M-point transform per instant in LDS. */
+typedef void *sfe_chan_t;     /* opaque: one channelizer over n_streams streams */
+/* Host-only (no GPU): validates the shape; *taps_per_branch = P = ceil(n_taps / M), *history =
+ * the samples of carried state per stream the device keeps (>= n_taps - 1: whole tap chunks of
+ * the kernel).  Either output pointer may be NULL. */
+int sfe_dsp_chan_plan(int n_taps, int n_chans, int decim, int *taps_per_branch, int *history);
+/*   taps       n_taps real float32 (copied, zero-padded to whole branches)
+ *   n_chans    M;  decim  D
+ *   n_streams  independent input streams sharing the taps, each with its own history and output
+ *              counter.  SFE_ENODEV without a GPU: nothing computes on the CPU. */
+int sfe_dsp_chan_create(const float *taps, int n_taps, int n_chans, int decim, int n_streams,
+                        int device, sfe_chan_t *out);
+/* SFE_FMT_F32 (cf32 input, 8-byte aligned) or SFE_FMT_U8 ((I,Q) byte pairs, 2-byte aligned,
+ * converted (b-128)*(1/127) on load exactly as sfe_dsp_rx_u8_to_f32).  The carried state is kept
+ * as cf32, so the format may change between calls. */
+int sfe_dsp_chan_set_input_format(sfe_chan_t h, int fmt);
+/* n_in samples of every stream: stream s at d_in + s*in_stride (samples of the input format);
+ * channel k of stream s at d_out + (s*M + k)*out_stride (cf32 samples, 8-byte aligned).  n_in a
+ * multiple of D (else SFE_EINVAL); *n_out = n_in / D per channel; n_in = 0 is a no-op.
+ * out_stride < *n_out is SFE_ERANGE; overlapping input and output byte ranges, misaligned
+ * buffers and in_stride < n_in with more than one stream are SFE_EINVAL; nothing is launched on
+ * a refusal.  Cutting a stream into calls at any multiple of D gives the one-call result bit for
+ * bit.  Asynchronous on `stream`, no host synchronisation or allocation.  The output counter
+ * lives on the host: a call on a stream under graph capture is SFE_ESTATE, nothing enqueued. */
+int sfe_dsp_chan_process_stream(sfe_chan_t h, const void *d_in, size_t n_in, size_t in_stride,
+                                void *d_out, size_t out_stride, size_t *n_out, sfe_stream_t stream);
+/* Zero the carried state and the output counter (a fresh handle). */
+int sfe_dsp_chan_reset(sfe_chan_t h);
+int sfe_dsp_chan_destroy(sfe_chan_t h);
+
 #ifdef __cplusplus
 }
 #endif

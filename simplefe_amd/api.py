@@ -6,7 +6,7 @@ Two layers, both thin:
     `process(in_array, out_len, rate) -> (n_out, out_array)` for the resamplers, so the
     reference's driver scripts (libdsp/test/test_decimate.py:22-25) read the same.
   * `Fir`, `Rs`, `DeviceArray` -- the device-resident bulk path used by bench.py and the
-    parity tests (sfe_dsp_*_process_stream).
+    parity tests (sfe_dsp_*_process_stream); `Chan`, the polyphase channelizer (sfe_dsp_chan_*).
 
 Everything computes on the GPU through the C ABI; numpy is only the host container.
 """
@@ -410,6 +410,75 @@ class Rs:
                 warnings.warn("Rs.close: a pipe still borrows this handle (sfe_dsp_pipe_destroy first); handle kept",
                               ResourceWarning, stacklevel=2)
                 return
+            self._h = None
+
+    __del__ = close
+
+
+def chan_plan(n_taps, n_chans, decim):
+    """sfe_dsp_chan_plan (host only, no GPU): (taps per branch P, samples of history carried per stream)."""
+    P, H = C.c_int(0), C.c_int(0)
+    check(_l.load().sfe_dsp_chan_plan(int(n_taps), int(n_chans), int(decim), C.byref(P), C.byref(H)))
+    return P.value, H.value
+
+
+class Chan:
+    """Polyphase filter-bank channelizer (sfe_dsp_chan_*): n_chans = M sub-bands of n_streams complex streams, one
+    output every `decim` (M or M/2) input samples per channel; real prototype taps."""
+
+    def __init__(self, taps, n_chans, decim, n_streams=1, device=0):
+        self._L = _l.load()
+        t = _f32(taps)
+        self.n_chans, self.decim, self.n_streams = int(n_chans), int(decim), int(n_streams)
+        self.in_u8 = False
+        h = C.c_void_p()
+        check(self._L.sfe_dsp_chan_create(t.ctypes.data, t.size, self.n_chans, self.decim, self.n_streams, device,
+                                          C.byref(h)))
+        self._h = h.value
+
+    def set_input_format(self, fmt):
+        """lib.FMT_F32 (cf32) or lib.FMT_U8 ((I,Q) byte pairs, converted on load)."""
+        check(self._L.sfe_dsp_chan_set_input_format(self._h, fmt))
+        self.in_u8 = fmt == _l.FMT_U8
+
+    def reset(self):
+        check(self._L.sfe_dsp_chan_reset(self._h))
+
+    def process_stream(self, d_in, n_in, d_out, in_stride=None, out_stride=None, stream=None):
+        """d_in / d_out: DeviceArray or raw device pointers; n_in samples per stream (a multiple of decim).  Channel k
+        of stream s goes to d_out + (s*M + k)*out_stride cf32 samples.  Returns n_out = n_in / decim."""
+        pi = d_in.ptr if isinstance(d_in, DeviceArray) else int(d_in)
+        po = d_out.ptr if isinstance(d_out, DeviceArray) else int(d_out)
+        n_out = C.c_size_t(0)
+        check(self._L.sfe_dsp_chan_process_stream(self._h, pi, int(n_in), int(n_in) if in_stride is None else int(in_stride),
+                                                  po, int(n_in) // self.decim if out_stride is None else int(out_stride),
+                                                  C.byref(n_out), stream))
+        return n_out.value
+
+    def channelize(self, x):
+        """Host convenience, computed on the GPU: x is (n_streams, n) complex -- or, with FMT_U8, (n_streams, 2n)
+        uint8 (I,Q) pairs -- (1-D for one stream); returns (n_streams, M, n // decim) complex64."""
+        if self.in_u8:
+            b = np.ascontiguousarray(x, dtype=np.uint8).reshape(self.n_streams, -1)
+            n = b.shape[1] // 2
+            d_in = DeviceArray.from_bytes(b)
+        else:
+            z = np.ascontiguousarray(x, dtype=np.complex64).reshape(self.n_streams, -1)
+            n = z.shape[1]
+            d_in = DeviceArray.from_numpy(z.view(np.float32))
+        n_out = n // self.decim
+        d_out = DeviceArray(max(1, self.n_streams * self.n_chans * n_out) * 2)
+        try:
+            k = self.process_stream(d_in, n, d_out)
+            y = d_out.to_numpy(self.n_streams * self.n_chans * k * 2)
+        finally:
+            d_in.free()
+            d_out.free()
+        return y.view(np.complex64).reshape(self.n_streams, self.n_chans, k)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.sfe_dsp_chan_destroy(self._h)
             self._h = None
 
     __del__ = close

@@ -19,12 +19,13 @@ LIB = os.path.join(HERE, "libsfe_dsp.so")
 # ablate.py); never loaded by simplefe_amd.lib, tests or bench.py, and not built by default.
 LIB_DIAG = os.path.join(HERE, "libsfe_dsp_diag.so")
 ARCH = "gfx950"
-# bit-exact restatements of the reference arithmetic: no implicit FMA contraction
-EXACT_SOURCES = ("polyphase.hip", "util.hip")
+# bit-exact restatements of the reference arithmetic: no implicit FMA contraction (chan.hip: its u8 and cf32
+# instantiations must give the same bits on the same samples; its multiply-adds are explicit)
+EXACT_SOURCES = ("polyphase.hip", "util.hip", "chan.hip")
 TICKET_SOURCES = ("fir_fft.hip", "poly_fft.hip")
 # host side only (handles, plans, launch choices, device groups):
 # not part of the kernel-source hash
-HOST_SOURCES = ("api.hip", "api_plans.hip", "api_fir.hip", "api_rs.hip", "api_pipe.hip", "group.hip", "host.h")
+HOST_SOURCES = ("api.hip", "api_plans.hip", "api_fir.hip", "api_rs.hip", "api_pipe.hip", "api_chan.hip", "group.hip", "host.h")
 
 
 def sources(diag=False):
@@ -40,7 +41,7 @@ def _deps():
 # the files that define one workload's kernel (round 5): a counter pass is stamped with the hash of THESE, so that a change to another
 # kernel's file does not orphan it.  None = every kernel source.
 KERNEL_FILES = {"fir": ("fir_fft.hip", "fft16.h", "common.h"), "resample": ("poly_fft.hip", "fft16.h", "common.h"),
-                "decimate": ("polyphase.hip", "common.h")}
+                "decimate": ("polyphase.hip", "common.h"), "chan": ("chan.hip", "fft16.h", "common.h")}
 
 
 def csrc_hash(kind=None):
@@ -146,8 +147,13 @@ def check_resources(res):
             bad.append("%s: %s" % (k[:200], r))
         if fl and not fl["DIAG"] and r.get("Occupancy", 4) < 4:
             bad.append("%s: fewer than 4 workgroups per CU: %s" % (k[:200], r))
+    # the channelizer: every instantiation keeps its windows and accumulators in registers
+    for k, r in res.get("chan.hip", {}).items():
+        if r.get("ScratchSize", 0) or r.get("VGPRs Spill", 0) or r.get("SGPRs Spill", 0):
+            bad.append("%s: channelizer kernel touches scratch: %s" % (k[:200], r))
     if bad:
-        raise RuntimeError("FIR kernels of the default path must not touch scratch and must keep 4 workgroups per CU:\n  " + "\n  ".join(bad))
+        raise RuntimeError("FIR kernels of the default path and the channelizer kernels must not touch scratch; the FIR ones must keep "
+                           "4 workgroups per CU:\n  " + "\n  ".join(bad))
 
 
 def build_lib(force=False, verbose=False, extra=(), diag=False):

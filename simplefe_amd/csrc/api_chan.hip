@@ -1,0 +1,229 @@
+// api_chan.hip -- the channelizer handle behind sfe_chan_t, sfe_dsp_chan_* (include/sfe_dsp.h).  Host code only; the
+// kernels are in chan.hip.
+#include "host.h"
+
+namespace sfe {
+
+// chan.hip
+int chan_tile_rows(int logm);
+int launch_chan(int logm, int half, int u8, const void *in, long long in_stride, const v2f *hist, v2f *hist_next,
+                const float *taps, const v2f *tw, v2f *out, long long out_stride, long long n_in, long long n_out, int P, int H,
+                int parity, int n_streams, hipStream_t st);
+
+namespace {
+
+constexpr int CHAN_RU = 8;      // tap rows per chunk of the kernel (chan.hip): P is padded to a multiple of it
+
+struct Chan {
+    uint32_t magic = 0x43484e31u;   // 'CHN1'
+    int M = 0, logm = 0, D = 0, n_taps = 0, P = 0, Ppad = 0, H = 0, n_streams = 1, device = 0, in_u8 = 0;
+    float *d_taps = nullptr;        // [Ppad][M]: h zero-padded
+    v2f *d_tw = nullptr;            // [M]: exp(+j 2 pi q / M)
+    v2f *d_hist[2] = {nullptr, nullptr};   // [n_streams][H] each: the current history and the next call's
+    int cur = 0;
+    unsigned long long m_count = 0; // outputs per channel since create / reset
+    size_t hist_bytes() const { return (size_t)n_streams * H * sizeof(v2f); }
+};
+
+Chan *as_chan(void *h)
+{
+    Chan *c = static_cast<Chan *>(h);
+    if (c && c->magic != 0x43484e31u) {
+        set_error("not a live channelizer handle");
+        return nullptr;
+    }
+    return c;
+}
+
+void chan_free(Chan *c)
+{
+    if (!c) return;
+    if (c->d_taps) (void)hipFree(c->d_taps);
+    if (c->d_tw) (void)hipFree(c->d_tw);
+    for (auto *p : c->d_hist)
+        if (p) (void)hipFree(p);
+    c->magic = 0;
+    delete c;
+}
+
+int chan_check_shape(int n_taps, int M, int D, int *logm)
+{
+    int lg = 0;
+    while (lg < 30 && (1 << lg) < M) lg++;
+    if (M < 4 || M > 1024 || (1 << lg) != M) {
+        set_error("chan: n_chans = %d must be a power of two in [4, 1024]", M);
+        return SFE_EINVAL;
+    }
+    if (D != M && D != M / 2) {
+        set_error("chan: decim = %d must be n_chans (%d) or n_chans / 2 (%d)", D, M, M / 2);
+        return SFE_EINVAL;
+    }
+    if (n_taps < 1 || n_taps > 32 * M) {
+        set_error("chan: n_taps = %d must be in [1, 32 * n_chans = %d]", n_taps, 32 * M);
+        return SFE_EINVAL;
+    }
+    if (logm) *logm = lg;
+    return SFE_OK;
+}
+
+}  // namespace
+}  // namespace sfe
+
+using namespace sfe;
+
+extern "C" {
+
+int sfe_dsp_chan_plan(int n_taps, int n_chans, int decim, int *taps_per_branch, int *history)
+{
+    const int rc = chan_check_shape(n_taps, n_chans, decim, nullptr);
+    if (rc != SFE_OK) return rc;
+    const int P = (n_taps + n_chans - 1) / n_chans;
+    if (taps_per_branch) *taps_per_branch = P;
+    if (history) *history = (P + CHAN_RU - 1) / CHAN_RU * CHAN_RU * n_chans;
+    return SFE_OK;
+}
+
+int sfe_dsp_chan_create(const float *taps, int n_taps, int n_chans, int decim, int n_streams, int device, sfe_chan_t *out)
+{
+    if (!out) return SFE_EINVAL;
+    *out = nullptr;
+    int logm = 0;
+    int rc = chan_check_shape(n_taps, n_chans, decim, &logm);
+    if (rc != SFE_OK) return rc;
+    if (!taps || n_streams < 1) {
+        set_error("chan_create: need taps and n_streams >= 1");
+        return SFE_EINVAL;
+    }
+    int prev_dev = -1;
+    (void)hipGetDevice(&prev_dev);
+    rc = use_device(device);
+    if (rc != SFE_OK) return rc;
+    struct Restore { int d; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore__{prev_dev};
+    Chan *c = new (std::nothrow) Chan;
+    if (!c) return SFE_ENOMEM;
+    c->M = n_chans;
+    c->logm = logm;
+    c->D = decim;
+    c->n_taps = n_taps;
+    c->P = (n_taps + n_chans - 1) / n_chans;
+    c->Ppad = (c->P + CHAN_RU - 1) / CHAN_RU * CHAN_RU;
+    c->H = c->Ppad * n_chans;
+    c->n_streams = n_streams;
+    c->device = device;
+    auto fail = [&](int code) { chan_free(c); return code; };
+#define TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail(hip_fail(e__, #call)); } while (0)
+    std::vector<float> hp((size_t)c->Ppad * n_chans, 0.0f);
+    std::copy(taps, taps + n_taps, hp.begin());
+    std::vector<v2f> tw(n_chans);
+    for (int q = 0; q < n_chans; q++) {
+        const double a = 2.0 * M_PI * q / n_chans;
+        tw[q] = v2f{(float)cos(a), (float)sin(a)};
+        if (q % (n_chans / 4) == 0) {       // the quarter turns exactly
+            static const float cq[4] = {1.0f, 0.0f, -1.0f, 0.0f}, sq[4] = {0.0f, 1.0f, 0.0f, -1.0f};
+            tw[q] = v2f{cq[q / (n_chans / 4)], sq[q / (n_chans / 4)]};
+        }
+    }
+    TRY(hipMalloc(&c->d_taps, hp.size() * sizeof(float)));
+    TRY(hipMemcpy(c->d_taps, hp.data(), hp.size() * sizeof(float), hipMemcpyHostToDevice));
+    TRY(hipMalloc(&c->d_tw, tw.size() * sizeof(v2f)));
+    TRY(hipMemcpy(c->d_tw, tw.data(), tw.size() * sizeof(v2f), hipMemcpyHostToDevice));
+    for (auto &p : c->d_hist) {
+        TRY(hipMalloc(&p, c->hist_bytes()));
+        TRY(hipMemset(p, 0, c->hist_bytes()));
+    }
+    TRY(hipDeviceSynchronize());
+#undef TRY
+    *out = c;
+    return SFE_OK;
+}
+
+int sfe_dsp_chan_set_input_format(sfe_chan_t h, int fmt)
+{
+    Chan *c = as_chan(h);
+    if (!c || (fmt != SFE_FMT_F32 && fmt != SFE_FMT_U8)) {
+        set_error("chan_set_input_format: null handle or a format other than SFE_FMT_F32 / SFE_FMT_U8");
+        return SFE_EINVAL;
+    }
+    c->in_u8 = fmt == SFE_FMT_U8;
+    return SFE_OK;
+}
+
+int sfe_dsp_chan_process_stream(sfe_chan_t h, const void *d_in, size_t n_in, size_t in_stride, void *d_out, size_t out_stride,
+                                size_t *n_out, sfe_stream_t stream)
+{
+    Chan *c = as_chan(h);
+    if (n_out) *n_out = 0;
+    if (!c || !n_out) {
+        set_error("chan_process_stream: null handle or n_out");
+        return SFE_EINVAL;
+    }
+    if (n_in % (size_t)c->D) {
+        set_error("chan_process_stream: n_in = %zu is not a multiple of decim = %d", n_in, c->D);
+        return SFE_EINVAL;
+    }
+    const size_t no = n_in / c->D;
+    if (n_in == 0) return SFE_OK;
+    if (!d_in || !d_out) {
+        set_error("chan_process_stream: null buffer");
+        return SFE_EINVAL;
+    }
+    if (out_stride < no) {
+        set_error("chan_process_stream: out_stride %zu < n_out %zu", out_stride, no);
+        return SFE_ERANGE;
+    }
+    if (c->n_streams > 1 && in_stride < n_in) {
+        set_error("chan_process_stream: in_stride %zu < n_in %zu with %d streams", in_stride, n_in, c->n_streams);
+        return SFE_EINVAL;
+    }
+    const size_t isz = c->in_u8 ? 2 : 8;
+    if ((reinterpret_cast<uintptr_t>(d_in) & (isz - 1)) || (reinterpret_cast<uintptr_t>(d_out) & 7)) {
+        set_error("chan_process_stream: buffers must be aligned to their element (cf32 8 B, u8 (I,Q) pairs 2 B)");
+        return SFE_EINVAL;
+    }
+    const size_t in_b = ((size_t)(c->n_streams - 1) * in_stride + n_in) * isz;
+    const size_t out_b = ((size_t)c->n_streams * c->M - 1) * out_stride * sizeof(v2f) + no * sizeof(v2f);
+    if (ranges_overlap(d_in, in_b, d_out, out_b)) {
+        set_error("chan_process_stream: input and output ranges overlap (in-place operation is not supported)");
+        return SFE_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (stream_is_capturing(s)) {
+        // the output counter (the D = M/2 parity) and the history buffer pair advance on the host
+        set_error("chan_process_stream: graph capture is not supported (the output counter lives on the host)");
+        return SFE_ESTATE;
+    }
+    SFE_ON_DEVICE(c->device);
+    const int rc = launch_chan(c->logm, c->D != c->M, c->in_u8, d_in, (long long)in_stride, c->d_hist[c->cur], c->d_hist[c->cur ^ 1],
+                               c->d_taps, c->d_tw, static_cast<v2f *>(d_out), (long long)out_stride, (long long)n_in, (long long)no,
+                               c->Ppad, c->H, (int)(c->m_count & 1), c->n_streams, s);
+    if (rc != SFE_OK) return rc;
+    c->cur ^= 1;
+    c->m_count += no;
+    *n_out = no;
+    return SFE_OK;
+}
+
+int sfe_dsp_chan_reset(sfe_chan_t h)
+{
+    Chan *c = as_chan(h);
+    if (!c) return SFE_EINVAL;
+    SFE_ON_DEVICE(c->device);
+    SFE_HIP(hipDeviceSynchronize());
+    for (auto *p : c->d_hist) SFE_HIP(hipMemset(p, 0, c->hist_bytes()));
+    SFE_HIP(hipDeviceSynchronize());
+    c->cur = 0;
+    c->m_count = 0;
+    return SFE_OK;
+}
+
+int sfe_dsp_chan_destroy(sfe_chan_t h)
+{
+    Chan *c = as_chan(h);
+    if (!c) return SFE_OK;
+    DeviceGuard g(c->device);
+    (void)hipDeviceSynchronize();
+    chan_free(c);
+    return SFE_OK;
+}
+
+}  // extern "C"

@@ -105,6 +105,12 @@ SIGNATURES = {
     "sfe_dsp_rs_group_destroy": (i32, [vp]),
     "sfe_dsp_rx_u8_to_f32": (i32, [vp, vp, sz, vp]),
     "sfe_dsp_tx_f32_to_10bit": (i32, [vp, vp, sz, vp]),
+    "sfe_dsp_chan_plan": (i32, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
+    "sfe_dsp_chan_create": (i32, [vp, i32, i32, i32, i32, i32, C.POINTER(vp)]),
+    "sfe_dsp_chan_set_input_format": (i32, [vp, i32]),
+    "sfe_dsp_chan_process_stream": (i32, [vp, vp, sz, sz, vp, sz, C.POINTER(sz), vp]),
+    "sfe_dsp_chan_reset": (i32, [vp]),
+    "sfe_dsp_chan_destroy": (i32, [vp]),
 }
 
 # the diagnostic library only (simplefe_amd/csrc/diag/sfe_dsp_diag.h; scripts/ load it by pointing LIB_PATH at it): bound when present

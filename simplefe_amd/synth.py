@@ -5,6 +5,8 @@ identically on the device (csrc/synth.hip: sfe_dsp_synth_fill), so a 2^30-sample
 can be generated in HBM and any window of it reproduced on the host for checking.
 Values are (int32(hash) >> 8) * 2^-23: exactly representable float32 in [-1, 1).
 """
+import os
+
 import numpy as np
 
 SEED = 20240601
@@ -101,3 +103,48 @@ def rel_rms(y, ref):
     ref = np.asarray(ref, dtype=np.float64)
     den = np.sqrt(np.sum(ref * ref))
     return float(np.sqrt(np.sum((y - ref) ** 2)) / den) if den > 0 else float(np.sqrt(np.sum(y * y)))
+
+
+def chan_reference(x, h, n_chans, decim, first=0):
+    """The channelizer's contract (sfe_dsp_chan_*) computed literally in float64, channel by channel: mix x down by
+    exp(-j 2 pi k i / M) (i the absolute sample index, x[0] being sample `first`), convolve with h (FFT convolution;
+    samples before x[0] are zero), keep the samples at i = m * decim.  Returns (M, n_out) complex128 for the instants
+    m * decim in [first, first + len(x))."""
+    x = np.asarray(x).astype(np.complex128).ravel()
+    h = np.asarray(h, dtype=np.float64).ravel()
+    M, D, n = int(n_chans), int(decim), x.size
+    i = first + np.arange(n)
+    keep = np.nonzero(i % D == 0)[0]
+    try:                                    # batched transforms on several cores where scipy is installed
+        from scipy import fft as F
+        kw = {"workers": min(16, os.cpu_count() or 1)}
+    except ImportError:
+        F, kw = np.fft, {}
+    nfft = 1 << int(np.ceil(np.log2(n + h.size)))
+    H = F.fft(h, nfft)
+    mix = np.exp(-2j * np.pi * np.arange(M) / M)          # exp(-j 2 pi q / M), indexed by (k i) mod M
+    out = np.empty((M, keep.size), dtype=np.complex128)
+    for k0 in range(0, M, 16):
+        k = np.arange(k0, min(M, k0 + 16))[:, None]
+        z = x[None, :] * mix[(k * (i % M)[None, :]) % M]
+        out[k0:k0 + k.shape[0]] = F.ifft(F.fft(z, nfft, axis=1, **kw) * H[None, :], axis=1, **kw)[:, keep]
+    return out
+
+
+def chan_reference_direct(x, h, n_chans, decim, first, m0, n_out):
+    """The same contract evaluated straight from its formula, for windows of long streams: outputs m0 .. m0+n_out-1,
+    y_k[m] = sum_n h[n] x[mD - n] exp(-j 2 pi k (mD - n) / M), with x[0] being sample `first` (which must be
+    <= m0 D - (len(h) - 1), or 0).  One matrix product per window: rows are instants, columns taps."""
+    x = np.asarray(x).astype(np.complex128).ravel()
+    h = np.asarray(h, dtype=np.float64).ravel()
+    M, D, L = int(n_chans), int(decim), h.size
+    m = m0 + np.arange(n_out)
+    idx = (m * D)[:, None] - np.arange(L)[None, :] - first         # [n_out, L] positions in x
+    X = np.where(idx >= 0, x[np.clip(idx, 0, None)], 0)
+    if first > 0:
+        assert idx.min() >= 0, "the window must hold the L-1 samples before its first output"
+    n = np.arange(L)
+    k = np.arange(M)
+    G = h[:, None] * np.exp(2j * np.pi * ((n[:, None] * k[None, :]) % M) / M)             # [L, M]
+    lead = np.exp(-2j * np.pi * (((m * D)[:, None] % M) * k[None, :] % M) / M)          # [n_out, M]
+    return ((X @ G) * lead).T
