@@ -546,6 +546,8 @@ static int rs_process_stream_impl(sfe_rs_t h, const void *d_in, size_t n_in, siz
         std::vector<size_t> extra_chunks;
         std::vector<SegChunk> chunks;
         chunks.reserve(n_in / (size_t)r->blksize + 1);
+        std::vector<int> chunk_ref;                             // per call: its memoised plan, -1 for the calls in `extra`
+        chunk_ref.reserve(n_in / (size_t)r->blksize + 1);
         size_t K = 0;
         int max_m = 0;
         int prev_ref = -1;          // plan of the previous (memoised) call of this launch: its `next` link is followed / filled in
@@ -591,12 +593,14 @@ static int rs_process_stream_impl(sfe_rs_t h, const void *d_in, size_t n_in, siz
                 c.n_seg = ref.n_seg;
                 c.n_out = ref.n_out;
                 prev_ref = idx;
+                chunk_ref.push_back(idx);
             } else {
                 prev_ref = -1;
                 c.seg_first = (int)extra.size();                 // + the table's final size, below
                 c.n_out = time_law_segments(&st, r->U, m, cap, rate, extra);
                 c.n_seg = (int)extra.size() - c.seg_first;
                 extra_chunks.push_back(chunks.size());
+                chunk_ref.push_back(-1);
             }
             chunks.push_back(c);
             K += (size_t)c.n_out;
@@ -626,7 +630,6 @@ static int rs_process_stream_impl(sfe_rs_t h, const void *d_in, size_t n_in, siz
         sa.taps_global = 0;
         sa.split = 1;
         sa.tile_cap = 0;
-        sa.span_slack = (int)ceilf(rate) + 64;          // one output's step in samples + room for the float32 recurrence's wobble
         // plan tables: grow-only device arrays + pinned staging.  The previous call's UPLOADS may still be reading the
         // staging: wait for them -- the event behind them -- not for the stream: that call's kernel runs on while this
         // call is planned and queued (waiting for the stream here made every call a full host/device round trip).
@@ -739,9 +742,41 @@ static int rs_process_stream_impl(sfe_rs_t h, const void *d_in, size_t n_in, siz
                       "reference's out_len-exhausted state)");
             return SFE_ESTATE;
         }
-        if (rc == SFE_ESTATE) rc = launch_poly_seg(sa, r->data_complex, r->exact_stream, r->n_channels, s);
         if (rc == SFE_ESTATE) {
-            // a call's input does not fit an LDS tile (huge blksize): expand on the host and use
+            // the direct kernel's LDS: a call larger than it is dealt to `split` workgroups, each tile sized by the largest input
+            // span any part of any call of this launch really reaches (segtile.h).  Per memoised plan and split that span is
+            // worked out once (Rs::SegPlanRef::max_span); the calls outside the memo are walked here.
+            auto max_span = [&](int split) -> long long {
+                int li = 0;
+                while ((1 << li) < split) li++;
+                long long mx = 0;
+                for (size_t i = 0; i < chunks.size(); i++) {
+                    const SegChunk &c = chunks[i];
+                    long long v;
+                    if (c.n_out <= 0) {
+                        v = 0;                          // (every workgroup of the call returns at once)
+                    } else if (chunk_ref[i] >= 0) {
+                        Rs::SegPlanRef &ref = r->seg_refs[(size_t)chunk_ref[i]];
+                        if (ref.max_span[li] < 0)
+                            ref.max_span[li] = (int)seg_max_span(r->seg_table.data() + ref.seg_first, c.m, c.n_out, r->U, r->plen, split);
+                        v = ref.max_span[li];
+                    } else {
+                        v = seg_max_span(&seg_at((size_t)c.seg_first), c.m, c.n_out, r->U, r->plen, split);
+                    }
+                    mx = v > mx ? v : mx;
+                }
+                return mx;
+            };
+            SegTilePlan tp;
+            if (seg_tile_plan(r->U, r->plen, r->esz(), max_m, max_span, &tp) == SFE_OK) {
+                sa.split = tp.split;
+                sa.tile_cap = tp.tile_cap;
+                sa.taps_global = tp.taps_global;
+                rc = launch_poly_seg(sa, r->data_complex, r->exact_stream, r->n_channels, s);
+            }
+        }
+        if (rc == SFE_ESTATE) {
+            // a part of a call reaches more input than the LDS holds, at any split (huge blksize): expand on the host and use
             // the per-output schedule kernel
             std::vector<long long> pos(K);
             std::vector<float> mu(K);

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "common.h"
+#include "segtile.h"
 #include "timelaw.h"
 
 namespace sfe {
@@ -179,6 +180,8 @@ struct Rs {
         sfe_rs_timestate after;
         int next = -1;                     // index of the plan for the state this call ends in, once it has been met:
                                            // a stream of full-size calls then walks the plans by index, no hashing
+        int max_span[7] = {-1, -1, -1, -1, -1, -1, -1};     // per log2(split): the largest tile a part of this call needs
+                                                            // (segtile.h: seg_max_span), once it has been asked for
     };
     std::unordered_map<uint64_t, int> seg_memo;      // start state -> index into seg_refs
     std::vector<SegPlanRef> seg_refs;

@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "segtile.h"
 
 // hipcc contracts a*b+c into an FMA by default (and HIP's __fmul_rn/__fadd_rn are plain * and +
 // defined in a header, so they contract too).  This file is compiled with -ffp-contract=off
@@ -925,16 +926,13 @@ __global__ __launch_bounds__(256) void poly_sched_kernel(PolyArgs a)
 }
 
 // ------------------------------------------------------- general rate, run-length form
-struct DevSeg {          // == sfe::TlSeg (timelaw.h), restated here to keep this file HIP-only
+struct DevSeg {          // == sfe::TlSeg (timelaw.h), restated with the device's types
     double t0;
     float  d;
     int    k0, count, pad;
 };
-constexpr int SEG_MAX_LDS = 96;
-// >= plen + 1 (the shifted rows read one tap further), a multiple of 4 floats, and never a multiple of 64 floats: a wave's
-// lanes read up to U different rows at once (one per phase), and rows a multiple of 256 bytes apart would put the same
-// tap of every phase on the same banks -- a U-way conflict on every 16-byte tap read
-__host__ __device__ constexpr int seg_row(int plen) { return ((plen + 4) & ~3) % 64 == 0 ? ((plen + 4) & ~3) + 4 : (plen + 4) & ~3; }
+static_assert(sizeof(DevSeg) == sizeof(TlSeg) && sizeof(DevSeg) == SEG_RUN_BYTES, "the run table is uploaded as TlSeg[]");
+// SEG_MAX_LDS, seg_row and the tile a part of a split call stages: segtile.h
 
 template <bool CPLX, bool EXACT>
 __global__ __launch_bounds__(256) void poly_seg_kernel(PolySegArgs a)
@@ -975,6 +973,7 @@ __global__ __launch_bounds__(256) void poly_seg_kernel(PolySegArgs a)
         for (int j = threadIdx.x; j < plp; j += 256) tsh[j] = j + 1 < a.plen ? a.taps[j + 1] : 0.0f;
     }
     // this workgroup's outputs [ka, kb) of the call and the first sample of its tile relative to the call's first (split == 1: all of them, - plen)
+    // (segtile.h: seg_part_span restates this arithmetic on the host, which sizes the tile by it: the two change together)
     const int ka = (int)((long long)c.n_out * part / a.split), kb = (int)((long long)c.n_out * (part + 1) / a.split);
     if (ka >= kb) return;
     int rel0 = -a.plen, n_tile = c.m + a.plen;          // tile: samples in_off - plen .. in_off + m - 1   (pos >= -1 reaches back plen samples)
@@ -993,7 +992,7 @@ __global__ __launch_bounds__(256) void poly_seg_kernel(PolySegArgs a)
         if (part > 0) rel0 = (int)n_first - a.plen;
         long long span = n_last - rel0 + 1;
         if (span > c.m - rel0) span = c.m - rel0;        // nothing beyond the call's own samples is ever read
-        n_tile = span > a.tile_cap ? a.tile_cap : (int)span;      // (the launcher sizes tile_cap with room to spare)
+        n_tile = (int)span;                              // <= a.tile_cap: the host sized the tile from every part's span (segtile.h: seg_part_span)
     }
     const long long tile0 = c.in_off + rel0;
     if (tile0 >= 0 && tile0 + n_tile <= a.n_in) {
@@ -1570,27 +1569,14 @@ int launch_poly_sched(const PolyArgs &a, int data_complex, int exact, int n_chan
     return SFE_OK;
 }
 
-int launch_poly_seg(const PolySegArgs &a0, int data_complex, int exact, int n_channels, hipStream_t s)
+int launch_poly_seg(const PolySegArgs &a, int data_complex, int exact, int n_channels, hipStream_t s)
 {
-    if (a0.n_chunks <= 0) return SFE_OK;
-    const size_t esz = data_complex ? 8 : 4;
-    PolySegArgs a = a0;
-    const size_t taps_b = (size_t)(a.U + 1) * seg_row(a.plen) * 4;
-    // a call's samples beside the runs and the taps; a call that does not fit is dealt to `split` workgroups, each with the span its outputs
-    // reach: max_m / split samples + what one output's step and the float32 recurrence's wobble can add (a.span_slack, api_rs.hip) + plen
-    a.split = 1;
-    auto tile = [&](int split) { return split == 1 ? (size_t)a.max_m + a.plen + 1 : (size_t)(a.max_m + split - 1) / split + a.span_slack + a.plen + 2; };
-    auto need = [&](int split, bool tg) { return SEG_MAX_LDS * sizeof(DevSeg) + (tg ? 0 : taps_b) + tile(split) * esz; };
-    a.taps_global = taps_b > 24 * 1024 && need(1, false) > 64 * 1024;
-    while (a.split < 64 && need(a.split, a.taps_global) > 64 * 1024) a.split *= 2;
-    if (need(a.split, a.taps_global) > 64 * 1024 && !a.taps_global) {
-        a.taps_global = 1;
-        a.split = 1;
-        while (a.split < 64 && need(a.split, true) > 64 * 1024) a.split *= 2;
-    }
-    const size_t sh = need(a.split, a.taps_global);
-    if (sh > 64 * 1024 || (long long)a.n_chunks * a.split > 0x7fffffffLL) return SFE_ESTATE;
-    a.tile_cap = (int)tile(a.split);
+    if (a.n_chunks <= 0) return SFE_OK;
+    // a.split, a.tile_cap, a.taps_global: the caller's seg_tile_plan (segtile.h), from every part's real span
+    const size_t sh = seg_lds_bytes(a.U, a.plen, data_complex ? 8 : 4, a.tile_cap, a.taps_global != 0);
+    if (a.split < 1 || a.split > SEG_MAX_SPLIT || a.tile_cap <= 0 || sh > SEG_LDS_BYTES ||
+        (long long)a.n_chunks * a.split > 0x7fffffffLL)
+        return SFE_ESTATE;
     dim3 grid((unsigned)(a.n_chunks * a.split), (unsigned)n_channels), block(256);
 #define LAUNCH(C, E) hipLaunchKernelGGL((poly_seg_kernel<C, E>), grid, block, sh, s, a)
     if (data_complex) { if (exact) LAUNCH(true, true); else LAUNCH(true, false); }

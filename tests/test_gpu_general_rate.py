@@ -96,8 +96,8 @@ def test_transform_domain_general_rate_against_the_oracle(api, L, orc, g4, rate)
     for part in (0, 1):
         ref, _ = orc.Resample(taps, U, 4096).stream(np.ascontiguousarray(x[part::2]), float(np.float32(rate)))
         got = y[part::2]
-        assert len(ref) - len(got) in (0, 1)
-        assert synth.rel_rms(got, ref[: len(got)]) <= TOL
+        assert len(got) == len(ref), (rate, part, len(got), len(ref))
+        assert synth.rel_rms(got, ref) <= TOL
 
 
 def test_default_dispatch_takes_the_transform_kernel_for_bulk_calls_only(api, L):
@@ -152,7 +152,7 @@ def test_transform_domain_general_rate_u8_input(api, L, orc, cplx, rate):
     for part in range(w):
         ref, _ = orc.Resample(taps, U, B).stream(np.ascontiguousarray(xf[part::w]), rate)
         got = outs["u8"][part::w]
-        assert len(ref) - len(got) in (0, 1) and synth.rel_rms(got, ref[: len(got)]) <= TOL
+        assert len(got) == len(ref) and synth.rel_rms(got, ref) <= TOL, (cplx, rate, part, len(got), len(ref))
 
 
 @pytest.mark.parametrize("cplx", [True, False])

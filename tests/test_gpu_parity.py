@@ -1023,11 +1023,88 @@ def test_general_rate_calls_larger_than_the_lds(api, L, orc, B, U, rate, n_taps,
         y = r.resample_array(x, rate, chunk=3 * B)[0]
         for part in range(w):
             got, ref = y[part::w], refs[part]
-            assert len(ref) - len(got) in (0, 1) and len(got) > 0, (B, U, rate, len(ref), len(got))
+            assert len(got) == len(ref) and len(got) > 0, (B, U, rate, len(ref), len(got))
             if exact:
-                assert np.array_equal(got.view(np.uint32), ref[: len(got)].view(np.uint32)), (B, U, rate, cplx)
+                assert np.array_equal(got.view(np.uint32), ref.view(np.uint32)), (B, U, rate, cplx)
             else:
-                assert synth.rel_rms(got, ref[: len(got)]) <= TOL, (B, U, rate, cplx)
+                assert synth.rel_rms(got, ref) <= TOL, (B, U, rate, cplx)
+
+
+# (complex, blksize, U, rate): calls dealt to 32 or 64 workgroups where the tile rule before csrc/segtile.h -- max_m / split +
+# ceil(rate) + 64 + plen + 2 samples -- was short of a part's real span by 2 to 153 samples (tests/host/test_seg_split.cpp), and a
+# complex call of 524288 samples that no split fits in 64 KiB: the host-scheduled path.  None of them leaves the reference in its
+# out_len-exhausted state.
+LARGE_SPLIT_SHAPES = [(True, 393216, 3, 1.0233), (True, 393216, 7, 0.77), (True, 393216, 2, 0.77), (True, 393216, 16, 0.77),
+                      (False, 393216, 3, 1.0233), (False, 393216, 7, 1.77), (False, 524288, 3, 1.0233), (True, 524288, 3, 1.0233)]
+
+
+def _rs_per_call(api, r, x, rate, B, w):
+    """x (n_channels, w * n) through r, one reference call (B samples) per process_stream: (outputs, per-call counts)."""
+    nch, n = x.shape[0], x.shape[1] // w
+    cap = int(n / rate) + 4 * (n // B + 1) + 64
+    d_in = api.DeviceArray.from_numpy(np.ascontiguousarray(x))
+    d_out = api.DeviceArray.from_numpy(np.full((nch, w * cap), np.nan, np.float32))       # an output never stored stays NaN
+    ks = []
+    for off in range(0, n, B):
+        m, k = min(B, n - off), sum(ks)
+        ks.append(r.process_stream(d_in.ptr + 4 * w * off, m, d_out.ptr + 4 * w * k, cap - k, rate, in_stride=n, out_stride=cap))
+    y = d_out.to_numpy().reshape(nch, w * cap)[:, : w * sum(ks)]
+    d_in.free()
+    d_out.free()
+    return y, ks
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("plen", [32, 8])
+@pytest.mark.parametrize("cplx,B,U,rate", LARGE_SPLIT_SHAPES)
+def test_general_rate_split_calls_at_large_blksize(api, L, orc, cplx, B, U, rate, plen):
+    """A call of the direct general-rate kernel larger than the LDS is dealt to up to 64 workgroups, each staging the input ITS
+    outputs reach.  The float32 time law steps by a different amount in every binade, so equal runs of outputs reach unequal
+    spans; the tile was sized max_m / split + a fixed slack and the kernel clamped a longer span to it, reading unstaged LDS with
+    SFE_OK.  The tile is now the largest real span (csrc/segtile.h) or the call takes the host-scheduled path.  5 1/3 calls per
+    stream.  Exact mode: the oracle's bits and ITS per-call output counts, one reference call per process_stream, then three;
+    SFE_RS_ALGO_DIRECT in fused arithmetic and, at 8 taps per phase, the default algorithm (the direct kernel too: fewer than 12
+    taps per phase): within 1e-5 and the same count.  Two channels on the first shape (blockIdx.y)."""
+    rate = float(np.float32(rate))
+    taps = synth.lowpass_taps(plen * U, 0.9 * min(1.0 / U, 1.0 / max(rate * U, 1.0)), gain=float(U))
+    w = 2 if cplx else 1
+    n = 5 * B + B // 3
+    nch = 2 if (cplx, B, U, plen) == (True, 393216, 3, 32) else 1
+    x = np.stack([synth.synth_f32(w * n, ch=150 + c) for c in range(nch)])
+    refs, ref_ks = [], None
+    for c in range(nch):
+        for part in range(w):
+            ref, ks = orc.Resample(taps, U, B).stream(np.ascontiguousarray(x[c, part::w]), rate)
+            assert ref_ks is None or ks == ref_ks
+            refs.append(ref)
+            ref_ks = ks
+    assert len(ref_ks) == 6 and min(ref_ks) > 0, ref_ks
+
+    def check(y, exact, what):
+        for c in range(nch):
+            for part in range(w):
+                got, ref = y[c, part::w], refs[c * w + part]
+                assert len(got) == len(ref), (what, c, part, len(got), len(ref))
+                if exact:
+                    bad = np.flatnonzero(got.view(np.uint32) != ref.view(np.uint32))
+                    assert bad.size == 0, (what, c, part, bad.size, bad[:8])
+                else:
+                    assert synth.rel_rms(got, ref) <= TOL, (what, c, part, synth.rel_rms(got, ref))
+
+    def handle(exact, algo):
+        r = api.Rs(taps, U, B, mode=L.RS_RESAMPLE, data_complex=cplx, n_channels=nch)
+        r.set_exact(exact)
+        if algo is not None:
+            r.set_algo(algo)
+        return r
+
+    y, ks = _rs_per_call(api, handle(True, None), x, rate, B, w)
+    assert ks == ref_ks, (ks, ref_ks)
+    check(y, True, "exact, one call per process_stream")
+    check(handle(True, None).resample_array(x, rate, chunk=3 * B), True, "exact, three calls per process_stream")
+    check(handle(False, L.RS_ALGO_DIRECT).resample_array(x, rate, chunk=3 * B), False, "direct, fused")
+    if plen == 8:
+        check(handle(False, None).resample_array(x, rate, chunk=3 * B), False, "default algorithm")
 
 
 @pytest.mark.parametrize("U,step", [(9, 10), (24, 25), (10, 9), (32, 33), (16, 1), (32, 1), (12, 5), (64, 3), (9, 2), (160, 147), (147, 160), (256, 255), (100, 3)])

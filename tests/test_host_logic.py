@@ -264,6 +264,22 @@ def test_time_law_closed_form_matches_literal_replay(tmp_path):
     assert r.returncode == 0 and "timelaw ok" in r.stdout, r.stdout + r.stderr
 
 
+def test_split_general_rate_tiles_hold_every_part_span(tmp_path):
+    """csrc/segtile.h: a reference call larger than the LDS is dealt to up to 64 workgroups of the direct general-rate kernel,
+    each staging the input its outputs reach.  The tile is sized from every part's real span: over blksize 4096 ... 2^20, 7 upsample
+    factors, 9 rates, 4 filter lengths (and two whose taps leave the LDS), real and complex, 8 calls and a ragged one with the
+    state carried (out_len-exhausted calls included), each launch either refuses or holds every part -- checked against the
+    kernel's own tile indexing.  The launcher's rule before it (max_m / split + ceil(rate) + 64 + plen + 2) must overflow on
+    complex blksize 393216, U 3, rate 1.0233 (tests/host/test_seg_split.cpp)."""
+    exe = str(tmp_path / "ss")
+    r = _cxx(["g++", "-O2", "-Wall", "-std=c++14", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+              os.path.join(ROOT, "tests/host/test_seg_split.cpp"), "-o", exe])
+    assert r.returncode == 0, r.stderr
+    r = _cxx([exe], timeout=600)
+    assert r.returncode == 0 and "segsplit ok" in r.stdout, r.stdout + r.stderr
+    assert "worst part over by 44 (call 3, part 62)" in r.stdout, r.stdout
+
+
 def test_bench_gpus_n_without_a_gpu_fails_loudly():
     """`python bench.py --gpus 2` on a host without a GPU: non-zero exit, no JSON line (the round-1
     script printed an n_gpus=1 line for --gpus 8; ADVICE bench.py:125)."""
