@@ -447,6 +447,52 @@ int sfe_dsp_chan_process_stream(sfe_chan_t h, const void *d_in, size_t n_in, siz
 int sfe_dsp_chan_reset(sfe_chan_t h);
 int sfe_dsp_chan_destroy(sfe_chan_t h);
 
+/* ------------------------------------------------- polyphase synthesis filter bank (combiner)
+ * The transpose of the channelizer: M baseband channels at rate 1/D, each interpolated by D,
+ * shifted up to its own sub-band and summed into one complex stream, in one pass.  With a real
+ * prototype low-pass g[0..L) and channel inputs X_k[m] (k < M; m the absolute instant since
+ * create / reset; X = 0 before the first instant), output sample i (absolute) is
+ *     z[i] = sum_{m : 0 <= i - mD < L}  g[i - mD] * sum_{k<M} X_k[m] exp(+j 2 pi k i / M)
+ * channel k zero-stuffed by D, filtered by g and shifted up by k/M cycles per sample (channels
+ * k >= M/2 are the negative frequencies, numbered as the channelizer numbers them), no 1/M
+ * factor.  Causal: a call over instants [m0, m0 + n) emits exactly the n D samples
+ * [m0 D, (m0 + n) D), each complete.  Shapes: M a power of two in [4, 1024], D = M or M/2,
+ * 1 <= n_taps <= 32 M; anything else is SFE_EINVAL.  The channelizer (D = M/2, h =
+ * lowpass(16M+1, 2/M)) followed by this combiner (D = M/2, g = lowpass(16M+1, 1/M)) gives the
+ * input back delayed by 16 M samples, times about 2/M.
+ * Computed by csrc/combine.hip: one M-point transform per instant in LDS, the output FIR in
+ * registers. */
+typedef void *sfe_combine_t;  /* opaque: one combiner over n_streams output streams */
+/* Host-only (no GPU): validates the shape; *taps_per_branch = P = ceil(n_taps / D) (taps per
+ * output phase), *history = the instants of carried state per stream the device keeps (>= P - 1:
+ * the kernel's delay line).  Either output pointer may be NULL. */
+int sfe_dsp_combine_plan(int n_taps, int n_chans, int interp, int *taps_per_branch, int *history);
+/*   taps       n_taps real float32 (copied, zero-padded to whole output phases)
+ *   n_chans    M;  interp  D
+ *   n_streams  independent streams sharing the taps, each with its own history and instant
+ *              counter.  SFE_ENODEV without a GPU: nothing computes on the CPU. */
+int sfe_dsp_combine_create(const float *taps, int n_taps, int n_chans, int interp, int n_streams,
+                           int device, sfe_combine_t *out);
+/* SFE_FMT_F32 (cf32 output, 8-byte aligned) or SFE_FMT_TX10 (the transmit wire format written by
+ * the same launch: 4 floats, i.e. 2 complex samples, in 5 bytes, the bits of
+ * sfe_dsp_tx_f32_to_10bit on the F32 output; stream s at byte d_out + s*(out_stride/2)*5, (n_out/2)*5
+ * bytes, no alignment needed; out_stride must be even). */
+int sfe_dsp_combine_set_output_format(sfe_combine_t h, int fmt);
+/* n_in instants of every channel of every stream: channel k of stream s at d_in + (s*M + k)*in_stride
+ * (cf32 samples, 8-byte aligned -- the channelizer's output layout); stream s's output at
+ * d_out + s*out_stride samples.  *n_out = n_in * D per stream; n_in = 0 is a no-op.
+ * out_stride < *n_out is SFE_ERANGE; in_stride < n_in, misaligned buffers, overlapping input and
+ * output byte ranges, an odd out_stride under SFE_FMT_TX10, or a stream whose input or output
+ * reaches 2^31 samples are SFE_EINVAL; nothing is launched on a refusal.  Cutting a stream into
+ * calls at any instant gives the one-call result bit for bit.  Asynchronous on `stream`, no host
+ * synchronisation or allocation.  The instant counter lives on the host: a call on a stream under
+ * graph capture is SFE_ESTATE, nothing enqueued. */
+int sfe_dsp_combine_process_stream(sfe_combine_t h, const void *d_in, size_t n_in, size_t in_stride,
+                                   void *d_out, size_t out_stride, size_t *n_out, sfe_stream_t stream);
+/* Zero the carried state and the instant counter (a fresh handle). */
+int sfe_dsp_combine_reset(sfe_combine_t h);
+int sfe_dsp_combine_destroy(sfe_combine_t h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,8 @@ Two layers, both thin:
     `process(in_array, out_len, rate) -> (n_out, out_array)` for the resamplers, so the
     reference's driver scripts (libdsp/test/test_decimate.py:22-25) read the same.
   * `Fir`, `Rs`, `DeviceArray` -- the device-resident bulk path used by bench.py and the
-    parity tests (sfe_dsp_*_process_stream); `Chan`, the polyphase channelizer (sfe_dsp_chan_*).
+    parity tests (sfe_dsp_*_process_stream); `Chan`, the polyphase channelizer (sfe_dsp_chan_*); `Combiner`, its
+    transpose, the synthesis filter bank (sfe_dsp_combine_*).
 
 Everything computes on the GPU through the C ABI; numpy is only the host container.
 """
@@ -479,6 +480,74 @@ class Chan:
     def close(self):
         if getattr(self, "_h", None):
             self._L.sfe_dsp_chan_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+def combine_plan(n_taps, n_chans, interp):
+    """sfe_dsp_combine_plan (host only, no GPU): (taps per output phase P, instants of history carried per stream)."""
+    P, H = C.c_int(0), C.c_int(0)
+    check(_l.load().sfe_dsp_combine_plan(int(n_taps), int(n_chans), int(interp), C.byref(P), C.byref(H)))
+    return P.value, H.value
+
+
+class Combiner:
+    """Polyphase synthesis filter bank (sfe_dsp_combine_*): n_chans = M baseband channels of n_streams streams, each
+    interpolated by `interp` (M or M/2), shifted up to its sub-band and summed; real prototype taps."""
+
+    def __init__(self, taps, n_chans, interp, n_streams=1, device=0):
+        self._L = _l.load()
+        t = _f32(taps)
+        self.n_chans, self.interp, self.n_streams = int(n_chans), int(interp), int(n_streams)
+        self.out_tx10 = False
+        h = C.c_void_p()
+        check(self._L.sfe_dsp_combine_create(t.ctypes.data, t.size, self.n_chans, self.interp, self.n_streams, device,
+                                             C.byref(h)))
+        self._h = h.value
+
+    def set_output_format(self, fmt):
+        """lib.FMT_F32 (cf32) or lib.FMT_TX10 (the transmit wire format, 2 complex samples in 5 bytes)."""
+        check(self._L.sfe_dsp_combine_set_output_format(self._h, fmt))
+        self.out_tx10 = fmt == _l.FMT_TX10
+
+    def reset(self):
+        check(self._L.sfe_dsp_combine_reset(self._h))
+
+    def process_stream(self, d_in, n_in, d_out, in_stride=None, out_stride=None, stream=None):
+        """d_in / d_out: DeviceArray or raw device pointers; n_in instants per channel.  Channel k of stream s is read at
+        d_in + (s*M + k)*in_stride cf32 samples; stream s is written at d_out + s*out_stride samples (TX10: at
+        s*(out_stride/2)*5 bytes).  Returns n_out = n_in * interp."""
+        pi = d_in.ptr if isinstance(d_in, DeviceArray) else int(d_in)
+        po = d_out.ptr if isinstance(d_out, DeviceArray) else int(d_out)
+        n_out = C.c_size_t(0)
+        check(self._L.sfe_dsp_combine_process_stream(self._h, pi, int(n_in), int(n_in) if in_stride is None else int(in_stride),
+                                                     po, int(n_in) * self.interp if out_stride is None else int(out_stride),
+                                                     C.byref(n_out), stream))
+        return n_out.value
+
+    def combine(self, X):
+        """Host convenience, computed on the GPU: X is (n_streams, M, n) complex ((M, n) for one stream); returns
+        (n_streams, n * interp) complex64 -- or, with FMT_TX10, (n_streams, n * interp // 2 * 5) uint8."""
+        z = np.ascontiguousarray(X, dtype=np.complex64).reshape(self.n_streams, self.n_chans, -1)
+        n = z.shape[2]
+        n_out = n * self.interp
+        d_in = DeviceArray.from_numpy(z.view(np.float32))
+        row_b = n_out // 2 * 5 if self.out_tx10 else 8 * n_out
+        d_out = DeviceArray(max(1, (self.n_streams * row_b + 3) // 4))
+        try:
+            k = self.process_stream(d_in, n, d_out)
+            y = d_out.to_numpy()
+        finally:
+            d_in.free()
+            d_out.free()
+        if self.out_tx10:
+            return y.view(np.uint8)[: self.n_streams * (k // 2 * 5)].reshape(self.n_streams, -1)
+        return y[: self.n_streams * 2 * k].view(np.complex64).reshape(self.n_streams, k)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.sfe_dsp_combine_destroy(self._h)
             self._h = None
 
     __del__ = close

@@ -111,6 +111,12 @@ SIGNATURES = {
     "sfe_dsp_chan_process_stream": (i32, [vp, vp, sz, sz, vp, sz, C.POINTER(sz), vp]),
     "sfe_dsp_chan_reset": (i32, [vp]),
     "sfe_dsp_chan_destroy": (i32, [vp]),
+    "sfe_dsp_combine_plan": (i32, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
+    "sfe_dsp_combine_create": (i32, [vp, i32, i32, i32, i32, i32, C.POINTER(vp)]),
+    "sfe_dsp_combine_set_output_format": (i32, [vp, i32]),
+    "sfe_dsp_combine_process_stream": (i32, [vp, vp, sz, sz, vp, sz, C.POINTER(sz), vp]),
+    "sfe_dsp_combine_reset": (i32, [vp]),
+    "sfe_dsp_combine_destroy": (i32, [vp]),
 }
 
 # the diagnostic library only (simplefe_amd/csrc/diag/sfe_dsp_diag.h; scripts/ load it by pointing LIB_PATH at it): bound when present

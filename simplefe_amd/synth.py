@@ -148,3 +148,46 @@ def chan_reference_direct(x, h, n_chans, decim, first, m0, n_out):
     G = h[:, None] * np.exp(2j * np.pi * ((n[:, None] * k[None, :]) % M) / M)             # [L, M]
     lead = np.exp(-2j * np.pi * (((m * D)[:, None] % M) * k[None, :] % M) / M)          # [n_out, M]
     return ((X @ G) * lead).T
+
+
+def combine_reference(X, g, n_chans, interp, first=0):
+    """The combiner's contract (sfe_dsp_combine_*) in float64: X is (M, n) complex, the channel inputs of instants
+    first .. first+n-1 (earlier instants are zero).  v = M * ifft(X) over the channels gives v_q[m] =
+    sum_k X_k[m] exp(+j 2 pi k q / M); each instant m then adds g[t] * v_{(mD + t) mod M}[m] to output sample mD + t
+    (overlap-add, t < L).  Returns the n*D complex128 samples [first*D, (first+n)*D)."""
+    X = np.asarray(X).astype(np.complex128)
+    g = np.asarray(g, dtype=np.float64).ravel()
+    M, D, L = int(n_chans), int(interp), g.size
+    n = X.shape[1]
+    v = np.fft.ifft(X, axis=0) * M                                   # [M, n]
+    z = np.zeros(n * D + L, dtype=np.complex128)
+    t = np.arange(L)
+    for m in range(n):
+        z[m * D:m * D + L] += g * v[((first + m) * D + t) % M, m]
+    return z[:n * D]
+
+
+def combine_reference_direct(X, g, n_chans, interp, first, i0, n_out):
+    """The same contract evaluated from its formula for a window of a long stream: outputs i0 .. i0+n_out-1 (absolute),
+    z[i] = sum_m g[i - mD] sum_k X_k[m] exp(+j 2 pi k i / M), with X (M, n) holding instants first .. first+n-1 (which
+    must include every instant the window reaches, or start at 0).  The channel sums are an explicit DFT matrix
+    product, the taps a gather per output phase: no FFT."""
+    X = np.asarray(X).astype(np.complex128)
+    g = np.asarray(g, dtype=np.float64).ravel()
+    M, D, L = int(n_chans), int(interp), g.size
+    i = i0 + np.arange(n_out)
+    m_lo = -(-(i0 - L + 1) // D)                                     # ceil: the earliest instant the window reaches
+    if first > 0:
+        assert first <= max(m_lo, 0), "the window must hold every instant its outputs reach"
+    m_hi = (i0 + n_out - 1) // D
+    ms = np.arange(max(m_lo, first), m_hi + 1)
+    k = np.arange(M)
+    E = np.exp(2j * np.pi * ((k[:, None] * k[None, :]) % M) / M)    # [k, q]
+    V = E.T @ X[:, ms - first]                                       # [q, m]: v_q[m]
+    z = np.zeros(n_out, dtype=np.complex128)
+    for j in range(-(-L // D)):
+        m = i // D - j
+        tap = i - m * D
+        ok = (tap < L) & (m >= ms[0]) & (m <= ms[-1])
+        z[ok] += g[tap[ok]] * V[i[ok] % M, m[ok] - ms[0]]
+    return z
