@@ -493,6 +493,61 @@ int sfe_dsp_combine_process_stream(sfe_combine_t h, const void *d_in, size_t n_i
 int sfe_dsp_combine_reset(sfe_combine_t h);
 int sfe_dsp_combine_destroy(sfe_combine_t h);
 
+/* ------------------------------------------------- digital down-converter bank
+ * K tunings of one stream, each shifted to baseband at its own frequency, low-pass filtered by
+ * one real prototype h[0..L) and decimated by any integer D, from one pass over the input (the
+ * frequency-translating FIR, K at a time).  Each frequency f_k in [-0.5, 0.5] cycles per sample
+ * is quantised to a 32-bit NCO increment inc_k = llround(f_k 2^32) mod 2^32 (NaN or any other
+ * value is SFE_EINVAL).  With i the absolute input index since create / reset (x = 0 before it):
+ *     phi_k(i) = (i inc_k) mod 2^32
+ *     y_k[m]   = sum_{n<L} h[n] x[mD - n] exp(-j 2 pi phi_k(mD - n) / 2^32)
+ * a true baseband signal, no 1/D factor.  Shapes: 1 <= D <= 1024, 1 <= L <= 8192 with
+ * P = ceil(L/D) <= 64, 1 <= K <= 64; anything else is SFE_EINVAL.  Input: complex (cf32, or u8
+ * (I,Q) pairs) or real float32; the output is always cf32.
+ * Computed by csrc/ddc.hip: the taps are rotated per tuning on the host (g_k[n] = h[n]
+ * exp(+j 2 pi phi_k(n) / 2^32)), the kernel is one complex-tap decimating FIR over the shared
+ * input samples, and each output is multiplied by exp(-j 2 pi phi_k(mD) / 2^32). */
+typedef void *sfe_ddc_t;  /* opaque: one down-converter bank over n_streams input streams */
+/* Host-only (no GPU): validates the shape and the frequencies; *taps_per_branch = P,
+ * *history = the samples of carried state per stream the device keeps (>= L - 1: whole tap
+ * chunks of the kernel), phase_inc[0..K) = the quantised increments.  Any output pointer may be
+ * NULL. */
+int sfe_dsp_ddc_plan(int n_taps, int decim, int n_tunings, const double *freqs,
+                     int *taps_per_branch, int *history, uint32_t *phase_inc);
+/*   taps          n_taps real float32 (copied)
+ *   decim         D;  n_tunings  K;  freqs  K frequencies in cycles per sample
+ *   data_complex  1: complex input (cf32, or u8 with sfe_dsp_ddc_set_input_format), 0: real float32
+ *   n_streams     independent streams sharing the taps and tunings, each with its own history
+ *                 and sample counter.  SFE_ENODEV without a GPU: nothing computes on the CPU. */
+int sfe_dsp_ddc_create(const float *taps, int n_taps, int decim, int n_tunings, const double *freqs,
+                       int data_complex, int n_streams, int device, sfe_ddc_t *out);
+/* SFE_FMT_F32 (cf32 input, 8-byte aligned; real float32, 4-byte aligned, for a real handle) or
+ * SFE_FMT_U8 ((I,Q) byte pairs, 2-byte aligned, converted (b-128)*(1/127) on load exactly as
+ * sfe_dsp_rx_u8_to_f32; complex handles only, SFE_EINVAL on a real one).  The carried state of a
+ * complex handle is kept as cf32, so the format may change between calls; u8 input gives the
+ * bits of the cf32 path on the converted samples. */
+int sfe_dsp_ddc_set_input_format(sfe_ddc_t h, int fmt);
+/* K new frequencies (validated as in create), used over the whole window of every output of
+ * every later call: from the first output of the next call on, the result equals, bit for bit,
+ * a fresh handle created with the new frequencies and fed the whole stream.  There is NO phase
+ * continuity across a retune: each output's phase is that of its absolute sample index under
+ * the new increments.  May block until the handle's earlier calls have finished; never changes
+ * what an already-enqueued call computes. */
+int sfe_dsp_ddc_set_freqs(sfe_ddc_t h, const double *freqs);
+/* n_in samples of every stream: stream s at d_in + s*in_stride (samples of the input format);
+ * tuning k of stream s at d_out + (s*K + k)*out_stride (cf32 samples, 8-byte aligned).  n_in a
+ * multiple of D below 2^31 (else SFE_EINVAL); *n_out = n_in / D per tuning; n_in = 0 is a no-op.
+ * out_stride < *n_out is SFE_ERANGE; overlapping input and output byte ranges, misaligned
+ * buffers and in_stride < n_in with more than one stream are SFE_EINVAL; nothing is launched on
+ * a refusal.  Cutting a stream into calls at any multiple of D gives the one-call result bit for
+ * bit.  Asynchronous on `stream`, no host synchronisation or allocation.  The sample counter
+ * lives on the host: a call on a stream under graph capture is SFE_ESTATE, nothing enqueued. */
+int sfe_dsp_ddc_process_stream(sfe_ddc_t h, const void *d_in, size_t n_in, size_t in_stride,
+                               void *d_out, size_t out_stride, size_t *n_out, sfe_stream_t stream);
+/* Zero the carried state and the sample counter; the tunings are kept. */
+int sfe_dsp_ddc_reset(sfe_ddc_t h);
+int sfe_dsp_ddc_destroy(sfe_ddc_t h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -553,6 +553,93 @@ class Combiner:
     __del__ = close
 
 
+def ddc_plan(n_taps, decim, freqs):
+    """sfe_dsp_ddc_plan (host only, no GPU): (taps per branch P, samples of history carried per stream, the quantised
+    32-bit NCO increments as a list of ints)."""
+    f = np.ascontiguousarray(freqs, dtype=np.float64).ravel()
+    P, H = C.c_int(0), C.c_int(0)
+    inc = (C.c_uint32 * max(1, f.size))()
+    check(_l.load().sfe_dsp_ddc_plan(int(n_taps), int(decim), int(f.size), f.ctypes.data_as(C.POINTER(C.c_double)), C.byref(P),
+                                     C.byref(H), inc))
+    return P.value, H.value, [int(v) for v in inc[:f.size]]
+
+
+class Ddc:
+    """Digital down-converter bank (sfe_dsp_ddc_*): len(freqs) = K tunings of n_streams streams, each shifted down by its
+    frequency (cycles per sample, quantised to a 32-bit NCO increment), filtered by the real prototype `taps` and
+    decimated by `decim`.  data_complex=False takes real float32 input; the output is always complex."""
+
+    def __init__(self, taps, decim, freqs, data_complex=True, n_streams=1, device=0):
+        self._L = _l.load()
+        t = _f32(taps)
+        f = np.ascontiguousarray(freqs, dtype=np.float64).ravel()
+        self.decim, self.n_tunings, self.n_streams = int(decim), int(f.size), int(n_streams)
+        self.data_complex = bool(data_complex)
+        self.in_u8 = False
+        h = C.c_void_p()
+        check(self._L.sfe_dsp_ddc_create(t.ctypes.data, t.size, self.decim, self.n_tunings, f.ctypes.data_as(C.POINTER(C.c_double)),
+                                         int(self.data_complex), self.n_streams, device, C.byref(h)))
+        self._h = h.value
+
+    def set_input_format(self, fmt):
+        """lib.FMT_F32 (cf32, or float32 for a real handle) or lib.FMT_U8 ((I,Q) byte pairs, converted on load)."""
+        check(self._L.sfe_dsp_ddc_set_input_format(self._h, fmt))
+        self.in_u8 = fmt == _l.FMT_U8
+
+    def set_freqs(self, freqs):
+        """K new frequencies, used from the next call on (no phase continuity across the retune)."""
+        f = np.ascontiguousarray(freqs, dtype=np.float64).ravel()
+        if f.size != self.n_tunings:
+            raise ValueError("set_freqs: %d frequencies for %d tunings" % (f.size, self.n_tunings))
+        check(self._L.sfe_dsp_ddc_set_freqs(self._h, f.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def reset(self):
+        check(self._L.sfe_dsp_ddc_reset(self._h))
+
+    def process_stream(self, d_in, n_in, d_out, in_stride=None, out_stride=None, stream=None):
+        """d_in / d_out: DeviceArray or raw device pointers; n_in samples per stream (a multiple of decim).  Tuning k of
+        stream s goes to d_out + (s*K + k)*out_stride cf32 samples.  Returns n_out = n_in / decim."""
+        pi = d_in.ptr if isinstance(d_in, DeviceArray) else int(d_in)
+        po = d_out.ptr if isinstance(d_out, DeviceArray) else int(d_out)
+        n_out = C.c_size_t(0)
+        check(self._L.sfe_dsp_ddc_process_stream(self._h, pi, int(n_in), int(n_in) if in_stride is None else int(in_stride),
+                                                 po, int(n_in) // self.decim if out_stride is None else int(out_stride),
+                                                 C.byref(n_out), stream))
+        return n_out.value
+
+    def downconvert(self, x):
+        """Host convenience, computed on the GPU: x is (n_streams, n) complex -- real for a real handle, or, with FMT_U8,
+        (n_streams, 2n) uint8 (I,Q) pairs -- (1-D for one stream); returns (n_streams, K, n // decim) complex64."""
+        if self.in_u8:
+            b = np.ascontiguousarray(x, dtype=np.uint8).reshape(self.n_streams, -1)
+            n = b.shape[1] // 2
+            d_in = DeviceArray.from_bytes(b)
+        elif self.data_complex:
+            z = np.ascontiguousarray(x, dtype=np.complex64).reshape(self.n_streams, -1)
+            n = z.shape[1]
+            d_in = DeviceArray.from_numpy(z.view(np.float32))
+        else:
+            z = np.ascontiguousarray(x, dtype=np.float32).reshape(self.n_streams, -1)
+            n = z.shape[1]
+            d_in = DeviceArray.from_numpy(z)
+        n_out = n // self.decim
+        d_out = DeviceArray(max(1, self.n_streams * self.n_tunings * n_out) * 2)
+        try:
+            k = self.process_stream(d_in, n, d_out)
+            y = d_out.to_numpy(self.n_streams * self.n_tunings * k * 2)
+        finally:
+            d_in.free()
+            d_out.free()
+        return y.view(np.complex64).reshape(self.n_streams, self.n_tunings, k)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.sfe_dsp_ddc_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
 def rs_plan(state, upsample, n_in, out_len, rate):
     """Host-only replay of one process() call's time law (sfe_dsp_rs_plan).
     state: lib.TimeState (updated in place).  Returns (rel_pos int32[], mu float32[])."""

@@ -1,0 +1,289 @@
+// api_ddc.hip -- the down-converter bank handle behind sfe_ddc_t, sfe_dsp_ddc_* (include/sfe_dsp.h).  Host code only; the
+// kernels are in ddc.hip.
+#include "host.h"
+
+namespace sfe {
+
+// ddc.hip
+int ddc_tunings_per_chunk(int K);
+int launch_ddc(int fmt, const void *in, long long in_stride, const void *hist, void *hist_next, const v2f *taps,
+               const unsigned *inc, v2f *out, long long out_stride, long long n_in, int D, int P, int H, int K, int Kpad,
+               unsigned c0, int n_streams, hipStream_t st);
+
+namespace {
+
+constexpr int DDC_RU = 4;       // tap rows per chunk of the kernel (ddc.hip): P is padded to a multiple of it
+
+struct Ddc {
+    uint32_t magic = 0x44444331u;   // 'DDC1'
+    int D = 0, n_taps = 0, P = 0, Ppad = 0, H = 0, K = 0, Kpad = 0, KT = 1, n_streams = 1, device = 0, complex_in = 1, in_u8 = 0;
+    std::vector<float> h;           // the prototype, for the tables of set_freqs
+    v2f *d_taps = nullptr;          // [Kpad / KT][Ppad][D][KT]: g_k[n] = h[n] exp(+j 2 pi phi_k(n) / 2^32), zero-padded
+    unsigned *d_inc = nullptr;      // [Kpad]
+    void *d_hist[2] = {nullptr, nullptr};   // [n_streams][H] each (cf32, or float for real input): current and next
+    int cur = 0;
+    unsigned long long count = 0;   // input samples per stream since create / reset
+    size_t hist_bytes() const { return (size_t)n_streams * H * (complex_in ? sizeof(v2f) : sizeof(float)); }
+};
+
+Ddc *as_ddc(void *h)
+{
+    Ddc *c = static_cast<Ddc *>(h);
+    if (c && c->magic != 0x44444331u) {
+        set_error("not a live down-converter handle");
+        return nullptr;
+    }
+    return c;
+}
+
+void ddc_free(Ddc *c)
+{
+    if (!c) return;
+    if (c->d_taps) (void)hipFree(c->d_taps);
+    if (c->d_inc) (void)hipFree(c->d_inc);
+    for (auto *p : c->d_hist)
+        if (p) (void)hipFree(p);
+    c->magic = 0;
+    delete c;
+}
+
+int ddc_check_freqs(int K, const double *freqs, uint32_t *inc)
+{
+    if (!freqs) {
+        set_error("ddc: need %d frequencies", K);
+        return SFE_EINVAL;
+    }
+    for (int k = 0; k < K; k++) {
+        const double f = freqs[k];
+        if (!(f >= -0.5 && f <= 0.5)) {            // NaN fails both
+            set_error("ddc: frequency %d = %g is not in [-0.5, 0.5] cycles per sample", k, f);
+            return SFE_EINVAL;
+        }
+        if (inc) inc[k] = (uint32_t)(uint64_t)llround(f * 4294967296.0);      // mod 2^32
+    }
+    return SFE_OK;
+}
+
+int ddc_check_shape(int n_taps, int D, int K)
+{
+    if (D < 1 || D > 1024) {
+        set_error("ddc: decim = %d must be in [1, 1024]", D);
+        return SFE_EINVAL;
+    }
+    if (n_taps < 1 || n_taps > 8192) {
+        set_error("ddc: n_taps = %d must be in [1, 8192]", n_taps);
+        return SFE_EINVAL;
+    }
+    if ((n_taps + D - 1) / D > 64) {
+        set_error("ddc: n_taps = %d needs %d taps per branch at decim = %d; at most 64", n_taps, (n_taps + D - 1) / D, D);
+        return SFE_EINVAL;
+    }
+    if (K < 1 || K > 64) {
+        set_error("ddc: n_tunings = %d must be in [1, 64]", K);
+        return SFE_EINVAL;
+    }
+    return SFE_OK;
+}
+
+// the kernel's tap table for increments inc[0..K): chunk-major, KT tunings interleaved per tap
+std::vector<v2f> ddc_table(const Ddc *c, const uint32_t *inc)
+{
+    std::vector<v2f> t((size_t)c->Kpad * c->Ppad * c->D, v2f{0.0f, 0.0f});
+    for (int k = 0; k < c->K; k++)
+        for (int n = 0; n < c->n_taps; n++) {
+            const uint32_t ph = (uint32_t)((uint64_t)n * inc[k]);                 // phi_k(n), exact
+            const double a = 2.0 * M_PI * (double)(int32_t)ph / 4294967296.0;
+            const int j = n / c->D, r = n % c->D, kc = k / c->KT, kk = k % c->KT;
+            t[(((size_t)kc * c->Ppad + j) * c->D + r) * c->KT + kk] = v2f{(float)(c->h[n] * cos(a)), (float)(c->h[n] * sin(a))};
+        }
+    return t;
+}
+
+}  // namespace
+}  // namespace sfe
+
+using namespace sfe;
+
+extern "C" {
+
+int sfe_dsp_ddc_plan(int n_taps, int decim, int n_tunings, const double *freqs, int *taps_per_branch, int *history,
+                     uint32_t *phase_inc)
+{
+    int rc = ddc_check_shape(n_taps, decim, n_tunings);
+    if (rc != SFE_OK) return rc;
+    rc = ddc_check_freqs(n_tunings, freqs, phase_inc);
+    if (rc != SFE_OK) return rc;
+    const int P = (n_taps + decim - 1) / decim;
+    if (taps_per_branch) *taps_per_branch = P;
+    if (history) *history = (P + DDC_RU - 1) / DDC_RU * DDC_RU * decim;
+    return SFE_OK;
+}
+
+int sfe_dsp_ddc_create(const float *taps, int n_taps, int decim, int n_tunings, const double *freqs, int data_complex,
+                       int n_streams, int device, sfe_ddc_t *out)
+{
+    if (!out) return SFE_EINVAL;
+    *out = nullptr;
+    int rc = ddc_check_shape(n_taps, decim, n_tunings);
+    if (rc != SFE_OK) return rc;
+    std::vector<uint32_t> inc(n_tunings);
+    rc = ddc_check_freqs(n_tunings, freqs, inc.data());
+    if (rc != SFE_OK) return rc;
+    if (!taps || n_streams < 1 || n_streams > 65535) {
+        set_error("ddc_create: need taps and 1 <= n_streams <= 65535");
+        return SFE_EINVAL;
+    }
+    int prev_dev = -1;
+    (void)hipGetDevice(&prev_dev);
+    rc = use_device(device);
+    if (rc != SFE_OK) return rc;
+    struct Restore { int d; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore__{prev_dev};
+    Ddc *c = new (std::nothrow) Ddc;
+    if (!c) return SFE_ENOMEM;
+    c->D = decim;
+    c->n_taps = n_taps;
+    c->P = (n_taps + decim - 1) / decim;
+    c->Ppad = (c->P + DDC_RU - 1) / DDC_RU * DDC_RU;
+    c->H = c->Ppad * decim;
+    c->K = n_tunings;
+    c->KT = ddc_tunings_per_chunk(n_tunings);
+    c->Kpad = (n_tunings + c->KT - 1) / c->KT * c->KT;
+    c->n_streams = n_streams;
+    c->device = device;
+    c->complex_in = data_complex != 0;
+    c->h.assign(taps, taps + n_taps);
+    auto fail = [&](int code) { ddc_free(c); return code; };
+#define TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail(hip_fail(e__, #call)); } while (0)
+    const std::vector<v2f> t = ddc_table(c, inc.data());
+    inc.resize(c->Kpad, 0u);
+    TRY(hipMalloc(&c->d_taps, t.size() * sizeof(v2f)));
+    TRY(hipMemcpy(c->d_taps, t.data(), t.size() * sizeof(v2f), hipMemcpyHostToDevice));
+    TRY(hipMalloc(&c->d_inc, inc.size() * sizeof(uint32_t)));
+    TRY(hipMemcpy(c->d_inc, inc.data(), inc.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    for (auto &p : c->d_hist) {
+        TRY(hipMalloc(&p, c->hist_bytes()));
+        TRY(hipMemset(p, 0, c->hist_bytes()));
+    }
+    TRY(hipDeviceSynchronize());
+#undef TRY
+    *out = c;
+    return SFE_OK;
+}
+
+int sfe_dsp_ddc_set_input_format(sfe_ddc_t h, int fmt)
+{
+    Ddc *c = as_ddc(h);
+    if (!c || (fmt != SFE_FMT_F32 && fmt != SFE_FMT_U8)) {
+        set_error("ddc_set_input_format: null handle or a format other than SFE_FMT_F32 / SFE_FMT_U8");
+        return SFE_EINVAL;
+    }
+    if (fmt == SFE_FMT_U8 && !c->complex_in) {
+        set_error("ddc_set_input_format: u8 input is (I,Q) pairs; this handle takes real data");
+        return SFE_EINVAL;
+    }
+    c->in_u8 = fmt == SFE_FMT_U8;
+    return SFE_OK;
+}
+
+int sfe_dsp_ddc_set_freqs(sfe_ddc_t h, const double *freqs)
+{
+    Ddc *c = as_ddc(h);
+    if (!c) return SFE_EINVAL;
+    std::vector<uint32_t> inc(c->K);
+    const int rc = ddc_check_freqs(c->K, freqs, inc.data());
+    if (rc != SFE_OK) return rc;
+    const std::vector<v2f> t = ddc_table(c, inc.data());
+    inc.resize(c->Kpad, 0u);
+    SFE_ON_DEVICE(c->device);
+    // calls already enqueued read the tables: they finish with the old ones before these are replaced
+    SFE_HIP(hipDeviceSynchronize());
+    SFE_HIP(hipMemcpy(c->d_taps, t.data(), t.size() * sizeof(v2f), hipMemcpyHostToDevice));
+    SFE_HIP(hipMemcpy(c->d_inc, inc.data(), inc.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    SFE_HIP(hipDeviceSynchronize());
+    return SFE_OK;
+}
+
+int sfe_dsp_ddc_process_stream(sfe_ddc_t h, const void *d_in, size_t n_in, size_t in_stride, void *d_out, size_t out_stride,
+                               size_t *n_out, sfe_stream_t stream)
+{
+    Ddc *c = as_ddc(h);
+    if (n_out) *n_out = 0;
+    if (!c || !n_out) {
+        set_error("ddc_process_stream: null handle or n_out");
+        return SFE_EINVAL;
+    }
+    if (n_in % (size_t)c->D) {
+        set_error("ddc_process_stream: n_in = %zu is not a multiple of decim = %d", n_in, c->D);
+        return SFE_EINVAL;
+    }
+    if (n_in >= ((size_t)1 << 31)) {
+        set_error("ddc_process_stream: n_in = %zu must be below 2^31 per call", n_in);
+        return SFE_EINVAL;
+    }
+    const size_t no = n_in / c->D;
+    if (n_in == 0) return SFE_OK;
+    if (!d_in || !d_out) {
+        set_error("ddc_process_stream: null buffer");
+        return SFE_EINVAL;
+    }
+    if (out_stride < no) {
+        set_error("ddc_process_stream: out_stride %zu < n_out %zu", out_stride, no);
+        return SFE_ERANGE;
+    }
+    if (c->n_streams > 1 && in_stride < n_in) {
+        set_error("ddc_process_stream: in_stride %zu < n_in %zu with %d streams", in_stride, n_in, c->n_streams);
+        return SFE_EINVAL;
+    }
+    const size_t isz = c->in_u8 ? 2 : c->complex_in ? 8 : 4;
+    if ((reinterpret_cast<uintptr_t>(d_in) & (isz - 1)) || (reinterpret_cast<uintptr_t>(d_out) & 7)) {
+        set_error("ddc_process_stream: buffers must be aligned to their element (cf32 8 B, real float 4 B, u8 (I,Q) pairs 2 B)");
+        return SFE_EINVAL;
+    }
+    const size_t in_b = ((size_t)(c->n_streams - 1) * in_stride + n_in) * isz;
+    const size_t out_b = ((size_t)c->n_streams * c->K - 1) * out_stride * sizeof(v2f) + no * sizeof(v2f);
+    if (ranges_overlap(d_in, in_b, d_out, out_b)) {
+        set_error("ddc_process_stream: input and output ranges overlap (in-place operation is not supported)");
+        return SFE_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (stream_is_capturing(s)) {
+        // the sample counter (the lead factors' phase) and the history buffer pair advance on the host
+        set_error("ddc_process_stream: graph capture is not supported (the sample counter lives on the host)");
+        return SFE_ESTATE;
+    }
+    SFE_ON_DEVICE(c->device);
+    const int fmt = c->in_u8 ? 1 : c->complex_in ? 0 : 2;
+    const int rc = launch_ddc(fmt, d_in, (long long)in_stride, c->d_hist[c->cur], c->d_hist[c->cur ^ 1], c->d_taps, c->d_inc,
+                              static_cast<v2f *>(d_out), (long long)out_stride, (long long)n_in, c->D, c->Ppad, c->H, c->K, c->Kpad,
+                              (unsigned)(c->count & 0xffffffffu), c->n_streams, s);
+    if (rc != SFE_OK) return rc;
+    c->cur ^= 1;
+    c->count += n_in;
+    *n_out = no;
+    return SFE_OK;
+}
+
+int sfe_dsp_ddc_reset(sfe_ddc_t h)
+{
+    Ddc *c = as_ddc(h);
+    if (!c) return SFE_EINVAL;
+    SFE_ON_DEVICE(c->device);
+    SFE_HIP(hipDeviceSynchronize());
+    for (auto *p : c->d_hist) SFE_HIP(hipMemset(p, 0, c->hist_bytes()));
+    SFE_HIP(hipDeviceSynchronize());
+    c->cur = 0;
+    c->count = 0;
+    return SFE_OK;
+}
+
+int sfe_dsp_ddc_destroy(sfe_ddc_t h)
+{
+    Ddc *c = as_ddc(h);
+    if (!c) return SFE_OK;
+    DeviceGuard g(c->device);
+    (void)hipDeviceSynchronize();
+    ddc_free(c);
+    return SFE_OK;
+}
+
+}  // extern "C"

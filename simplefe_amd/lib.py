@@ -117,6 +117,13 @@ SIGNATURES = {
     "sfe_dsp_combine_process_stream": (i32, [vp, vp, sz, sz, vp, sz, C.POINTER(sz), vp]),
     "sfe_dsp_combine_reset": (i32, [vp]),
     "sfe_dsp_combine_destroy": (i32, [vp]),
+    "sfe_dsp_ddc_plan": (i32, [i32, i32, i32, C.POINTER(C.c_double), C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_uint32)]),
+    "sfe_dsp_ddc_create": (i32, [vp, i32, i32, i32, C.POINTER(C.c_double), i32, i32, i32, C.POINTER(vp)]),
+    "sfe_dsp_ddc_set_input_format": (i32, [vp, i32]),
+    "sfe_dsp_ddc_set_freqs": (i32, [vp, C.POINTER(C.c_double)]),
+    "sfe_dsp_ddc_process_stream": (i32, [vp, vp, sz, sz, vp, sz, C.POINTER(sz), vp]),
+    "sfe_dsp_ddc_reset": (i32, [vp]),
+    "sfe_dsp_ddc_destroy": (i32, [vp]),
 }
 
 # the diagnostic library only (simplefe_amd/csrc/diag/sfe_dsp_diag.h; scripts/ load it by pointing LIB_PATH at it): bound when present

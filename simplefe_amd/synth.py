@@ -150,6 +150,54 @@ def chan_reference_direct(x, h, n_chans, decim, first, m0, n_out):
     return ((X @ G) * lead).T
 
 
+def ddc_incs(freqs):
+    """The down-converter's quantised NCO increments: llround(f 2^32) mod 2^32 (sfe_dsp_ddc_plan)."""
+    v = np.atleast_1d(np.asarray(freqs, dtype=np.float64)) * 2.0 ** 32
+    return [int(np.sign(a) * np.floor(abs(a) + 0.5)) % (1 << 32) for a in v]          # llround: halves away from zero
+
+
+def _ddc_phase(i, inc):
+    """exp(-j 2 pi ((i inc) mod 2^32) / 2^32) for integer sample indices i (numpy int64), exactly in the integer phase."""
+    ph = (np.asarray(i, dtype=np.int64) % (1 << 32)).astype(np.uint64) * np.uint64(inc) % np.uint64(1 << 32)
+    return np.exp(-2j * np.pi * ph.astype(np.float64) / 2.0 ** 32)
+
+
+def ddc_reference(x, h, decim, incs, first=0):
+    """The down-converter bank's contract (sfe_dsp_ddc_*) in float64, tuning by tuning: mix x down by exp(-j 2 pi
+    phi_k(i) / 2^32) with the exact integer phase (i the absolute sample index, x[0] being sample `first`), convolve with h
+    (FFT convolution; samples before x[0] are zero), keep i = m * decim.  Returns (K, n_out) complex128 for the instants
+    m * decim in [first, first + len(x))."""
+    x = np.asarray(x).astype(np.complex128).ravel()
+    h = np.asarray(h, dtype=np.float64).ravel()
+    D, n = int(decim), x.size
+    i = first + np.arange(n)
+    keep = np.nonzero(i % D == 0)[0]
+    nfft = 1 << int(np.ceil(np.log2(n + h.size)))
+    H = np.fft.fft(h, nfft)
+    out = np.empty((len(incs), keep.size), dtype=np.complex128)
+    for k, inc in enumerate(incs):
+        out[k] = np.fft.ifft(np.fft.fft(x * _ddc_phase(i, inc), nfft) * H)[keep]
+    return out
+
+
+def ddc_reference_direct(x, h, decim, incs, first, m0, n_out):
+    """The same contract evaluated straight from its formula, for windows of long streams: outputs m0 .. m0+n_out-1,
+    y_k[m] = sum_n h[n] x[mD - n] exp(-j 2 pi phi_k(mD - n) / 2^32), with x[0] being sample `first` (which must be
+    <= m0 D - (len(h) - 1), or 0).  One matrix product per tuning: rows are instants, columns taps."""
+    x = np.asarray(x).astype(np.complex128).ravel()
+    h = np.asarray(h, dtype=np.float64).ravel()
+    D, L = int(decim), h.size
+    m = m0 + np.arange(n_out, dtype=np.int64)
+    idx = (m * D)[:, None] - np.arange(L)[None, :] - first            # [n_out, L] positions in x
+    X = np.where(idx >= 0, x[np.clip(idx, 0, None)], 0)
+    if first > 0:
+        assert idx.min() >= 0, "the window must hold the L-1 samples before its first output"
+    out = np.empty((len(incs), n_out), dtype=np.complex128)
+    for k, inc in enumerate(incs):
+        out[k] = (X * _ddc_phase(idx + first, inc)) @ h
+    return out
+
+
 def combine_reference(X, g, n_chans, interp, first=0):
     """The combiner's contract (sfe_dsp_combine_*) in float64: X is (M, n) complex, the channel inputs of instants
     first .. first+n-1 (earlier instants are zero).  v = M * ifft(X) over the channels gives v_q[m] =
