@@ -548,6 +548,66 @@ int sfe_dsp_ddc_process_stream(sfe_ddc_t h, const void *d_in, size_t n_in, size_
 int sfe_dsp_ddc_reset(sfe_ddc_t h);
 int sfe_dsp_ddc_destroy(sfe_ddc_t h);
 
+/* ------------------------------------------------- streaming Welch spectrum estimator
+ * Averaged, windowed periodograms of complex streams, every stream in one kernel pass per call:
+ * what is in this band, before anything is tuned to it.  With a real window w[0..N), a hop H, an
+ * averaging count A and a float32 scale; i the absolute sample index since create / reset
+ * (x[i] = 0 for i < 0) and m >= 0 the absolute segment index:
+ *     b_m      = (m + 1) H - N                      first sample of segment m
+ *     X_m[k]   = sum_{n<N} w[n] x[b_m + n] exp(-j 2 pi k n / N)
+ *     P_m[k]   = Re(X_m[k])^2 + Im(X_m[k])^2
+ *     out_r[k] = scale * S_r[k],   S_r = the sum of P_m over m in [rA, (r + 1)A)
+ * Bin k is frequency k/N cycles per sample (bins k >= N/2 are the negative frequencies, numbered
+ * as the channelizer numbers them).  No implicit normalisation: the caller puts 1 / (A sum w^2),
+ * or whatever it wants, into scale.  Causal like the channelizer: a call of n_in = q H samples
+ * completes exactly q segments, and every emitted value is complete.
+ * Summation order (part of the contract: any cut of the stream gives the same bits).  A row's
+ * segments are taken in chunks of C consecutive segments counted from the row's first one (the
+ * last chunk of a row may be shorter); a chunk sum is the float32 left fold, from 0, of its P_m
+ * in ascending m; S_r is the float32 left fold, from 0, of its chunk sums in ascending order;
+ * scale multiplies once, after the last fold.  C is the smallest power of two with C C >= A
+ * (sfe_dsp_psd_plan reports it).  The order is a function of (A, m - rA) only: never of where
+ * calls are cut, of the grid size, or of the input format.  Every fold is about 2 sqrt(A) deep at
+ * the most, and a one-row average over a whole capture is still sqrt(A) workgroups wide.
+ * Shapes: N a power of two in [256, 4096], 1 <= H <= N (any integer), 1 <= A <= 2^24, scale
+ * finite, n_streams >= 1; anything else is SFE_EINVAL.  There is no flush: an unfinished row is
+ * dropped by reset; for one Welch estimate of a capture set A to its segment count.
+ * Computed by csrc/psd.hip: windowed segments transformed in LDS, squared and folded in
+ * registers per chunk; a second small kernel folds the chunk sums per row. */
+typedef void *sfe_psd_t;  /* opaque: one estimator over n_streams streams */
+/* Host-only (no GPU): validates the shape; *chunk = C, *history = N - H, the samples of carried
+ * state per stream.  Either output pointer may be NULL. */
+int sfe_dsp_psd_plan(int n_fft, int hop, int n_avg, int *chunk, int *history);
+/*   window     n_fft real float32 (copied)
+ *   hop        H;  n_avg  A;  scale  multiplies every row once
+ *   n_streams  independent streams sharing the window, each with its own history, open chunk and
+ *              open row; one segment counter.  SFE_ENODEV without a GPU: nothing computes on the CPU. */
+int sfe_dsp_psd_create(const float *window, int n_fft, int hop, int n_avg, float scale,
+                       int n_streams, int device, sfe_psd_t *out);
+/* SFE_FMT_F32 (cf32 input, 8-byte aligned) or SFE_FMT_U8 ((I,Q) byte pairs, 2-byte aligned,
+ * converted (b-128)*(1/127) on load exactly as sfe_dsp_rx_u8_to_f32).  The carried history is kept
+ * as cf32, so the format may change between calls; u8 input gives the bits of the cf32 path on
+ * the converted samples, and any element-aligned buffer gives the same bits. */
+int sfe_dsp_psd_set_input_format(sfe_psd_t h, int fmt);
+/* n_in samples of every stream: stream s at d_in + s*in_stride (samples of the input format).
+ * The rows this call completes are written consecutively: row j of stream s at
+ * d_out + s*out_stride + j*N (float32, 4-byte aligned); *n_rows = floor((segments_before mod A +
+ * n_in/H) / A).  A call that completes no row writes nothing and returns SFE_OK with *n_rows = 0.
+ * n_in a multiple of H below 2^31 (else SFE_EINVAL); n_in = 0 is a no-op.  out_stride <
+ * *n_rows * N is SFE_ERANGE; null or misaligned buffers, in_stride < n_in with more than one
+ * stream and overlapping input and output byte ranges are SFE_EINVAL; nothing is launched on a
+ * refusal.  Cutting a stream into calls at any multiple of H gives the one-call rows bit for bit,
+ * cuts in mid-chunk and mid-row included.  Asynchronous on `stream`.  The handle owns a scratch
+ * buffer for the chunk sums of one call, sized on the first call and grown only when a larger
+ * call arrives (synchronise, free, allocate): that is the one allocation, and the one host
+ * synchronisation, a call may make.  The segment counter lives on the host: a call on a stream
+ * under graph capture is SFE_ESTATE, nothing enqueued. */
+int sfe_dsp_psd_process_stream(sfe_psd_t h, const void *d_in, size_t n_in, size_t in_stride,
+                               void *d_out, size_t out_stride, size_t *n_rows, sfe_stream_t stream);
+/* Zero the carried state and the segment counter (a fresh handle); an unfinished row is dropped. */
+int sfe_dsp_psd_reset(sfe_psd_t h);
+int sfe_dsp_psd_destroy(sfe_psd_t h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,7 @@ Two layers, both thin:
     reference's driver scripts (libdsp/test/test_decimate.py:22-25) read the same.
   * `Fir`, `Rs`, `DeviceArray` -- the device-resident bulk path used by bench.py and the
     parity tests (sfe_dsp_*_process_stream); `Chan`, the polyphase channelizer (sfe_dsp_chan_*); `Combiner`, its
-    transpose, the synthesis filter bank (sfe_dsp_combine_*).
+    transpose, the synthesis filter bank (sfe_dsp_combine_*); `Psd`, the streaming Welch spectrum estimator (sfe_dsp_psd_*).
 
 Everything computes on the GPU through the C ABI; numpy is only the host container.
 """
@@ -635,6 +635,78 @@ class Ddc:
     def close(self):
         if getattr(self, "_h", None):
             self._L.sfe_dsp_ddc_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+def psd_plan(n_fft, hop, n_avg):
+    """sfe_dsp_psd_plan (host only, no GPU): (segments per chunk C of the summation order, samples of history carried
+    per stream = n_fft - hop)."""
+    c, h = C.c_int(0), C.c_int(0)
+    check(_l.load().sfe_dsp_psd_plan(int(n_fft), int(hop), int(n_avg), C.byref(c), C.byref(h)))
+    return c.value, h.value
+
+
+class Psd:
+    """Streaming Welch spectrum estimator (sfe_dsp_psd_*): scale times the sum of n_avg windowed periodograms of
+    n_fft = len(window) samples, one every `hop` samples, of n_streams complex streams."""
+
+    def __init__(self, window, hop, n_avg, scale=1.0, n_streams=1, device=0):
+        self._L = _l.load()
+        w = _f32(window).ravel()
+        self.n_fft, self.hop, self.n_avg, self.n_streams = int(w.size), int(hop), int(n_avg), int(n_streams)
+        self.in_u8 = False
+        h = C.c_void_p()
+        check(self._L.sfe_dsp_psd_create(w.ctypes.data, self.n_fft, self.hop, self.n_avg, float(scale), self.n_streams, device,
+                                         C.byref(h)))
+        self._h = h.value
+
+    def set_input_format(self, fmt):
+        """lib.FMT_F32 (cf32) or lib.FMT_U8 ((I,Q) byte pairs, converted on load)."""
+        check(self._L.sfe_dsp_psd_set_input_format(self._h, fmt))
+        self.in_u8 = fmt == _l.FMT_U8
+
+    def reset(self):
+        check(self._L.sfe_dsp_psd_reset(self._h))
+
+    def process_stream(self, d_in, n_in, d_out, in_stride=None, out_stride=None, stream=None):
+        """d_in / d_out: DeviceArray or raw device pointers; n_in samples per stream (a multiple of hop).  Row j of
+        stream s that the call completes goes to d_out + s*out_stride + j*n_fft floats; out_stride defaults to the rows
+        n_in samples can complete at the most.  Returns the number of rows written per stream."""
+        pi = d_in.ptr if isinstance(d_in, DeviceArray) else int(d_in)
+        po = d_out.ptr if isinstance(d_out, DeviceArray) else int(d_out)
+        n_rows = C.c_size_t(0)
+        most = -(-(int(n_in) // self.hop) // self.n_avg) * self.n_fft
+        check(self._L.sfe_dsp_psd_process_stream(self._h, pi, int(n_in), int(n_in) if in_stride is None else int(in_stride),
+                                                 po, most if out_stride is None else int(out_stride), C.byref(n_rows), stream))
+        return n_rows.value
+
+    def spectrum(self, x):
+        """Host convenience, computed on the GPU: x is (n_streams, n) complex64 -- or (n_streams, n, 2) uint8 (I,Q)
+        pairs with FMT_U8 -- (one dimension less for one stream), n a multiple of hop; returns the rows the call
+        completes, (n_streams, rows, n_fft) float32."""
+        if self.in_u8:
+            b = np.ascontiguousarray(x, dtype=np.uint8).reshape(self.n_streams, -1)
+            n = b.shape[1] // 2
+            d_in = DeviceArray.from_bytes(b)
+        else:
+            z = np.ascontiguousarray(x, dtype=np.complex64).reshape(self.n_streams, -1)
+            n = z.shape[1]
+            d_in = DeviceArray.from_numpy(z.view(np.float32))
+        stride = -(-(n // self.hop) // self.n_avg) * self.n_fft
+        d_out = DeviceArray(max(1, self.n_streams * stride))
+        try:
+            k = self.process_stream(d_in, n, d_out, out_stride=stride)
+            y = d_out.to_numpy(self.n_streams * stride).reshape(self.n_streams, -1, self.n_fft)[:, :k]
+        finally:
+            d_in.free()
+            d_out.free()
+        return np.ascontiguousarray(y)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.sfe_dsp_psd_destroy(self._h)
             self._h = None
 
     __del__ = close

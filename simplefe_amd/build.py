@@ -21,13 +21,14 @@ LIB_DIAG = os.path.join(HERE, "libsfe_dsp_diag.so")
 ARCH = "gfx950"
 # bit-exact restatements of the reference arithmetic: no implicit FMA contraction (chan.hip: its u8 and cf32
 # instantiations must give the same bits on the same samples; its multiply-adds are explicit; combine.hip: its TX10
-# bytes must be sfe_dsp_tx_f32_to_10bit's of its F32 output; ddc.hip: as chan.hip)
-EXACT_SOURCES = ("polyphase.hip", "util.hip", "chan.hip", "combine.hip", "ddc.hip")
+# bytes must be sfe_dsp_tx_f32_to_10bit's of its F32 output; ddc.hip: as chan.hip; psd.hip: as chan.hip, and its sums of
+# squares are folded in a stated order)
+EXACT_SOURCES = ("polyphase.hip", "util.hip", "chan.hip", "combine.hip", "ddc.hip", "psd.hip")
 TICKET_SOURCES = ("fir_fft.hip", "poly_fft.hip")
 # host side only (handles, plans, launch choices, device groups):
 # not part of the kernel-source hash
 HOST_SOURCES = ("api.hip", "api_plans.hip", "api_fir.hip", "api_rs.hip", "api_pipe.hip", "api_chan.hip", "api_combine.hip", "api_ddc.hip",
-                "group.hip", "host.h")
+                "api_psd.hip", "group.hip", "host.h")
 
 
 def sources(diag=False):
@@ -44,7 +45,8 @@ def _deps():
 # kernel's file does not orphan it.  None = every kernel source.
 KERNEL_FILES = {"fir": ("fir_fft.hip", "fft16.h", "common.h"), "resample": ("poly_fft.hip", "fft16.h", "common.h"),
                 "decimate": ("polyphase.hip", "common.h"), "chan": ("chan.hip", "fft16.h", "common.h"),
-                "combine": ("combine.hip", "fft16.h", "common.h"), "ddc": ("ddc.hip", "common.h")}
+                "combine": ("combine.hip", "fft16.h", "common.h"), "ddc": ("ddc.hip", "common.h"),
+                "psd": ("psd.hip", "fft16.h", "common.h")}
 
 
 def csrc_hash(kind=None):
@@ -162,8 +164,13 @@ def check_resources(res):
     for k, r in res.get("ddc.hip", {}).items():
         if r.get("ScratchSize", 0) or r.get("VGPRs Spill", 0) or r.get("SGPRs Spill", 0):
             bad.append("%s: down-converter kernel touches scratch: %s" % (k[:200], r))
+    # the spectrum estimator: every instantiation keeps its window, its prefetched samples and its bin sums in registers
+    for k, r in res.get("psd.hip", {}).items():
+        if r.get("ScratchSize", 0) or r.get("VGPRs Spill", 0) or r.get("SGPRs Spill", 0):
+            bad.append("%s: spectrum-estimator kernel touches scratch: %s" % (k[:200], r))
     if bad:
-        raise RuntimeError("FIR kernels of the default path and the channelizer, combiner and down-converter kernels must not touch scratch; "
+        raise RuntimeError("FIR kernels of the default path and the channelizer, combiner, down-converter and spectrum-estimator kernels "
+                           "must not touch scratch; "
                            "the FIR ones must keep "
                            "4 workgroups per CU:\n  " + "\n  ".join(bad))
 

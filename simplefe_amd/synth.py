@@ -239,3 +239,59 @@ def combine_reference_direct(X, g, n_chans, interp, first, i0, n_out):
         ok = (tap < L) & (m >= ms[0]) & (m <= ms[-1])
         z[ok] += g[tap[ok]] * V[i[ok] % M, m[ok] - ms[0]]
     return z
+
+
+def psd_rows(n, n_fft, hop, n_avg, first=0):
+    """The rows of the spectrum estimator (sfe_dsp_psd_*) that samples [first, first + n) hold whole: (r_lo, r_hi),
+    rows r_lo <= r < r_hi.  Segment m reads samples [(m + 1) H - N, (m + 1) H); a stream that starts at sample 0 has zeros
+    before it, one that starts later must hold every sample of a row's first segment."""
+    N, H, A = int(n_fft), int(hop), int(n_avg)
+    m_lo = 0 if first == 0 else max(0, -(-(first + N) // H) - 1)      # the first m with (m + 1) H - N >= first
+    r_lo = -(-m_lo // A)
+    return r_lo, max(r_lo, ((first + n) // H) // A)
+
+
+def psd_reference(x, w, hop, n_avg, scale, first=0):
+    """The spectrum estimator's contract (sfe_dsp_psd_*) in float64 through np.fft.fft: x[0] is absolute sample `first`
+    (zeros before it when first = 0); segment m is the N samples that end at (m + 1) hop, times the window w; row r is
+    scale times the sum of |fft|^2 over segments [r n_avg, (r + 1) n_avg).  Returns (rows, N) float64 for the rows
+    psd_rows(len(x), N, hop, n_avg, first) names."""
+    x = np.asarray(x).astype(np.complex128).ravel()
+    w = np.asarray(w, dtype=np.float64).ravel()
+    N, H, A = w.size, int(hop), int(n_avg)
+    r_lo, r_hi = psd_rows(x.size, N, H, A, first)
+    try:                                    # batched transforms on several cores where scipy is installed
+        from scipy import fft as F
+        kw = {"workers": min(16, os.cpu_count() or 1)}
+    except ImportError:
+        F, kw = np.fft, {}
+    xp = np.concatenate([np.zeros(N, dtype=np.complex128), x]) if first == 0 else x
+    off = N if first == 0 else -first       # position in xp of absolute sample 0
+    out = np.empty((r_hi - r_lo, N), dtype=np.float64)
+    for r in range(r_lo, r_hi):
+        b = (np.arange(r * A, (r + 1) * A) + 1) * H - N + off
+        seg = xp[b[:, None] + np.arange(N)[None, :]] * w[None, :]
+        X = F.fft(seg, axis=1, **kw)
+        out[r - r_lo] = scale * np.sum(X.real ** 2 + X.imag ** 2, axis=0)
+    return out
+
+
+def psd_reference_direct(x, w, hop, n_avg, scale, first, row, bins):
+    """The same contract with the DFT sum written out, for chosen bins of one absolute row: out[k] = scale sum_m
+    |sum_n w[n] x[(m + 1) hop - N + n] exp(-j 2 pi k n / N)|^2 over the row's segments, x[0] being absolute sample
+    `first` (which must be 0 or at most the row's first sample).  One matrix product per row: no FFT, no shared framing
+    code with psd_reference."""
+    x = np.asarray(x).astype(np.complex128).ravel()
+    w = np.asarray(w, dtype=np.float64).ravel()
+    N, H, A = w.size, int(hop), int(n_avg)
+    k = np.asarray(bins, dtype=np.int64)
+    n = np.arange(N)
+    E = w[:, None] * np.exp(-2j * np.pi * ((n[:, None] * k[None, :]) % N) / N)          # [N, bins]
+    acc = np.zeros(k.size, dtype=np.float64)
+    for m in range(row * A, (row + 1) * A):
+        idx = (m + 1) * H - N + n - first
+        if first > 0:
+            assert idx[0] >= 0, "the window must hold the row's first sample"
+        seg = np.where(idx >= 0, x[np.clip(idx, 0, None)], 0)
+        acc += np.abs(seg @ E) ** 2
+    return scale * acc
