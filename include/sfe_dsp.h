@@ -608,6 +608,73 @@ int sfe_dsp_psd_process_stream(sfe_psd_t h, const void *d_in, size_t n_in, size_
 int sfe_dsp_psd_reset(sfe_psd_t h);
 int sfe_dsp_psd_destroy(sfe_psd_t h);
 
+/* ------------------------------------------------- streaming preamble correlator bank
+ * Where in a stream a known waveform starts: K complex templates s_k[0..L) against every stream,
+ * normalised by the sliding signal energy and reduced to one peak per block on the chip, so a call
+ * reads its input once, whatever K is, and writes 8 bytes per template and block.  With i the
+ * absolute sample index since create / reset (x[i] = 0 for i < 0):
+ *     c_k[i] = sum_{n<L} conj(s_k[n]) x[i - (L-1) + n]      window ENDING at sample i (causal)
+ *     e[i]   = sum_{n<L} |x[i - (L-1) + n]|^2
+ *     E_k    = sum_n |s_k[n]|^2       (host, float64, rounded once to float32; 0 is SFE_EINVAL)
+ *     m_k[i] = |c_k[i]|^2 / (E_k e[i])   if e[i] > min_energy,   else 0
+ * m is the squared normalised correlation: in [0, 1] up to rounding, not clamped, 1 where the
+ * window is a multiple of the template.  Block j is the samples [jB, (j+1)B); per stream, template
+ * and block the call emits peak_val = the maximum of m_k over the block and peak_idx = the smallest
+ * offset i - jB that attains it (uint32).  The template whose peak this is began at sample
+ * jB + peak_idx - (L-1).  Optionally m_k[i] of every sample is written too (the dense output).
+ * Shapes: 1 <= L <= 2049, 1 <= K <= 16, n_streams >= 1, min_energy finite and >= 0, B a positive
+ * multiple of the transform advance V(L) = 4096 - 256 ceil((L-1)/256) (sfe_dsp_fir_plan's rule for a
+ * single partition: 4096 for L = 1, 3840 for L <= 257, 2048 at L = 2049); anything else is
+ * SFE_EINVAL with a message that starts with "corr: ".
+ * Computed by overlap-save through 4096-point transforms whose slots start at absolute multiples
+ * of V, so every value is a function of absolute position only:
+ *   - cutting the stream into calls at any multiple of B gives the one-call bits, peaks and dense;
+ *   - u8 input gives the bits of the cf32 path on the converted samples, and the format may change
+ *     between calls (the carried history, 4096 - V samples per stream, is cf32);
+ *   - stream s of an n-stream handle gives the bits of a one-stream handle fed that stream, and
+ *     template k of a K-template handle those of a one-template handle holding s_k;
+ *   - the peaks are the same bits with and without the dense output, and equal the maximum and the
+ *     first arg-maximum of the dense values of their block exactly.
+ * e[i] is summed from the squares themselves (runs of 1, 16 and 256 samples in an order fixed by
+ * the window's place in its slot), never as a difference of prefix sums.  The transform's rounding
+ * error in c is relative to the RMS of the whole 4096-sample slot, not of the window: in a slot
+ * that holds a strong burst and near-silence, m over the silence is noise divided by a tiny e, and
+ * min_energy is the gate for that.  Non-finite samples poison the slots they touch. */
+typedef void *sfe_corr_t;  /* opaque: one bank of K templates over n_streams streams */
+/* Host-only (no GPU): validates what create validates except the template values;
+ * *advance = V(L), *history = 4096 - V.  Either output pointer may be NULL. */
+int sfe_dsp_corr_plan(int len, int n_templates, int block, int *advance, int *history);
+/*   templates  [n_templates][len] complex float32 as (re, im) pairs (copied; their spectra are
+ *              computed here, in float64)
+ *   block      B;  min_energy  the gate on e[i]
+ *   n_streams  independent streams sharing the templates, each with its own history.
+ * Shapes and template values are checked before the device: SFE_ENODEV without a GPU. */
+int sfe_dsp_corr_create(const float *templates, int len, int n_templates, int block,
+                        float min_energy, int n_streams, int device, sfe_corr_t *out);
+/* SFE_FMT_F32 (cf32 input, 8-byte aligned) or SFE_FMT_U8 ((I,Q) byte pairs, 2-byte aligned,
+ * converted (b-128)*(1/127) on load exactly as sfe_dsp_rx_u8_to_f32). */
+int sfe_dsp_corr_set_input_format(sfe_corr_t h, int fmt);
+/* n_in samples of every stream: stream s at d_in + s*in_stride (samples of the input format).
+ * Block j of template k of stream s goes to element (s*K + k)*peak_stride + j of d_peak_val
+ * (float32) and of d_peak_idx (uint32), both 4-byte aligned; with d_metric != NULL, m_k of the
+ * call's sample i goes to element (s*K + k)*metric_stride + i of d_metric (float32).
+ * *n_blocks = n_in / B.  n_in a multiple of B below 2^31 (else SFE_EINVAL); n_in = 0 is a no-op.
+ * peak_stride < *n_blocks, or metric_stride < n_in with a dense pointer, is SFE_ERANGE; null or
+ * misaligned buffers, in_stride < n_in with more than one stream and any overlap between the
+ * input and an output byte range (or between two outputs) are SFE_EINVAL; nothing is launched on
+ * a refusal.  Asynchronous on `stream`.  With B = V a call allocates nothing; with B > V the handle
+ * owns a table of one peak per 4096-point slot of a call, sized on the first call and grown only
+ * when a larger call arrives (synchronise, free, allocate): the one allocation, and the one host
+ * synchronisation, a call may make.  The sample counter lives on the host: a call on a stream
+ * under graph capture is SFE_ESTATE, nothing enqueued. */
+int sfe_dsp_corr_process_stream(sfe_corr_t h, const void *d_in, size_t n_in, size_t in_stride,
+                                void *d_peak_val, void *d_peak_idx, size_t peak_stride,
+                                void *d_metric, size_t metric_stride,
+                                size_t *n_blocks, sfe_stream_t stream);
+/* Zero the carried history and the sample counter (a fresh handle); the templates are kept. */
+int sfe_dsp_corr_reset(sfe_corr_t h);
+int sfe_dsp_corr_destroy(sfe_corr_t h);
+
 #ifdef __cplusplus
 }
 #endif

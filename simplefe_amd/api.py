@@ -7,7 +7,8 @@ Two layers, both thin:
     reference's driver scripts (libdsp/test/test_decimate.py:22-25) read the same.
   * `Fir`, `Rs`, `DeviceArray` -- the device-resident bulk path used by bench.py and the
     parity tests (sfe_dsp_*_process_stream); `Chan`, the polyphase channelizer (sfe_dsp_chan_*); `Combiner`, its
-    transpose, the synthesis filter bank (sfe_dsp_combine_*); `Psd`, the streaming Welch spectrum estimator (sfe_dsp_psd_*).
+    transpose, the synthesis filter bank (sfe_dsp_combine_*); `Psd`, the streaming Welch spectrum estimator (sfe_dsp_psd_*);
+    `Corr`, the streaming preamble correlator bank (sfe_dsp_corr_*).
 
 Everything computes on the GPU through the C ABI; numpy is only the host container.
 """
@@ -707,6 +708,89 @@ class Psd:
     def close(self):
         if getattr(self, "_h", None):
             self._L.sfe_dsp_psd_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+def corr_plan(length, n_templates, block):
+    """sfe_dsp_corr_plan (host only, no GPU): (transform advance V, samples of history carried per stream = 4096 - V)."""
+    v, h = C.c_int(0), C.c_int(0)
+    check(_l.load().sfe_dsp_corr_plan(int(length), int(n_templates), int(block), C.byref(v), C.byref(h)))
+    return v.value, h.value
+
+
+class Corr:
+    """Streaming preamble correlator bank (sfe_dsp_corr_*): the squared normalised correlation of K complex templates
+    (n_templates, len) against n_streams complex streams, reduced to (peak value, first peak offset) per block of
+    `block` samples."""
+
+    def __init__(self, templates, block, min_energy=0.0, n_streams=1, device=0):
+        self._L = _l.load()
+        t = np.atleast_2d(np.ascontiguousarray(templates, dtype=np.complex64))
+        self.n_templates, self.len = int(t.shape[0]), int(t.shape[1])
+        self.block, self.n_streams = int(block), int(n_streams)
+        self.in_u8 = False
+        h = C.c_void_p()
+        check(self._L.sfe_dsp_corr_create(t.view(np.float32).ctypes.data, self.len, self.n_templates, self.block, float(min_energy),
+                                          self.n_streams, device, C.byref(h)))
+        self._h = h.value
+
+    def set_input_format(self, fmt):
+        """lib.FMT_F32 (cf32) or lib.FMT_U8 ((I,Q) byte pairs, converted on load)."""
+        check(self._L.sfe_dsp_corr_set_input_format(self._h, fmt))
+        self.in_u8 = fmt == _l.FMT_U8
+
+    def reset(self):
+        check(self._L.sfe_dsp_corr_reset(self._h))
+
+    def process_stream(self, d_in, n_in, d_peak_val, d_peak_idx, d_metric=None, in_stride=None, peak_stride=None, metric_stride=None,
+                       stream=None):
+        """d_*: DeviceArray or raw device pointers; n_in samples per stream (a multiple of block).  Block j of template k
+        of stream s goes to element (s*K + k)*peak_stride + j of d_peak_val (float32) and d_peak_idx (uint32), and with
+        d_metric every m_k[i] to (s*K + k)*metric_stride + i; the strides default to n_in / block and n_in.  Returns the
+        number of blocks."""
+        ptr = lambda d: d.ptr if isinstance(d, DeviceArray) else (None if d is None else int(d))  # noqa: E731
+        n_blocks = C.c_size_t(0)
+        check(self._L.sfe_dsp_corr_process_stream(self._h, ptr(d_in), int(n_in), int(n_in) if in_stride is None else int(in_stride),
+                                                  ptr(d_peak_val), ptr(d_peak_idx),
+                                                  int(n_in) // self.block if peak_stride is None else int(peak_stride), ptr(d_metric),
+                                                  int(n_in) if metric_stride is None else int(metric_stride), C.byref(n_blocks), stream))
+        return n_blocks.value
+
+    def search(self, x, dense=False):
+        """Host convenience, computed on the GPU: x is (n_streams, n) complex64 -- or (n_streams, n, 2) uint8 (I,Q)
+        pairs with FMT_U8 -- (one dimension less for one stream), n a multiple of block.  Returns (peak_val float32,
+        peak_idx uint32), each (n_streams, K, n / block), and with dense=True also m, (n_streams, K, n) float32."""
+        if self.in_u8:
+            b = np.ascontiguousarray(x, dtype=np.uint8).reshape(self.n_streams, -1)
+            n = b.shape[1] // 2
+            d_in = DeviceArray.from_bytes(b)
+        else:
+            z = np.ascontiguousarray(x, dtype=np.complex64).reshape(self.n_streams, -1)
+            n = z.shape[1]
+            d_in = DeviceArray.from_numpy(z.view(np.float32))
+        rows, nb = self.n_streams * self.n_templates, n // self.block
+        d_val, d_idx = DeviceArray(max(1, rows * nb)), DeviceArray(max(1, rows * nb))
+        d_m = DeviceArray(max(1, rows * n)) if dense else None
+        try:
+            k = self.process_stream(d_in, n, d_val, d_idx, d_m)
+            shape = (self.n_streams, self.n_templates, nb)
+            out = (d_val.to_numpy(rows * nb).reshape(shape)[:, :, :k].copy(),
+                   d_idx.to_numpy(rows * nb).view(np.uint32).reshape(shape)[:, :, :k].copy())
+            if dense:
+                out += (d_m.to_numpy(rows * n).reshape(self.n_streams, self.n_templates, n),)
+        finally:
+            d_in.free()
+            d_val.free()
+            d_idx.free()
+            if d_m is not None:
+                d_m.free()
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.sfe_dsp_corr_destroy(self._h)
             self._h = None
 
     __del__ = close

@@ -130,6 +130,12 @@ SIGNATURES = {
     "sfe_dsp_psd_process_stream": (i32, [vp, vp, sz, sz, vp, sz, C.POINTER(sz), vp]),
     "sfe_dsp_psd_reset": (i32, [vp]),
     "sfe_dsp_psd_destroy": (i32, [vp]),
+    "sfe_dsp_corr_plan": (i32, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
+    "sfe_dsp_corr_create": (i32, [vp, i32, i32, i32, f32, i32, i32, C.POINTER(vp)]),
+    "sfe_dsp_corr_set_input_format": (i32, [vp, i32]),
+    "sfe_dsp_corr_process_stream": (i32, [vp, vp, sz, sz, vp, vp, sz, vp, sz, C.POINTER(sz), vp]),
+    "sfe_dsp_corr_reset": (i32, [vp]),
+    "sfe_dsp_corr_destroy": (i32, [vp]),
 }
 
 # the diagnostic library only (simplefe_amd/csrc/diag/sfe_dsp_diag.h; scripts/ load it by pointing LIB_PATH at it): bound when present

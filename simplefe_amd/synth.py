@@ -295,3 +295,62 @@ def psd_reference_direct(x, w, hop, n_avg, scale, first, row, bins):
         seg = np.where(idx >= 0, x[np.clip(idx, 0, None)], 0)
         acc += np.abs(seg @ E) ** 2
     return scale * acc
+
+
+def _corr_frame(x, templates, first):
+    """x and the templates as complex128, with the L - 1 zeros a stream that starts at sample 0 has before it."""
+    x = np.asarray(x).astype(np.complex128).ravel()
+    t = np.atleast_2d(np.asarray(templates).astype(np.complex128))
+    L = t.shape[1]
+    if first == 0:
+        x = np.concatenate([np.zeros(L - 1, dtype=np.complex128), x])
+    return x, t, L
+
+
+def corr_reference(x, templates, block, min_energy, first=0):
+    """The correlator bank's contract (sfe_dsp_corr_*) in float64: the returned values are those of absolute samples
+    first, first + 1, ..., `first` a multiple of block.  With first = 0, x[0] is sample 0 and zeros precede it; otherwise
+    x starts with the L - 1 samples before `first`, so every returned value has its whole window.  c_k is the
+    convolution with conj(s_k) reversed (np.convolve; through float64 transforms for templates longer than 64), the
+    window energy e np.convolve of |x|^2 with L ones (a direct sum, no differenced cumsum), m_k = |c_k|^2 / (E_k e)
+    where e > min_energy, else 0.  Returns (m (K, n) float64, peak_val (K, n // block), peak_idx (K, n // block) int64:
+    the first arg-maximum of each block)."""
+    assert first % int(block) == 0
+    xp, t, L = _corr_frame(x, templates, first)
+    n = xp.size - (L - 1)
+    e = np.convolve(xp.real ** 2 + xp.imag ** 2, np.ones(L), mode="valid")
+    m = np.zeros((t.shape[0], n), dtype=np.float64)
+    ok = e > min_energy
+    nfft = 1 << int(np.ceil(np.log2(xp.size + L)))
+    X = np.fft.fft(xp, nfft) if L > 64 else None
+    for k in range(t.shape[0]):
+        h = np.conj(t[k])[::-1]
+        c = np.convolve(xp, h, mode="valid") if X is None else np.fft.ifft(X * np.fft.fft(h, nfft))[L - 1:L - 1 + n]
+        E = float(np.sum(t[k].real ** 2 + t[k].imag ** 2))
+        m[k, ok] = (c.real[ok] ** 2 + c.imag[ok] ** 2) / (E * e[ok])
+    nb = n // int(block)
+    blocks = m[:, :nb * int(block)].reshape(t.shape[0], nb, int(block))
+    return m, blocks.max(axis=2), blocks.argmax(axis=2)
+
+
+def corr_reference_direct(x, templates, min_energy, first, points):
+    """The same contract by the explicit double loop, for chosen (k, i) with i absolute: no convolution, no shared
+    framing code with corr_reference.  x[0] is absolute sample `first`; samples before absolute 0 are zero, and with
+    first > 0 every window must lie inside x."""
+    x = np.asarray(x).astype(np.complex128).ravel()
+    t = np.atleast_2d(np.asarray(templates).astype(np.complex128))
+    L = t.shape[1]
+    out = []
+    for k, i in points:
+        c, e, E = 0.0 + 0.0j, 0.0, 0.0
+        for n in range(L):
+            a = i - (L - 1) + n
+            E += abs(t[k, n]) ** 2
+            if a < 0:
+                continue
+            assert a - first >= 0, "the window must lie inside x"
+            v = x[a - first]
+            c += np.conj(t[k, n]) * v
+            e += abs(v) ** 2
+        out.append(abs(c) ** 2 / (E * e) if e > min_energy else 0.0)
+    return np.array(out)
