@@ -675,6 +675,74 @@ int sfe_dsp_corr_process_stream(sfe_corr_t h, const void *d_in, size_t n_in, siz
 int sfe_dsp_corr_reset(sfe_corr_t h);
 int sfe_dsp_corr_destroy(sfe_corr_t h);
 
+/* ------------------------------------------------- streaming biquad-cascade IIR filter
+ * A recursive filter over every stream: S second-order sections in cascade, 1 <= S <= 8.  What no
+ * finite window reaches at a bearable length: a DC blocker at pole radius 0.9999, a narrow notch,
+ * a one-pole smoother, a steep low-pass.
+ * Coefficients come as const double sos[S][6], one row (b0, b1, b2, a0, a1, a2) per section
+ * (scipy's sos layout; a first-order section has b2 = a2 = 0).  The host divides each row by a0 in
+ * float64 and rounds each of B0, B1, B2, A1, A2 ONCE to float32; the law is stated on those
+ * float32 values promoted to real numbers.  With i the absolute sample index since create / reset
+ * and everything 0 for i < 0:
+ *     v_0 = x
+ *     v_{s+1}[i] = B0_s v_s[i] + B1_s v_s[i-1] + B2_s v_s[i-2] - A1_s v_{s+1}[i-1] - A2_s v_{s+1}[i-2]
+ *     y = v_S
+ * The coefficients are real: on a complex stream I and Q never mix.
+ * Refused with SFE_EINVAL and a message that starts with "iir: ": S outside [1, 8]; any of the 6S
+ * numbers non-finite; a0 = 0; a section that is not strictly stable AS THE KERNEL WILL RUN IT, the
+ * test being on the rounded values: |A2| < 1 and |A1| < 1 + A2.
+ * Input: cf32; u8 (I,Q) pairs, converted exactly as sfe_dsp_rx_u8_to_f32 converts them; or, on a
+ * handle created with data_complex = 0, real float32.  Output: cf32, or real float32 for a real
+ * handle; one output sample per input sample.  A non-finite sample poisons its stream until reset
+ * (the carried state is then non-finite, and so is every later output).
+ * Computed exactly in parallel, not by warm-up and discard (csrc/iir.hip): a call is cut into
+ * blocks of G samples, every block is run from zero state, the block states are chained from the
+ * carried state (in two levels, grouped by the absolute block index since create / reset, never
+ * by where calls are cut), and every block is run again from its true state.
+ * Contracts about bits:
+ *   1. cutting a stream into calls at any multiple of G gives the one-call output bit for bit;
+ *   2. u8 input gives the bits of the cf32 path on the converted samples, at any 2-byte-aligned
+ *      address, and the format may change between calls (the carried state is float32);
+ *   3. stream s of an n-stream handle gives the bits of a one-stream handle fed that stream;
+ *   4. a complex handle's output equals, bit for bit, two real handles run on its real and its
+ *      imaginary parts;
+ *   5. the same calls give the same bits on every run: nothing depends on the order in which
+ *      workgroups finish, and there are no floating-point atomics;
+ *   6. reset makes a fresh handle.
+ * Not promised: the bits of the sample-by-sample float32 recursion (the error is of its size, see
+ * DESIGN.md 4.10), nor equal bits between a cascade and the same sections run as separate handles. */
+typedef void *sfe_iir_t;  /* opaque: one cascade over n_streams streams */
+/* Host-only (no GPU): validates the coefficients as above; *block = G, the granule of a call (a
+ * power of two in [1024, 65536], the same for every S and format); *state_floats = 6S, the float32
+ * values of carried state per stream and component (a complex stream carries I's and Q's): the
+ * 2S states of the cascade, and two more such vectors of the two-level fold over the blocks.
+ * Either output pointer may be NULL. */
+int sfe_dsp_iir_plan(const double *sos, int n_sections, int *block, int *state_floats);
+/*   sos           [n_sections][6] float64 (copied after normalising and rounding)
+ *   data_complex  0: real float32 streams; else complex
+ *   n_streams     independent streams sharing the coefficients, each with its own state.
+ * The coefficients are checked before the device: SFE_ENODEV without a GPU. */
+int sfe_dsp_iir_create(const double *sos, int n_sections, int data_complex, int n_streams,
+                       int device, sfe_iir_t *out);
+/* SFE_FMT_F32 (cf32 input, 8-byte aligned; float32, 4-byte aligned, on a real handle) or
+ * SFE_FMT_U8 ((I,Q) byte pairs, 2-byte aligned, converted (b-128)*(1/127) on load).  u8 on a real
+ * handle and any other format are SFE_EINVAL. */
+int sfe_dsp_iir_set_input_format(sfe_iir_t h, int fmt);
+/* n_in samples of every stream: stream s at d_in + s*in_stride (samples of the input format) goes
+ * to d_out + s*out_stride (samples of the output format).  *n_out = n_in.  n_in a positive
+ * multiple of G below 2^31 (else SFE_EINVAL); n_in = 0 is a no-op.  out_stride < n_in is
+ * SFE_ERANGE; null or misaligned buffers, overlapping input and output byte ranges and
+ * in_stride < n_in with more than one stream are SFE_EINVAL; nothing is launched on a refusal.
+ * Asynchronous on `stream`.  The handle owns one table of per-block states, sized on the first
+ * call and grown only when a larger call arrives (synchronise, free, allocate): that is the one
+ * allocation, and the one host synchronisation, a call may make.  The sample counter lives on the
+ * host: a call on a stream under graph capture is SFE_ESTATE, nothing enqueued. */
+int sfe_dsp_iir_process_stream(sfe_iir_t h, const void *d_in, size_t n_in, size_t in_stride,
+                               void *d_out, size_t out_stride, size_t *n_out, sfe_stream_t stream);
+/* Zero the carried state and the sample counter (a fresh handle); the coefficients are kept. */
+int sfe_dsp_iir_reset(sfe_iir_t h);
+int sfe_dsp_iir_destroy(sfe_iir_t h);
+
 #ifdef __cplusplus
 }
 #endif

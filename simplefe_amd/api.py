@@ -8,7 +8,8 @@ Two layers, both thin:
   * `Fir`, `Rs`, `DeviceArray` -- the device-resident bulk path used by bench.py and the
     parity tests (sfe_dsp_*_process_stream); `Chan`, the polyphase channelizer (sfe_dsp_chan_*); `Combiner`, its
     transpose, the synthesis filter bank (sfe_dsp_combine_*); `Psd`, the streaming Welch spectrum estimator (sfe_dsp_psd_*);
-    `Corr`, the streaming preamble correlator bank (sfe_dsp_corr_*).
+    `Corr`, the streaming preamble correlator bank (sfe_dsp_corr_*); `Iir`, the streaming biquad-cascade IIR filter
+    (sfe_dsp_iir_*).
 
 Everything computes on the GPU through the C ABI; numpy is only the host container.
 """
@@ -791,6 +792,98 @@ class Corr:
     def close(self):
         if getattr(self, "_h", None):
             self._L.sfe_dsp_corr_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+def _sos(sos):
+    a = np.atleast_2d(np.ascontiguousarray(sos, dtype=np.float64))
+    if a.ndim != 2 or a.shape[1] != 6:
+        raise ValueError("sos must be (n_sections, 6) rows of (b0, b1, b2, a0, a1, a2)")
+    return np.ascontiguousarray(a)
+
+
+def iir_plan(sos):
+    """sfe_dsp_iir_plan (host only, no GPU): (block G, the granule of a call; float32 values of carried state per
+    stream and component).  Raises SfeError on coefficients the filter refuses."""
+    a = _sos(sos)
+    g, st = C.c_int(0), C.c_int(0)
+    check(_l.load().sfe_dsp_iir_plan(a.ctypes.data_as(C.POINTER(C.c_double)), int(a.shape[0]), C.byref(g), C.byref(st)))
+    return g.value, st.value
+
+
+class Iir:
+    """Streaming biquad-cascade IIR filter (sfe_dsp_iir_*): `sos` is (n_sections, 6) float64 rows (b0, b1, b2, a0, a1, a2)
+    (scipy's layout; synth.iir_* design some), run over n_streams complex (or, data_complex=False, real) streams."""
+
+    def __init__(self, sos, data_complex=True, n_streams=1, device=0):
+        self._L = _l.load()
+        a = _sos(sos)
+        self.n_sections, self.data_complex, self.n_streams = int(a.shape[0]), bool(data_complex), int(n_streams)
+        self.in_u8 = False
+        h = C.c_void_p()
+        check(self._L.sfe_dsp_iir_create(a.ctypes.data_as(C.POINTER(C.c_double)), self.n_sections, int(self.data_complex), self.n_streams,
+                                         device, C.byref(h)))
+        self._h = h.value
+        self.block = iir_plan(a)[0]
+
+    def set_input_format(self, fmt):
+        """lib.FMT_F32 (cf32, or float32 on a real handle) or lib.FMT_U8 ((I,Q) byte pairs, converted on load)."""
+        check(self._L.sfe_dsp_iir_set_input_format(self._h, fmt))
+        self.in_u8 = fmt == _l.FMT_U8
+
+    def reset(self):
+        check(self._L.sfe_dsp_iir_reset(self._h))
+
+    def process_stream(self, d_in, n_in, d_out, in_stride=None, out_stride=None, stream=None):
+        """d_in / d_out: DeviceArray or raw device pointers; n_in samples per stream (a multiple of self.block).  Stream s
+        goes from d_in + s*in_stride to d_out + s*out_stride samples; both strides default to n_in.  Returns n_out = n_in."""
+        pi = d_in.ptr if isinstance(d_in, DeviceArray) else int(d_in)
+        po = d_out.ptr if isinstance(d_out, DeviceArray) else int(d_out)
+        n_out = C.c_size_t(0)
+        check(self._L.sfe_dsp_iir_process_stream(self._h, pi, int(n_in), int(n_in) if in_stride is None else int(in_stride),
+                                                 po, int(n_in) if out_stride is None else int(out_stride), C.byref(n_out), stream))
+        return n_out.value
+
+    def filter(self, x):
+        """Host convenience, computed on the GPU, continuing the handle's state: x is (n_streams, n) complex64 -- float32
+        for a real handle, or (n_streams, n, 2) uint8 (I,Q) pairs with FMT_U8 -- (one dimension less for one stream).
+        The tail is padded with zeros to a multiple of the block (the filter is causal: the padding changes no sample
+        before it, but it does advance the state, so only the last piece of a stream may be ragged).  Returns x's
+        samples filtered, (n_streams, n) (or (n,)) complex64 / float32."""
+        G, S = self.block, self.n_streams
+        if self.in_u8:
+            b = np.ascontiguousarray(x, dtype=np.uint8).reshape(S, -1)
+            n = b.shape[1] // 2
+            one = S == 1 and np.ndim(x) <= 2                    # (n, 2) or 2n bytes
+            npad = -(-n // G) * G
+            z = np.full((S, 2 * npad), 128, np.uint8)           # byte 128 converts to 0.0
+            z[:, :2 * n] = b
+            d_in = DeviceArray.from_bytes(z)
+        else:
+            z = np.ascontiguousarray(x, dtype=np.complex64 if self.data_complex else np.float32).reshape(S, -1)
+            n = z.shape[1]
+            one = np.ndim(x) == 1
+            npad = -(-n // G) * G
+            zp = np.zeros((S, npad), z.dtype)
+            zp[:, :n] = z
+            d_in = DeviceArray.from_numpy(zp.view(np.float32))
+        w = 2 if self.data_complex else 1
+        d_out = DeviceArray(max(1, S * npad * w))
+        try:
+            if npad:
+                self.process_stream(d_in, npad, d_out)
+            y = d_out.to_numpy(S * npad * w)
+        finally:
+            d_in.free()
+            d_out.free()
+        y = (y.view(np.complex64) if self.data_complex else y).reshape(S, npad)[:, :n]
+        return np.ascontiguousarray(y[0] if one else y)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.sfe_dsp_iir_destroy(self._h)
             self._h = None
 
     __del__ = close

@@ -22,13 +22,14 @@ ARCH = "gfx950"
 # bit-exact restatements of the reference arithmetic: no implicit FMA contraction (chan.hip: its u8 and cf32
 # instantiations must give the same bits on the same samples; its multiply-adds are explicit; combine.hip: its TX10
 # bytes must be sfe_dsp_tx_f32_to_10bit's of its F32 output; ddc.hip: as chan.hip; psd.hip: as chan.hip, and its sums of
-# squares are folded in a stated order; corr.hip: as psd.hip)
-EXACT_SOURCES = ("polyphase.hip", "util.hip", "chan.hip", "combine.hip", "ddc.hip", "psd.hip", "corr.hip")
+# squares are folded in a stated order; corr.hip: as psd.hip; iir.hip: its u8, cf32 and real instantiations must run the
+# same explicit multiply-adds on the same samples)
+EXACT_SOURCES = ("polyphase.hip", "util.hip", "chan.hip", "combine.hip", "ddc.hip", "psd.hip", "corr.hip", "iir.hip")
 TICKET_SOURCES = ("fir_fft.hip", "poly_fft.hip")
 # host side only (handles, plans, launch choices, device groups):
 # not part of the kernel-source hash
 HOST_SOURCES = ("api.hip", "api_plans.hip", "api_fir.hip", "api_rs.hip", "api_pipe.hip", "api_chan.hip", "api_combine.hip", "api_ddc.hip",
-                "api_psd.hip", "api_corr.hip", "group.hip", "host.h")
+                "api_psd.hip", "api_corr.hip", "api_iir.hip", "group.hip", "host.h")
 
 
 def sources(diag=False):
@@ -46,7 +47,8 @@ def _deps():
 KERNEL_FILES = {"fir": ("fir_fft.hip", "fft16.h", "common.h"), "resample": ("poly_fft.hip", "fft16.h", "common.h"),
                 "decimate": ("polyphase.hip", "common.h"), "chan": ("chan.hip", "fft16.h", "common.h"),
                 "combine": ("combine.hip", "fft16.h", "common.h"), "ddc": ("ddc.hip", "common.h"),
-                "psd": ("psd.hip", "fft16.h", "common.h"), "corr": ("corr.hip", "fft16.h", "common.h")}
+                "psd": ("psd.hip", "fft16.h", "common.h"), "corr": ("corr.hip", "fft16.h", "common.h"),
+                "iir": ("iir.hip", "iir.h", "common.h")}
 
 
 def csrc_hash(kind=None):
@@ -172,8 +174,12 @@ def check_resources(res):
     for k, r in res.get("corr.hip", {}).items():
         if r.get("ScratchSize", 0) or r.get("VGPRs Spill", 0) or r.get("SGPRs Spill", 0):
             bad.append("%s: correlator kernel touches scratch: %s" % (k[:200], r))
+    # the IIR filter: a thread's run of samples, the section's scan and the fold's matrix row stay in registers
+    for k, r in res.get("iir.hip", {}).items():
+        if r.get("ScratchSize", 0) or r.get("VGPRs Spill", 0) or r.get("SGPRs Spill", 0):
+            bad.append("%s: IIR kernel touches scratch: %s" % (k[:200], r))
     if bad:
-        raise RuntimeError("FIR kernels of the default path and the channelizer, combiner, down-converter, spectrum-estimator and correlator kernels "
+        raise RuntimeError("FIR kernels of the default path and the channelizer, combiner, down-converter, spectrum-estimator, correlator and IIR kernels "
                            "must not touch scratch; "
                            "the FIR ones must keep "
                            "4 workgroups per CU:\n  " + "\n  ".join(bad))

@@ -1,0 +1,333 @@
+// api_iir.hip -- the IIR-filter handle behind sfe_iir_t, sfe_dsp_iir_* (include/sfe_dsp.h).  Host code only; the kernels
+// are in iir.hip.  Everything the kernels multiply by is computed here in float64 from the float32 coefficients of the
+// law and rounded once: the powers of each section's transition matrix and the cascade's transition over one block.
+#include <cmath>
+
+#include "host.h"
+#include "iir.h"
+
+namespace sfe {
+namespace {
+
+struct Iir {
+    uint32_t magic = 0x49495231u;   // 'IIR1'
+    int S = 0, data_complex = 1, n_streams = 1, device = 0, in_u8 = 0;
+    float *d_sec = nullptr;         // [S][IIR_SEC_FLOATS]
+    float *d_phi = nullptr;         // [2][2S][2S]: the cascade's transition over one block, and over one group of blocks
+    // carried, a pair (the current one and the next call's): per stream and component the true state, the open group's
+    // partial fold and its start state (iir.hip: struct IirSpan)
+    float *d_state[2] = {nullptr, nullptr};
+    int cur = 0;
+    float *d_table = nullptr;       // the per-block and per-group states of one call; grows with the largest call seen
+    size_t table_floats = 0;
+    unsigned long long blocks = 0;  // per stream since create / reset: the fold's groups are counted from there
+    int nc() const { return data_complex ? 2 : 1; }
+    size_t state_bytes() const { return (size_t)n_streams * nc() * 3 * 2 * S * sizeof(float); }
+};
+
+Iir *as_iir(void *h)
+{
+    Iir *p = static_cast<Iir *>(h);
+    if (p && p->magic != 0x49495231u) {
+        set_error("not a live IIR-filter handle");
+        return nullptr;
+    }
+    return p;
+}
+
+void iir_free(Iir *p)
+{
+    if (!p) return;
+    if (p->d_sec) (void)hipFree(p->d_sec);
+    if (p->d_phi) (void)hipFree(p->d_phi);
+    for (int i = 0; i < 2; i++)
+        if (p->d_state[i]) (void)hipFree(p->d_state[i]);
+    if (p->d_table) (void)hipFree(p->d_table);
+    p->magic = 0;
+    delete p;
+}
+
+struct Mat2 {
+    double m[4];
+};
+Mat2 mul2(const Mat2 &a, const Mat2 &b)
+{
+    return Mat2{{a.m[0] * b.m[0] + a.m[1] * b.m[2], a.m[0] * b.m[1] + a.m[1] * b.m[3], a.m[2] * b.m[0] + a.m[3] * b.m[2],
+                 a.m[2] * b.m[1] + a.m[3] * b.m[3]}};
+}
+
+// The float32 coefficients of the law, (b0, b1, b2, a1, a2) per section, from scipy-layout rows; the refusals.
+int iir_round(const double *sos, int S, float *coef)
+{
+    if (S < 1 || S > IIR_MAX_SECTIONS) {
+        set_error("iir: n_sections = %d must be in [1, %d]", S, IIR_MAX_SECTIONS);
+        return SFE_EINVAL;
+    }
+    if (!sos) {
+        set_error("iir: null coefficients");
+        return SFE_EINVAL;
+    }
+    for (int q = 0; q < S; q++) {
+        const double *r = sos + 6 * q;
+        for (int k = 0; k < 6; k++)
+            if (!std::isfinite(r[k])) {
+                set_error("iir: section %d has a non-finite coefficient", q);
+                return SFE_EINVAL;
+            }
+        if (r[3] == 0.0) {
+            set_error("iir: section %d has a0 = 0", q);
+            return SFE_EINVAL;
+        }
+        float *c = coef + 5 * q;
+        c[0] = (float)(r[0] / r[3]);
+        c[1] = (float)(r[1] / r[3]);
+        c[2] = (float)(r[2] / r[3]);
+        c[3] = (float)(r[4] / r[3]);
+        c[4] = (float)(r[5] / r[3]);
+        for (int k = 0; k < 5; k++)
+            if (!std::isfinite(c[k])) {
+                set_error("iir: section %d has a coefficient outside float32 after the division by a0", q);
+                return SFE_EINVAL;
+            }
+        // the stability triangle, on the values the kernel multiplies by
+        const double a1 = c[3], a2 = c[4];
+        if (!(std::fabs(a2) < 1.0 && std::fabs(a1) < 1.0 + a2)) {
+            set_error("iir: section %d is not strictly stable in float32 (a1 = %.9g, a2 = %.9g: need |a2| < 1 and |a1| < 1 + a2)", q,
+                      a1, a2);
+            return SFE_EINVAL;
+        }
+    }
+    return SFE_OK;
+}
+
+// One section's table (struct IirSec of iir.hip)
+void iir_section_table(const float *c, float *t)
+{
+    const int R = 16;
+    std::fill(t, t + IIR_SEC_FLOATS, 0.0f);
+    std::copy(c, c + 5, t);
+    const Mat2 A{{-(double)c[3], 1.0, -(double)c[4], 0.0}};
+    Mat2 pw{{1.0, 0.0, 0.0, 1.0}};
+    float *corr = t + 8 + 7 * 4;
+    for (int k = 0; k < R; k++) {           // [1 0] A^k
+        corr[2 * k] = (float)pw.m[0];
+        corr[2 * k + 1] = (float)pw.m[1];
+        pw = mul2(pw, A);
+    }
+    const Mat2 AR = pw;                     // A^16
+    Mat2 sq = AR;
+    for (int k = 0; k < 7; k++) {           // A^(16 2^k)
+        for (int e = 0; e < 4; e++) t[8 + 4 * k + e] = (float)sq.m[e];
+        sq = mul2(sq, sq);
+    }
+    float *P = t + 8 + 7 * 4 + R * 2;
+    pw = Mat2{{1.0, 0.0, 0.0, 1.0}};
+    for (int l = 0; l < 64; l++) {          // A^(16 l)
+        for (int e = 0; e < 4; e++) P[4 * l + e] = (float)pw.m[e];
+        pw = mul2(pw, AR);
+    }
+}
+
+// The cascade as one linear system of 2S states (s.x, s.y of section 0, of section 1, ...): its transition over `block`
+// samples of zero input, row-major, followed by the same over `group` blocks (each rounded once from float64)
+std::vector<float> iir_phi(const float *coef, int S, int block, int group)
+{
+    const int n = 2 * S;
+    std::vector<double> T((size_t)n * n, 0.0), u(n), y(n);
+    std::fill(u.begin(), u.end(), 0.0);     // the section's input as a row over the states: zero for section 0
+    for (int q = 0; q < S; q++) {
+        const double b0 = coef[5 * q], b1 = coef[5 * q + 1], b2 = coef[5 * q + 2], a1 = coef[5 * q + 3], a2 = coef[5 * q + 4];
+        for (int k = 0; k < n; k++) y[k] = b0 * u[k] + (k == 2 * q ? 1.0 : 0.0);
+        for (int k = 0; k < n; k++) {
+            T[(size_t)(2 * q) * n + k] = b1 * u[k] - a1 * y[k] + (k == 2 * q + 1 ? 1.0 : 0.0);
+            T[(size_t)(2 * q + 1) * n + k] = b2 * u[k] - a2 * y[k];
+        }
+        u = y;
+    }
+    std::vector<double> tmp((size_t)n * n);
+    auto square = [&](int times) {          // block and group are powers of two
+        for (int b = times; b > 1; b >>= 1) {
+            for (int i = 0; i < n; i++)
+                for (int j = 0; j < n; j++) {
+                    double acc = 0.0;
+                    for (int k = 0; k < n; k++) acc += T[(size_t)i * n + k] * T[(size_t)k * n + j];
+                    tmp[(size_t)i * n + j] = acc;
+                }
+            T.swap(tmp);
+        }
+    };
+    square(block);
+    std::vector<float> out(T.begin(), T.end());
+    square(group);
+    out.insert(out.end(), T.begin(), T.end());
+    return out;
+}
+
+}  // namespace
+}  // namespace sfe
+
+using namespace sfe;
+
+extern "C" {
+
+int sfe_dsp_iir_plan(const double *sos, int n_sections, int *block, int *state_floats)
+{
+    float coef[5 * IIR_MAX_SECTIONS];
+    const int rc = iir_round(sos, n_sections, coef);
+    if (rc != SFE_OK) return rc;
+    if (block) *block = iir_block();
+    if (state_floats) *state_floats = 3 * 2 * n_sections;
+    return SFE_OK;
+}
+
+int sfe_dsp_iir_create(const double *sos, int n_sections, int data_complex, int n_streams, int device, sfe_iir_t *out)
+{
+    if (!out) return SFE_EINVAL;
+    *out = nullptr;
+    float coef[5 * IIR_MAX_SECTIONS];
+    int rc = iir_round(sos, n_sections, coef);
+    if (rc != SFE_OK) return rc;
+    if (n_streams < 1 || n_streams > 32767) {
+        set_error("iir: n_streams = %d must be in [1, 32767]", n_streams);
+        return SFE_EINVAL;
+    }
+    int prev_dev = -1;
+    (void)hipGetDevice(&prev_dev);
+    rc = use_device(device);
+    if (rc != SFE_OK) return rc;
+    struct Restore { int d; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore__{prev_dev};
+    Iir *p = new (std::nothrow) Iir;
+    if (!p) return SFE_ENOMEM;
+    p->S = n_sections;
+    p->data_complex = data_complex ? 1 : 0;
+    p->n_streams = n_streams;
+    p->device = device;
+    auto fail = [&](int code) { iir_free(p); return code; };
+#define TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail(hip_fail(e__, #call)); } while (0)
+    std::vector<float> sec((size_t)n_sections * IIR_SEC_FLOATS);
+    for (int q = 0; q < n_sections; q++) iir_section_table(coef + 5 * q, sec.data() + (size_t)q * IIR_SEC_FLOATS);
+    const std::vector<float> phi = iir_phi(coef, n_sections, iir_block(), iir_group());
+    TRY(hipMalloc(&p->d_sec, sec.size() * sizeof(float)));
+    TRY(hipMemcpy(p->d_sec, sec.data(), sec.size() * sizeof(float), hipMemcpyHostToDevice));
+    TRY(hipMalloc(&p->d_phi, phi.size() * sizeof(float)));
+    TRY(hipMemcpy(p->d_phi, phi.data(), phi.size() * sizeof(float), hipMemcpyHostToDevice));
+    for (int i = 0; i < 2; i++) {
+        TRY(hipMalloc(&p->d_state[i], p->state_bytes()));
+        TRY(hipMemset(p->d_state[i], 0, p->state_bytes()));
+    }
+    TRY(hipDeviceSynchronize());
+#undef TRY
+    *out = p;
+    return SFE_OK;
+}
+
+int sfe_dsp_iir_set_input_format(sfe_iir_t h, int fmt)
+{
+    Iir *p = as_iir(h);
+    if (!p || (fmt != SFE_FMT_F32 && fmt != SFE_FMT_U8)) {
+        set_error("iir_set_input_format: null handle or a format other than SFE_FMT_F32 / SFE_FMT_U8");
+        return SFE_EINVAL;
+    }
+    if (fmt == SFE_FMT_U8 && !p->data_complex) {
+        set_error("iir_set_input_format: SFE_FMT_U8 is (I,Q) byte pairs: not for a real handle");
+        return SFE_EINVAL;
+    }
+    p->in_u8 = fmt == SFE_FMT_U8;
+    return SFE_OK;
+}
+
+int sfe_dsp_iir_process_stream(sfe_iir_t h, const void *d_in, size_t n_in, size_t in_stride, void *d_out, size_t out_stride,
+                               size_t *n_out, sfe_stream_t stream)
+{
+    Iir *p = as_iir(h);
+    if (n_out) *n_out = 0;
+    if (!p || !n_out) {
+        set_error("iir_process_stream: null handle or n_out");
+        return SFE_EINVAL;
+    }
+    const size_t G = (size_t)iir_block();
+    if (n_in % G) {
+        set_error("iir_process_stream: n_in = %zu is not a multiple of the block = %zu", n_in, G);
+        return SFE_EINVAL;
+    }
+    if (n_in >= ((size_t)1 << 31)) {
+        set_error("iir_process_stream: n_in = %zu must be below 2^31", n_in);
+        return SFE_EINVAL;
+    }
+    if (n_in == 0) return SFE_OK;
+    if (!d_in || !d_out) {
+        set_error("iir_process_stream: null buffer");
+        return SFE_EINVAL;
+    }
+    if (out_stride < n_in) {
+        set_error("iir_process_stream: out_stride %zu < n_in = %zu", out_stride, n_in);
+        return SFE_ERANGE;
+    }
+    if (p->n_streams > 1 && in_stride < n_in) {
+        set_error("iir_process_stream: in_stride %zu < n_in %zu with %d streams", in_stride, n_in, p->n_streams);
+        return SFE_EINVAL;
+    }
+    const size_t isz = p->in_u8 ? 2 : p->data_complex ? 8 : 4, osz = p->data_complex ? 8 : 4;
+    if ((reinterpret_cast<uintptr_t>(d_in) & (isz - 1)) || (reinterpret_cast<uintptr_t>(d_out) & (osz - 1))) {
+        set_error("iir_process_stream: buffers must be aligned to their element (cf32 8 B, u8 (I,Q) pairs 2 B, float32 4 B)");
+        return SFE_EINVAL;
+    }
+    const size_t in_b = ((size_t)(p->n_streams - 1) * in_stride + n_in) * isz;
+    const size_t out_b = ((size_t)(p->n_streams - 1) * out_stride + n_in) * osz;
+    if (ranges_overlap(d_in, in_b, d_out, out_b)) {
+        set_error("iir_process_stream: input and output ranges overlap (in-place operation is not supported)");
+        return SFE_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (stream_is_capturing(s)) {
+        // the block counter and the buffer pair of the carried state advance on the host
+        set_error("iir_process_stream: graph capture is not supported (the sample counter lives on the host)");
+        return SFE_ESTATE;
+    }
+    SFE_ON_DEVICE(p->device);
+    // the one allocation a call may make: the table of block and group states grows when a larger call than any before arrives
+    // (sized for the most groups a call of nb blocks can touch, wherever it starts)
+    const size_t nb = n_in / G, K = (size_t)iir_group(), need = (nb + (nb + K - 2) / K + 1) * p->n_streams * p->nc() * 2 * p->S;
+    if (need > p->table_floats) {
+        SFE_HIP(hipDeviceSynchronize());
+        if (p->d_table) (void)hipFree(p->d_table);
+        p->d_table = nullptr;
+        p->table_floats = 0;
+        SFE_HIP(hipMalloc(&p->d_table, need * sizeof(float)));
+        p->table_floats = need;
+    }
+    const int fmt = p->in_u8 ? 1 : p->data_complex ? 0 : 2;
+    const int n2 = 2 * p->S, c = p->cur;
+    const int rc = launch_iir(fmt, d_in, (long long)in_stride, d_out, (long long)out_stride, p->d_sec, p->d_phi, p->d_phi + n2 * n2,
+                              p->d_table, p->d_state[c], p->d_state[c ^ 1], (long long)p->blocks, (int)nb, p->S, p->n_streams, s);
+    if (rc != SFE_OK) return rc;
+    p->cur ^= 1;
+    p->blocks += nb;
+    *n_out = n_in;
+    return SFE_OK;
+}
+
+int sfe_dsp_iir_reset(sfe_iir_t h)
+{
+    Iir *p = as_iir(h);
+    if (!p) return SFE_EINVAL;
+    SFE_ON_DEVICE(p->device);
+    SFE_HIP(hipDeviceSynchronize());
+    for (int i = 0; i < 2; i++) SFE_HIP(hipMemset(p->d_state[i], 0, p->state_bytes()));
+    SFE_HIP(hipDeviceSynchronize());
+    p->cur = 0;
+    p->blocks = 0;
+    return SFE_OK;
+}
+
+int sfe_dsp_iir_destroy(sfe_iir_t h)
+{
+    Iir *p = as_iir(h);
+    if (!p) return SFE_OK;
+    DeviceGuard g(p->device);
+    (void)hipDeviceSynchronize();
+    iir_free(p);
+    return SFE_OK;
+}
+
+}  // extern "C"

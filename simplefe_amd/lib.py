@@ -136,6 +136,12 @@ SIGNATURES = {
     "sfe_dsp_corr_process_stream": (i32, [vp, vp, sz, sz, vp, vp, sz, vp, sz, C.POINTER(sz), vp]),
     "sfe_dsp_corr_reset": (i32, [vp]),
     "sfe_dsp_corr_destroy": (i32, [vp]),
+    "sfe_dsp_iir_plan": (i32, [C.POINTER(C.c_double), i32, C.POINTER(i32), C.POINTER(i32)]),
+    "sfe_dsp_iir_create": (i32, [C.POINTER(C.c_double), i32, i32, i32, i32, C.POINTER(vp)]),
+    "sfe_dsp_iir_set_input_format": (i32, [vp, i32]),
+    "sfe_dsp_iir_process_stream": (i32, [vp, vp, sz, sz, vp, sz, C.POINTER(sz), vp]),
+    "sfe_dsp_iir_reset": (i32, [vp]),
+    "sfe_dsp_iir_destroy": (i32, [vp]),
 }
 
 # the diagnostic library only (simplefe_amd/csrc/diag/sfe_dsp_diag.h; scripts/ load it by pointing LIB_PATH at it): bound when present

@@ -354,3 +354,110 @@ def corr_reference_direct(x, templates, min_energy, first, points):
             e += abs(v) ** 2
         out.append(abs(c) ** 2 / (E * e) if e > min_energy else 0.0)
     return np.array(out)
+
+
+# ---- the biquad-cascade IIR filter (sfe_dsp_iir_*): designers that return float64 sos rows (b0, b1, b2, a0, a1, a2), the
+# float32 coefficients of the law, and the law itself sample by sample
+def iir_dc_blocker(r):
+    """y[i] = x[i] - x[i-1] + r y[i-1]: a zero at DC, a pole at radius r."""
+    return np.array([[1.0, -1.0, 0.0, 1.0, -float(r), 0.0]])
+
+
+def iir_one_pole(a):
+    """y[i] = (1 - a) x[i] + a y[i-1]: unit DC gain."""
+    return np.array([[1.0 - float(a), 0.0, 0.0, 1.0, -float(a), 0.0]])
+
+
+def iir_notch(f0, q):
+    """The RBJ cookbook notch at f0 cycles per sample with quality q."""
+    w0 = 2.0 * np.pi * float(f0)
+    al = np.sin(w0) / (2.0 * float(q))
+    return np.array([[1.0, -2.0 * np.cos(w0), 1.0, 1.0 + al, -2.0 * np.cos(w0), 1.0 - al]])
+
+
+def iir_butter_lowpass(order, fc):
+    """Butterworth low-pass of even `order`, -3 dB at fc cycles per sample: order / 2 RBJ low-pass sections with
+    Q_k = 1 / (2 sin((2k + 1) pi / (2 order)))."""
+    order = int(order)
+    if order < 2 or order % 2:
+        raise ValueError("iir_butter_lowpass: order must be even and >= 2")
+    w0 = 2.0 * np.pi * float(fc)
+    c, s = np.cos(w0), np.sin(w0)
+    rows = []
+    for k in range(order // 2):
+        al = s * np.sin((2 * k + 1) * np.pi / (2.0 * order))       # sin(w0) / (2 Q_k)
+        rows.append([(1.0 - c) / 2.0, 1.0 - c, (1.0 - c) / 2.0, 1.0 + al, -2.0 * c, 1.0 - al])
+    return np.array(rows)
+
+
+def iir_round(sos):
+    """The float32 values the law is stated on: (S, 5) rows (B0, B1, B2, A1, A2) = the sos rows divided by a0 in
+    float64, each rounded once."""
+    sos = np.atleast_2d(np.asarray(sos, dtype=np.float64))
+    return (sos[:, [0, 1, 2, 4, 5]] / sos[:, 3:4]).astype(np.float32)
+
+
+def iir_reference(x, sos, dtype=np.float64):
+    """The law of sfe_dsp_iir_* sample by sample on the rounded coefficients, zero state before x[0].  x is (..., n) real
+    or complex (I and Q never mix); the result has x's shape, float64 / complex128.  With dtype=np.float32 every product
+    and every sum is rounded to float32, in the order ((B0 v[i] + B1 v[i-1]) + B2 v[i-2]) - A1 y[i-1] - A2 y[i-2]: the
+    yardstick of what float32 itself makes of the recursion."""
+    x = np.asarray(x)
+    cplx = np.iscomplexobj(x)
+    v = x.astype(np.complex128).view(np.float64).reshape(x.shape + (2,)) if cplx else x.astype(np.float64)[..., None]
+    n = x.shape[-1]
+    v = np.moveaxis(v, -2, 0).reshape(n, -1)                # (n, columns): time first
+    c32 = iir_round(sos)
+    if dtype == np.float64:
+        try:                                # the same recursion compiled, where scipy is installed
+            from scipy.signal import sosfilt
+            c = c32.astype(np.float64)
+            rows = np.ascontiguousarray(np.concatenate([c[:, :3], np.ones((c.shape[0], 1)), c[:, 3:]], axis=1))
+            y = sosfilt(rows, v, axis=0)
+        except ImportError:
+            y = _iir_loop(v, c32.astype(np.float64), np.float64)
+    else:
+        y = _iir_loop(v.astype(np.float32), c32, np.float32).astype(np.float64)
+    y = np.moveaxis(y.reshape((n,) + x.shape[:-1] + (2 if cplx else 1,)), 0, -2)
+    return np.ascontiguousarray(y).view(np.complex128)[..., 0] if cplx else y[..., 0]
+
+
+def _iir_loop(v, coef, dt):
+    """(n, columns) through the cascade; every operation in dt."""
+    n = v.shape[0]
+    for b0, b1, b2, a1, a2 in coef.astype(dt):
+        w = b0 * v                                          # the feed-forward part has no recursion: whole columns at once
+        if b1 != 0:
+            w[1:] = w[1:] + b1 * v[:-1]
+        if b2 != 0:
+            w[2:] = w[2:] + b2 * v[:-2]
+        y = np.empty_like(w)
+        y1 = y2 = np.zeros(v.shape[1], dt)
+        for i in range(n):
+            t = w[i] - a1 * y1
+            if a2 != 0:
+                t = t - a2 * y2
+            y[i] = t
+            y2, y1 = y1, t
+        v = y
+    return v
+
+
+def iir_grid_filters():
+    """The filters the IIR tests and scripts/time_iir.py share, by name: S = 1, 1, 1, 1, 2, 8 and 5 sections."""
+    return {"dc(0.995)": iir_dc_blocker(0.995), "dc(0.9999)": iir_dc_blocker(0.9999), "notch(0.125,30)": iir_notch(0.125, 30.0),
+            "notch(0.125,1000)": iir_notch(0.125, 1000.0), "butter(4,0.025)": iir_butter_lowpass(4, 0.025),
+            "butter(16,0.1)": iir_butter_lowpass(16, 0.1),
+            "dc(0.999)+butter(8,0.1)": np.vstack([iir_dc_blocker(0.999), iir_butter_lowpass(8, 0.1)])}
+
+
+def offset_bytes(n_samples, bias=0, seed=SEED):
+    """2 n uint8 (I,Q) bytes, uniformly random: over all 256 values with bias = 0 (the converted stream has a mean near 0),
+    or over [2 bias, 256) (a mean near 128 + bias: bias = 38 gives bytes around 166, a converted mean near 0.3)."""
+    rng = np.random.default_rng(seed)
+    return rng.integers(2 * int(bias), 256, size=2 * int(n_samples), dtype=np.uint8)
+
+
+def u8_to_cf32(b):
+    """The receive converter's law (sfe_dsp_rx_u8_to_f32) in float32: (b - 128) * (1/127)."""
+    return ((np.asarray(b, dtype=np.uint8).astype(np.float32) - np.float32(128.0)) * np.float32(1.0 / 127.0)).view(np.complex64)
