@@ -418,6 +418,61 @@ class Rs:
     __del__ = close
 
 
+class _Block:
+    """What the wrappers of the streaming blocks share: the handle behind `_h`, made by sfe_dsp_<_prefix>_create and
+    destroyed by close(), the block's reset, and the pointer and upload plumbing of their calls."""
+    _prefix = None              # the block's functions are sfe_dsp_<_prefix>_*
+
+    def _fn(self, name):
+        return getattr(self._L, "sfe_dsp_%s_%s" % (self._prefix, name))
+
+    def _create(self, *args):
+        self._L = _l.load()
+        h = C.c_void_p()
+        check(self._fn("create")(*args, C.byref(h)))
+        self._h = h.value
+
+    @staticmethod
+    def _ptr(d):
+        return d.ptr if isinstance(d, DeviceArray) else (None if d is None else int(d))
+
+    def _set_input_format(self, fmt):
+        check(self._fn("set_input_format")(self._h, fmt))
+        self.in_u8 = fmt == _l.FMT_U8
+
+    def _process_stream(self, d_in, n_in, in_stride, d_out, out_stride, stream):
+        """The call most blocks share; in_stride None: n_in.  Returns what the library counted."""
+        k = C.c_size_t(0)
+        check(self._fn("process_stream")(self._h, self._ptr(d_in), int(n_in), int(n_in) if in_stride is None else int(in_stride),
+                                         self._ptr(d_out), int(out_stride), C.byref(k), stream))
+        return k.value
+
+    def _upload_input(self, x, granule=1):
+        """x as (n_streams, n) samples in the handle's input format -- (I,Q) bytes with FMT_U8, complex64, or float32 on a
+        real handle -- each row padded with zero samples to a multiple of `granule`; returns (its DeviceArray, n)."""
+        if self.in_u8:
+            a, w, zero = np.ascontiguousarray(x, dtype=np.uint8).reshape(self.n_streams, -1), 2, 128   # byte 128 converts to 0.0
+        elif getattr(self, "data_complex", True):     # the blocks without a real form have no such attribute
+            a, w, zero = np.ascontiguousarray(x, dtype=np.complex64).reshape(self.n_streams, -1).view(np.float32), 2, 0
+        else:
+            a, w, zero = np.ascontiguousarray(x, dtype=np.float32).reshape(self.n_streams, -1), 1, 0
+        n = a.shape[1] // w
+        npad = -(-n // granule) * granule
+        if npad != n:
+            a = np.concatenate([a[:, :w * n], np.full((self.n_streams, w * (npad - n)), zero, a.dtype)], axis=1)
+        return (DeviceArray.from_bytes(a) if self.in_u8 else DeviceArray.from_numpy(a)), n
+
+    def reset(self):
+        check(self._fn("reset")(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._fn("destroy")(self._h)
+            self._h = None
+
+    __del__ = close
+
+
 def chan_plan(n_taps, n_chans, decim):
     """sfe_dsp_chan_plan (host only, no GPU): (taps per branch P, samples of history carried per stream)."""
     P, H = C.c_int(0), C.c_int(0)
@@ -425,50 +480,30 @@ def chan_plan(n_taps, n_chans, decim):
     return P.value, H.value
 
 
-class Chan:
+class Chan(_Block):
     """Polyphase filter-bank channelizer (sfe_dsp_chan_*): n_chans = M sub-bands of n_streams complex streams, one
     output every `decim` (M or M/2) input samples per channel; real prototype taps."""
+    _prefix = "chan"
 
     def __init__(self, taps, n_chans, decim, n_streams=1, device=0):
-        self._L = _l.load()
         t = _f32(taps)
         self.n_chans, self.decim, self.n_streams = int(n_chans), int(decim), int(n_streams)
         self.in_u8 = False
-        h = C.c_void_p()
-        check(self._L.sfe_dsp_chan_create(t.ctypes.data, t.size, self.n_chans, self.decim, self.n_streams, device,
-                                          C.byref(h)))
-        self._h = h.value
+        self._create(t.ctypes.data, t.size, self.n_chans, self.decim, self.n_streams, device)
 
     def set_input_format(self, fmt):
         """lib.FMT_F32 (cf32) or lib.FMT_U8 ((I,Q) byte pairs, converted on load)."""
-        check(self._L.sfe_dsp_chan_set_input_format(self._h, fmt))
-        self.in_u8 = fmt == _l.FMT_U8
-
-    def reset(self):
-        check(self._L.sfe_dsp_chan_reset(self._h))
+        self._set_input_format(fmt)
 
     def process_stream(self, d_in, n_in, d_out, in_stride=None, out_stride=None, stream=None):
         """d_in / d_out: DeviceArray or raw device pointers; n_in samples per stream (a multiple of decim).  Channel k
         of stream s goes to d_out + (s*M + k)*out_stride cf32 samples.  Returns n_out = n_in / decim."""
-        pi = d_in.ptr if isinstance(d_in, DeviceArray) else int(d_in)
-        po = d_out.ptr if isinstance(d_out, DeviceArray) else int(d_out)
-        n_out = C.c_size_t(0)
-        check(self._L.sfe_dsp_chan_process_stream(self._h, pi, int(n_in), int(n_in) if in_stride is None else int(in_stride),
-                                                  po, int(n_in) // self.decim if out_stride is None else int(out_stride),
-                                                  C.byref(n_out), stream))
-        return n_out.value
+        return self._process_stream(d_in, n_in, in_stride, d_out, int(n_in) // self.decim if out_stride is None else out_stride, stream)
 
     def channelize(self, x):
         """Host convenience, computed on the GPU: x is (n_streams, n) complex -- or, with FMT_U8, (n_streams, 2n)
         uint8 (I,Q) pairs -- (1-D for one stream); returns (n_streams, M, n // decim) complex64."""
-        if self.in_u8:
-            b = np.ascontiguousarray(x, dtype=np.uint8).reshape(self.n_streams, -1)
-            n = b.shape[1] // 2
-            d_in = DeviceArray.from_bytes(b)
-        else:
-            z = np.ascontiguousarray(x, dtype=np.complex64).reshape(self.n_streams, -1)
-            n = z.shape[1]
-            d_in = DeviceArray.from_numpy(z.view(np.float32))
+        d_in, n = self._upload_input(x)
         n_out = n // self.decim
         d_out = DeviceArray(max(1, self.n_streams * self.n_chans * n_out) * 2)
         try:
@@ -479,13 +514,6 @@ class Chan:
             d_out.free()
         return y.view(np.complex64).reshape(self.n_streams, self.n_chans, k)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.sfe_dsp_chan_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
 
 def combine_plan(n_taps, n_chans, interp):
     """sfe_dsp_combine_plan (host only, no GPU): (taps per output phase P, instants of history carried per stream)."""
@@ -494,39 +522,27 @@ def combine_plan(n_taps, n_chans, interp):
     return P.value, H.value
 
 
-class Combiner:
+class Combiner(_Block):
     """Polyphase synthesis filter bank (sfe_dsp_combine_*): n_chans = M baseband channels of n_streams streams, each
     interpolated by `interp` (M or M/2), shifted up to its sub-band and summed; real prototype taps."""
+    _prefix = "combine"
 
     def __init__(self, taps, n_chans, interp, n_streams=1, device=0):
-        self._L = _l.load()
         t = _f32(taps)
         self.n_chans, self.interp, self.n_streams = int(n_chans), int(interp), int(n_streams)
         self.out_tx10 = False
-        h = C.c_void_p()
-        check(self._L.sfe_dsp_combine_create(t.ctypes.data, t.size, self.n_chans, self.interp, self.n_streams, device,
-                                             C.byref(h)))
-        self._h = h.value
+        self._create(t.ctypes.data, t.size, self.n_chans, self.interp, self.n_streams, device)
 
     def set_output_format(self, fmt):
         """lib.FMT_F32 (cf32) or lib.FMT_TX10 (the transmit wire format, 2 complex samples in 5 bytes)."""
-        check(self._L.sfe_dsp_combine_set_output_format(self._h, fmt))
+        check(self._fn("set_output_format")(self._h, fmt))
         self.out_tx10 = fmt == _l.FMT_TX10
-
-    def reset(self):
-        check(self._L.sfe_dsp_combine_reset(self._h))
 
     def process_stream(self, d_in, n_in, d_out, in_stride=None, out_stride=None, stream=None):
         """d_in / d_out: DeviceArray or raw device pointers; n_in instants per channel.  Channel k of stream s is read at
         d_in + (s*M + k)*in_stride cf32 samples; stream s is written at d_out + s*out_stride samples (TX10: at
         s*(out_stride/2)*5 bytes).  Returns n_out = n_in * interp."""
-        pi = d_in.ptr if isinstance(d_in, DeviceArray) else int(d_in)
-        po = d_out.ptr if isinstance(d_out, DeviceArray) else int(d_out)
-        n_out = C.c_size_t(0)
-        check(self._L.sfe_dsp_combine_process_stream(self._h, pi, int(n_in), int(n_in) if in_stride is None else int(in_stride),
-                                                     po, int(n_in) * self.interp if out_stride is None else int(out_stride),
-                                                     C.byref(n_out), stream))
-        return n_out.value
+        return self._process_stream(d_in, n_in, in_stride, d_out, int(n_in) * self.interp if out_stride is None else out_stride, stream)
 
     def combine(self, X):
         """Host convenience, computed on the GPU: X is (n_streams, M, n) complex ((M, n) for one stream); returns
@@ -547,13 +563,6 @@ class Combiner:
             return y.view(np.uint8)[: self.n_streams * (k // 2 * 5)].reshape(self.n_streams, -1)
         return y[: self.n_streams * 2 * k].view(np.complex64).reshape(self.n_streams, k)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.sfe_dsp_combine_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
 
 def ddc_plan(n_taps, decim, freqs):
     """sfe_dsp_ddc_plan (host only, no GPU): (taps per branch P, samples of history carried per stream, the quantised
@@ -566,64 +575,41 @@ def ddc_plan(n_taps, decim, freqs):
     return P.value, H.value, [int(v) for v in inc[:f.size]]
 
 
-class Ddc:
+class Ddc(_Block):
     """Digital down-converter bank (sfe_dsp_ddc_*): len(freqs) = K tunings of n_streams streams, each shifted down by its
     frequency (cycles per sample, quantised to a 32-bit NCO increment), filtered by the real prototype `taps` and
     decimated by `decim`.  data_complex=False takes real float32 input; the output is always complex."""
+    _prefix = "ddc"
 
     def __init__(self, taps, decim, freqs, data_complex=True, n_streams=1, device=0):
-        self._L = _l.load()
         t = _f32(taps)
         f = np.ascontiguousarray(freqs, dtype=np.float64).ravel()
         self.decim, self.n_tunings, self.n_streams = int(decim), int(f.size), int(n_streams)
         self.data_complex = bool(data_complex)
         self.in_u8 = False
-        h = C.c_void_p()
-        check(self._L.sfe_dsp_ddc_create(t.ctypes.data, t.size, self.decim, self.n_tunings, f.ctypes.data_as(C.POINTER(C.c_double)),
-                                         int(self.data_complex), self.n_streams, device, C.byref(h)))
-        self._h = h.value
+        self._create(t.ctypes.data, t.size, self.decim, self.n_tunings, f.ctypes.data_as(C.POINTER(C.c_double)), int(self.data_complex),
+                     self.n_streams, device)
 
     def set_input_format(self, fmt):
         """lib.FMT_F32 (cf32, or float32 for a real handle) or lib.FMT_U8 ((I,Q) byte pairs, converted on load)."""
-        check(self._L.sfe_dsp_ddc_set_input_format(self._h, fmt))
-        self.in_u8 = fmt == _l.FMT_U8
+        self._set_input_format(fmt)
 
     def set_freqs(self, freqs):
         """K new frequencies, used from the next call on (no phase continuity across the retune)."""
         f = np.ascontiguousarray(freqs, dtype=np.float64).ravel()
         if f.size != self.n_tunings:
             raise ValueError("set_freqs: %d frequencies for %d tunings" % (f.size, self.n_tunings))
-        check(self._L.sfe_dsp_ddc_set_freqs(self._h, f.ctypes.data_as(C.POINTER(C.c_double))))
-
-    def reset(self):
-        check(self._L.sfe_dsp_ddc_reset(self._h))
+        check(self._fn("set_freqs")(self._h, f.ctypes.data_as(C.POINTER(C.c_double))))
 
     def process_stream(self, d_in, n_in, d_out, in_stride=None, out_stride=None, stream=None):
         """d_in / d_out: DeviceArray or raw device pointers; n_in samples per stream (a multiple of decim).  Tuning k of
         stream s goes to d_out + (s*K + k)*out_stride cf32 samples.  Returns n_out = n_in / decim."""
-        pi = d_in.ptr if isinstance(d_in, DeviceArray) else int(d_in)
-        po = d_out.ptr if isinstance(d_out, DeviceArray) else int(d_out)
-        n_out = C.c_size_t(0)
-        check(self._L.sfe_dsp_ddc_process_stream(self._h, pi, int(n_in), int(n_in) if in_stride is None else int(in_stride),
-                                                 po, int(n_in) // self.decim if out_stride is None else int(out_stride),
-                                                 C.byref(n_out), stream))
-        return n_out.value
+        return self._process_stream(d_in, n_in, in_stride, d_out, int(n_in) // self.decim if out_stride is None else out_stride, stream)
 
     def downconvert(self, x):
         """Host convenience, computed on the GPU: x is (n_streams, n) complex -- real for a real handle, or, with FMT_U8,
         (n_streams, 2n) uint8 (I,Q) pairs -- (1-D for one stream); returns (n_streams, K, n // decim) complex64."""
-        if self.in_u8:
-            b = np.ascontiguousarray(x, dtype=np.uint8).reshape(self.n_streams, -1)
-            n = b.shape[1] // 2
-            d_in = DeviceArray.from_bytes(b)
-        elif self.data_complex:
-            z = np.ascontiguousarray(x, dtype=np.complex64).reshape(self.n_streams, -1)
-            n = z.shape[1]
-            d_in = DeviceArray.from_numpy(z.view(np.float32))
-        else:
-            z = np.ascontiguousarray(x, dtype=np.float32).reshape(self.n_streams, -1)
-            n = z.shape[1]
-            d_in = DeviceArray.from_numpy(z)
+        d_in, n = self._upload_input(x)
         n_out = n // self.decim
         d_out = DeviceArray(max(1, self.n_streams * self.n_tunings * n_out) * 2)
         try:
@@ -634,13 +620,6 @@ class Ddc:
             d_out.free()
         return y.view(np.complex64).reshape(self.n_streams, self.n_tunings, k)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.sfe_dsp_ddc_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
 
 def psd_plan(n_fft, hop, n_avg):
     """sfe_dsp_psd_plan (host only, no GPU): (segments per chunk C of the summation order, samples of history carried
@@ -650,52 +629,33 @@ def psd_plan(n_fft, hop, n_avg):
     return c.value, h.value
 
 
-class Psd:
+class Psd(_Block):
     """Streaming Welch spectrum estimator (sfe_dsp_psd_*): scale times the sum of n_avg windowed periodograms of
     n_fft = len(window) samples, one every `hop` samples, of n_streams complex streams."""
+    _prefix = "psd"
 
     def __init__(self, window, hop, n_avg, scale=1.0, n_streams=1, device=0):
-        self._L = _l.load()
         w = _f32(window).ravel()
         self.n_fft, self.hop, self.n_avg, self.n_streams = int(w.size), int(hop), int(n_avg), int(n_streams)
         self.in_u8 = False
-        h = C.c_void_p()
-        check(self._L.sfe_dsp_psd_create(w.ctypes.data, self.n_fft, self.hop, self.n_avg, float(scale), self.n_streams, device,
-                                         C.byref(h)))
-        self._h = h.value
+        self._create(w.ctypes.data, self.n_fft, self.hop, self.n_avg, float(scale), self.n_streams, device)
 
     def set_input_format(self, fmt):
         """lib.FMT_F32 (cf32) or lib.FMT_U8 ((I,Q) byte pairs, converted on load)."""
-        check(self._L.sfe_dsp_psd_set_input_format(self._h, fmt))
-        self.in_u8 = fmt == _l.FMT_U8
-
-    def reset(self):
-        check(self._L.sfe_dsp_psd_reset(self._h))
+        self._set_input_format(fmt)
 
     def process_stream(self, d_in, n_in, d_out, in_stride=None, out_stride=None, stream=None):
         """d_in / d_out: DeviceArray or raw device pointers; n_in samples per stream (a multiple of hop).  Row j of
         stream s that the call completes goes to d_out + s*out_stride + j*n_fft floats; out_stride defaults to the rows
         n_in samples can complete at the most.  Returns the number of rows written per stream."""
-        pi = d_in.ptr if isinstance(d_in, DeviceArray) else int(d_in)
-        po = d_out.ptr if isinstance(d_out, DeviceArray) else int(d_out)
-        n_rows = C.c_size_t(0)
         most = -(-(int(n_in) // self.hop) // self.n_avg) * self.n_fft
-        check(self._L.sfe_dsp_psd_process_stream(self._h, pi, int(n_in), int(n_in) if in_stride is None else int(in_stride),
-                                                 po, most if out_stride is None else int(out_stride), C.byref(n_rows), stream))
-        return n_rows.value
+        return self._process_stream(d_in, n_in, in_stride, d_out, most if out_stride is None else out_stride, stream)
 
     def spectrum(self, x):
         """Host convenience, computed on the GPU: x is (n_streams, n) complex64 -- or (n_streams, n, 2) uint8 (I,Q)
         pairs with FMT_U8 -- (one dimension less for one stream), n a multiple of hop; returns the rows the call
         completes, (n_streams, rows, n_fft) float32."""
-        if self.in_u8:
-            b = np.ascontiguousarray(x, dtype=np.uint8).reshape(self.n_streams, -1)
-            n = b.shape[1] // 2
-            d_in = DeviceArray.from_bytes(b)
-        else:
-            z = np.ascontiguousarray(x, dtype=np.complex64).reshape(self.n_streams, -1)
-            n = z.shape[1]
-            d_in = DeviceArray.from_numpy(z.view(np.float32))
+        d_in, n = self._upload_input(x)
         stride = -(-(n // self.hop) // self.n_avg) * self.n_fft
         d_out = DeviceArray(max(1, self.n_streams * stride))
         try:
@@ -706,13 +666,6 @@ class Psd:
             d_out.free()
         return np.ascontiguousarray(y)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.sfe_dsp_psd_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
 
 def corr_plan(length, n_templates, block):
     """sfe_dsp_corr_plan (host only, no GPU): (transform advance V, samples of history carried per stream = 4096 - V)."""
@@ -721,29 +674,22 @@ def corr_plan(length, n_templates, block):
     return v.value, h.value
 
 
-class Corr:
+class Corr(_Block):
     """Streaming preamble correlator bank (sfe_dsp_corr_*): the squared normalised correlation of K complex templates
     (n_templates, len) against n_streams complex streams, reduced to (peak value, first peak offset) per block of
     `block` samples."""
+    _prefix = "corr"
 
     def __init__(self, templates, block, min_energy=0.0, n_streams=1, device=0):
-        self._L = _l.load()
         t = np.atleast_2d(np.ascontiguousarray(templates, dtype=np.complex64))
         self.n_templates, self.len = int(t.shape[0]), int(t.shape[1])
         self.block, self.n_streams = int(block), int(n_streams)
         self.in_u8 = False
-        h = C.c_void_p()
-        check(self._L.sfe_dsp_corr_create(t.view(np.float32).ctypes.data, self.len, self.n_templates, self.block, float(min_energy),
-                                          self.n_streams, device, C.byref(h)))
-        self._h = h.value
+        self._create(t.view(np.float32).ctypes.data, self.len, self.n_templates, self.block, float(min_energy), self.n_streams, device)
 
     def set_input_format(self, fmt):
         """lib.FMT_F32 (cf32) or lib.FMT_U8 ((I,Q) byte pairs, converted on load)."""
-        check(self._L.sfe_dsp_corr_set_input_format(self._h, fmt))
-        self.in_u8 = fmt == _l.FMT_U8
-
-    def reset(self):
-        check(self._L.sfe_dsp_corr_reset(self._h))
+        self._set_input_format(fmt)
 
     def process_stream(self, d_in, n_in, d_peak_val, d_peak_idx, d_metric=None, in_stride=None, peak_stride=None, metric_stride=None,
                        stream=None):
@@ -751,26 +697,19 @@ class Corr:
         of stream s goes to element (s*K + k)*peak_stride + j of d_peak_val (float32) and d_peak_idx (uint32), and with
         d_metric every m_k[i] to (s*K + k)*metric_stride + i; the strides default to n_in / block and n_in.  Returns the
         number of blocks."""
-        ptr = lambda d: d.ptr if isinstance(d, DeviceArray) else (None if d is None else int(d))  # noqa: E731
+        ptr = self._ptr
         n_blocks = C.c_size_t(0)
-        check(self._L.sfe_dsp_corr_process_stream(self._h, ptr(d_in), int(n_in), int(n_in) if in_stride is None else int(in_stride),
-                                                  ptr(d_peak_val), ptr(d_peak_idx),
-                                                  int(n_in) // self.block if peak_stride is None else int(peak_stride), ptr(d_metric),
-                                                  int(n_in) if metric_stride is None else int(metric_stride), C.byref(n_blocks), stream))
+        check(self._fn("process_stream")(self._h, ptr(d_in), int(n_in), int(n_in) if in_stride is None else int(in_stride),
+                                         ptr(d_peak_val), ptr(d_peak_idx),
+                                         int(n_in) // self.block if peak_stride is None else int(peak_stride), ptr(d_metric),
+                                         int(n_in) if metric_stride is None else int(metric_stride), C.byref(n_blocks), stream))
         return n_blocks.value
 
     def search(self, x, dense=False):
         """Host convenience, computed on the GPU: x is (n_streams, n) complex64 -- or (n_streams, n, 2) uint8 (I,Q)
         pairs with FMT_U8 -- (one dimension less for one stream), n a multiple of block.  Returns (peak_val float32,
         peak_idx uint32), each (n_streams, K, n / block), and with dense=True also m, (n_streams, K, n) float32."""
-        if self.in_u8:
-            b = np.ascontiguousarray(x, dtype=np.uint8).reshape(self.n_streams, -1)
-            n = b.shape[1] // 2
-            d_in = DeviceArray.from_bytes(b)
-        else:
-            z = np.ascontiguousarray(x, dtype=np.complex64).reshape(self.n_streams, -1)
-            n = z.shape[1]
-            d_in = DeviceArray.from_numpy(z.view(np.float32))
+        d_in, n = self._upload_input(x)
         rows, nb = self.n_streams * self.n_templates, n // self.block
         d_val, d_idx = DeviceArray(max(1, rows * nb)), DeviceArray(max(1, rows * nb))
         d_m = DeviceArray(max(1, rows * n)) if dense else None
@@ -789,13 +728,6 @@ class Corr:
                 d_m.free()
         return out
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.sfe_dsp_corr_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
 
 def _sos(sos):
     a = np.atleast_2d(np.ascontiguousarray(sos, dtype=np.float64))
@@ -813,38 +745,26 @@ def iir_plan(sos):
     return g.value, st.value
 
 
-class Iir:
+class Iir(_Block):
     """Streaming biquad-cascade IIR filter (sfe_dsp_iir_*): `sos` is (n_sections, 6) float64 rows (b0, b1, b2, a0, a1, a2)
     (scipy's layout; synth.iir_* design some), run over n_streams complex (or, data_complex=False, real) streams."""
+    _prefix = "iir"
 
     def __init__(self, sos, data_complex=True, n_streams=1, device=0):
-        self._L = _l.load()
         a = _sos(sos)
         self.n_sections, self.data_complex, self.n_streams = int(a.shape[0]), bool(data_complex), int(n_streams)
         self.in_u8 = False
-        h = C.c_void_p()
-        check(self._L.sfe_dsp_iir_create(a.ctypes.data_as(C.POINTER(C.c_double)), self.n_sections, int(self.data_complex), self.n_streams,
-                                         device, C.byref(h)))
-        self._h = h.value
+        self._create(a.ctypes.data_as(C.POINTER(C.c_double)), self.n_sections, int(self.data_complex), self.n_streams, device)
         self.block = iir_plan(a)[0]
 
     def set_input_format(self, fmt):
         """lib.FMT_F32 (cf32, or float32 on a real handle) or lib.FMT_U8 ((I,Q) byte pairs, converted on load)."""
-        check(self._L.sfe_dsp_iir_set_input_format(self._h, fmt))
-        self.in_u8 = fmt == _l.FMT_U8
-
-    def reset(self):
-        check(self._L.sfe_dsp_iir_reset(self._h))
+        self._set_input_format(fmt)
 
     def process_stream(self, d_in, n_in, d_out, in_stride=None, out_stride=None, stream=None):
         """d_in / d_out: DeviceArray or raw device pointers; n_in samples per stream (a multiple of self.block).  Stream s
         goes from d_in + s*in_stride to d_out + s*out_stride samples; both strides default to n_in.  Returns n_out = n_in."""
-        pi = d_in.ptr if isinstance(d_in, DeviceArray) else int(d_in)
-        po = d_out.ptr if isinstance(d_out, DeviceArray) else int(d_out)
-        n_out = C.c_size_t(0)
-        check(self._L.sfe_dsp_iir_process_stream(self._h, pi, int(n_in), int(n_in) if in_stride is None else int(in_stride),
-                                                 po, int(n_in) if out_stride is None else int(out_stride), C.byref(n_out), stream))
-        return n_out.value
+        return self._process_stream(d_in, n_in, in_stride, d_out, int(n_in) if out_stride is None else out_stride, stream)
 
     def filter(self, x):
         """Host convenience, computed on the GPU, continuing the handle's state: x is (n_streams, n) complex64 -- float32
@@ -853,22 +773,9 @@ class Iir:
         before it, but it does advance the state, so only the last piece of a stream may be ragged).  Returns x's
         samples filtered, (n_streams, n) (or (n,)) complex64 / float32."""
         G, S = self.block, self.n_streams
-        if self.in_u8:
-            b = np.ascontiguousarray(x, dtype=np.uint8).reshape(S, -1)
-            n = b.shape[1] // 2
-            one = S == 1 and np.ndim(x) <= 2                    # (n, 2) or 2n bytes
-            npad = -(-n // G) * G
-            z = np.full((S, 2 * npad), 128, np.uint8)           # byte 128 converts to 0.0
-            z[:, :2 * n] = b
-            d_in = DeviceArray.from_bytes(z)
-        else:
-            z = np.ascontiguousarray(x, dtype=np.complex64 if self.data_complex else np.float32).reshape(S, -1)
-            n = z.shape[1]
-            one = np.ndim(x) == 1
-            npad = -(-n // G) * G
-            zp = np.zeros((S, npad), z.dtype)
-            zp[:, :n] = z
-            d_in = DeviceArray.from_numpy(zp.view(np.float32))
+        one = S == 1 and np.ndim(x) <= 2 if self.in_u8 else np.ndim(x) == 1      # u8: (n, 2) or 2n bytes
+        d_in, n = self._upload_input(x, G)
+        npad = -(-n // G) * G
         w = 2 if self.data_complex else 1
         d_out = DeviceArray(max(1, S * npad * w))
         try:
@@ -880,13 +787,6 @@ class Iir:
             d_out.free()
         y = (y.view(np.complex64) if self.data_complex else y).reshape(S, npad)[:, :n]
         return np.ascontiguousarray(y[0] if one else y)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.sfe_dsp_iir_destroy(self._h)
-            self._h = None
-
-    __del__ = close
 
 
 def rs_plan(state, upsample, n_in, out_len, rate):

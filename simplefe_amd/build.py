@@ -29,7 +29,7 @@ TICKET_SOURCES = ("fir_fft.hip", "poly_fft.hip")
 # host side only (handles, plans, launch choices, device groups):
 # not part of the kernel-source hash
 HOST_SOURCES = ("api.hip", "api_plans.hip", "api_fir.hip", "api_rs.hip", "api_pipe.hip", "api_chan.hip", "api_combine.hip", "api_ddc.hip",
-                "api_psd.hip", "api_corr.hip", "api_iir.hip", "group.hip", "host.h")
+                "api_psd.hip", "api_corr.hip", "api_iir.hip", "group.hip", "host.h", "block.h")
 
 
 def sources(diag=False):
@@ -125,6 +125,10 @@ def parse_resources(text):
     return out
 
 
+# kernel files in which no instantiation may touch scratch, and what check_resources calls their kernels
+SCRATCH_FREE = {"chan.hip": "channelizer", "combine.hip": "combiner", "ddc.hip": "down-converter", "psd.hip": "spectrum-estimator",
+                "corr.hip": "correlator", "iir.hip": "IIR"}
+
 FIR_TEMPLATE_ARGS = "IN_C OUT_C IN_U8 PAIR OUT_TX10 DMA DIAG ACC WP HCH".split()
 
 
@@ -154,30 +158,11 @@ def check_resources(res):
             bad.append("%s: %s" % (k[:200], r))
         if fl and not fl["DIAG"] and r.get("Occupancy", 4) < 4:
             bad.append("%s: fewer than 4 workgroups per CU: %s" % (k[:200], r))
-    # the channelizer: every instantiation keeps its windows and accumulators in registers
-    for k, r in res.get("chan.hip", {}).items():
-        if r.get("ScratchSize", 0) or r.get("VGPRs Spill", 0) or r.get("SGPRs Spill", 0):
-            bad.append("%s: channelizer kernel touches scratch: %s" % (k[:200], r))
-    # the combiner: every instantiation keeps its delay line and taps in registers
-    for k, r in res.get("combine.hip", {}).items():
-        if r.get("ScratchSize", 0) or r.get("VGPRs Spill", 0) or r.get("SGPRs Spill", 0):
-            bad.append("%s: combiner kernel touches scratch: %s" % (k[:200], r))
-    # the down-converter bank: every instantiation keeps its windows and accumulators in registers
-    for k, r in res.get("ddc.hip", {}).items():
-        if r.get("ScratchSize", 0) or r.get("VGPRs Spill", 0) or r.get("SGPRs Spill", 0):
-            bad.append("%s: down-converter kernel touches scratch: %s" % (k[:200], r))
-    # the spectrum estimator: every instantiation keeps its window, its prefetched samples and its bin sums in registers
-    for k, r in res.get("psd.hip", {}).items():
-        if r.get("ScratchSize", 0) or r.get("VGPRs Spill", 0) or r.get("SGPRs Spill", 0):
-            bad.append("%s: spectrum-estimator kernel touches scratch: %s" % (k[:200], r))
-    # the correlator bank: samples, spectrum, window energies and correlation values stay in registers
-    for k, r in res.get("corr.hip", {}).items():
-        if r.get("ScratchSize", 0) or r.get("VGPRs Spill", 0) or r.get("SGPRs Spill", 0):
-            bad.append("%s: correlator kernel touches scratch: %s" % (k[:200], r))
-    # the IIR filter: a thread's run of samples, the section's scan and the fold's matrix row stay in registers
-    for k, r in res.get("iir.hip", {}).items():
-        if r.get("ScratchSize", 0) or r.get("VGPRs Spill", 0) or r.get("SGPRs Spill", 0):
-            bad.append("%s: IIR kernel touches scratch: %s" % (k[:200], r))
+    # the streaming blocks: every instantiation keeps its windows, samples, taps and sums in registers
+    for name, noun in SCRATCH_FREE.items():
+        for k, r in res.get(name, {}).items():
+            if r.get("ScratchSize", 0) or r.get("VGPRs Spill", 0) or r.get("SGPRs Spill", 0):
+                bad.append("%s: %s kernel touches scratch: %s" % (k[:200], noun, r))
     if bad:
         raise RuntimeError("FIR kernels of the default path and the channelizer, combiner, down-converter, spectrum-estimator, correlator and IIR kernels "
                            "must not touch scratch; "

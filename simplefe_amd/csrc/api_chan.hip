@@ -1,6 +1,7 @@
 // api_chan.hip -- the channelizer handle behind sfe_chan_t, sfe_dsp_chan_* (include/sfe_dsp.h).  Host code only; the
 // kernels are in chan.hip.
 #include "host.h"
+#include "block.h"
 
 namespace sfe {
 
@@ -15,36 +16,17 @@ namespace {
 constexpr int CHAN_RU = 8;      // tap rows per chunk of the kernel (chan.hip): P is padded to a multiple of it
 
 struct Chan {
-    uint32_t magic = 0x43484e31u;   // 'CHN1'
+    static constexpr uint32_t MAGIC = 0x43484e31u;   // 'CHN1'
+    uint32_t magic = MAGIC;
     int M = 0, logm = 0, D = 0, n_taps = 0, P = 0, Ppad = 0, H = 0, n_streams = 1, device = 0, in_u8 = 0;
-    float *d_taps = nullptr;        // [Ppad][M]: h zero-padded
-    v2f *d_tw = nullptr;            // [M]: exp(+j 2 pi q / M)
-    v2f *d_hist[2] = {nullptr, nullptr};   // [n_streams][H] each: the current history and the next call's
-    int cur = 0;
+    DevBuf<float> d_taps;           // [Ppad][M]: h zero-padded
+    DevBuf<v2f> d_tw;               // [M]: exp(+j 2 pi q / M)
+    CarriedPair hist;               // [n_streams][H] cf32 each
     unsigned long long m_count = 0; // outputs per channel since create / reset
     size_t hist_bytes() const { return (size_t)n_streams * H * sizeof(v2f); }
 };
 
-Chan *as_chan(void *h)
-{
-    Chan *c = static_cast<Chan *>(h);
-    if (c && c->magic != 0x43484e31u) {
-        set_error("not a live channelizer handle");
-        return nullptr;
-    }
-    return c;
-}
-
-void chan_free(Chan *c)
-{
-    if (!c) return;
-    if (c->d_taps) (void)hipFree(c->d_taps);
-    if (c->d_tw) (void)hipFree(c->d_tw);
-    for (auto *p : c->d_hist)
-        if (p) (void)hipFree(p);
-    c->magic = 0;
-    delete c;
-}
+Chan *as_chan(void *h) { return as_handle<Chan>(h, "channelizer"); }
 
 int chan_check_shape(int n_taps, int M, int D, int *logm)
 {
@@ -94,12 +76,9 @@ int sfe_dsp_chan_create(const float *taps, int n_taps, int n_chans, int decim, i
         set_error("chan_create: need taps and n_streams >= 1");
         return SFE_EINVAL;
     }
-    int prev_dev = -1;
-    (void)hipGetDevice(&prev_dev);
-    rc = use_device(device);
-    if (rc != SFE_OK) return rc;
-    struct Restore { int d; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore__{prev_dev};
-    Chan *c = new (std::nothrow) Chan;
+    CreateScope scope(device);
+    if (scope.rc != SFE_OK) return scope.rc;
+    std::unique_ptr<Chan> c(new (std::nothrow) Chan);
     if (!c) return SFE_ENOMEM;
     c->M = n_chans;
     c->logm = logm;
@@ -110,30 +89,13 @@ int sfe_dsp_chan_create(const float *taps, int n_taps, int n_chans, int decim, i
     c->H = c->Ppad * n_chans;
     c->n_streams = n_streams;
     c->device = device;
-    auto fail = [&](int code) { chan_free(c); return code; };
-#define TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail(hip_fail(e__, #call)); } while (0)
     std::vector<float> hp((size_t)c->Ppad * n_chans, 0.0f);
     std::copy(taps, taps + n_taps, hp.begin());
-    std::vector<v2f> tw(n_chans);
-    for (int q = 0; q < n_chans; q++) {
-        const double a = 2.0 * M_PI * q / n_chans;
-        tw[q] = v2f{(float)cos(a), (float)sin(a)};
-        if (q % (n_chans / 4) == 0) {       // the quarter turns exactly
-            static const float cq[4] = {1.0f, 0.0f, -1.0f, 0.0f}, sq[4] = {0.0f, 1.0f, 0.0f, -1.0f};
-            tw[q] = v2f{cq[q / (n_chans / 4)], sq[q / (n_chans / 4)]};
-        }
-    }
-    TRY(hipMalloc(&c->d_taps, hp.size() * sizeof(float)));
-    TRY(hipMemcpy(c->d_taps, hp.data(), hp.size() * sizeof(float), hipMemcpyHostToDevice));
-    TRY(hipMalloc(&c->d_tw, tw.size() * sizeof(v2f)));
-    TRY(hipMemcpy(c->d_tw, tw.data(), tw.size() * sizeof(v2f), hipMemcpyHostToDevice));
-    for (auto &p : c->d_hist) {
-        TRY(hipMalloc(&p, c->hist_bytes()));
-        TRY(hipMemset(p, 0, c->hist_bytes()));
-    }
-    TRY(hipDeviceSynchronize());
-#undef TRY
-    *out = c;
+    if ((rc = c->d_taps.upload(hp)) != SFE_OK || (rc = c->d_tw.upload(unit_circle(n_chans, +1))) != SFE_OK ||
+        (rc = c->hist.alloc_zero(c->hist_bytes())) != SFE_OK)
+        return rc;
+    SFE_HIP(hipDeviceSynchronize());
+    *out = c.release();
     return SFE_OK;
 }
 
@@ -151,22 +113,17 @@ int sfe_dsp_chan_set_input_format(sfe_chan_t h, int fmt)
 int sfe_dsp_chan_process_stream(sfe_chan_t h, const void *d_in, size_t n_in, size_t in_stride, void *d_out, size_t out_stride,
                                 size_t *n_out, sfe_stream_t stream)
 {
-    Chan *c = as_chan(h);
-    if (n_out) *n_out = 0;
-    if (!c || !n_out) {
-        set_error("chan_process_stream: null handle or n_out");
-        return SFE_EINVAL;
-    }
+    static const char who[] = "chan_process_stream";
+    Chan *c = stream_handle(as_chan(h), who, n_out);
+    if (!c) return SFE_EINVAL;
     if (n_in % (size_t)c->D) {
         set_error("chan_process_stream: n_in = %zu is not a multiple of decim = %d", n_in, c->D);
         return SFE_EINVAL;
     }
     const size_t no = n_in / c->D;
     if (n_in == 0) return SFE_OK;
-    if (!d_in || !d_out) {
-        set_error("chan_process_stream: null buffer");
-        return SFE_EINVAL;
-    }
+    int rc = refuse_null(who, {d_in, d_out});
+    if (rc != SFE_OK) return rc;
     if (out_stride < no) {
         set_error("chan_process_stream: out_stride %zu < n_out %zu", out_stride, no);
         return SFE_ERANGE;
@@ -176,28 +133,19 @@ int sfe_dsp_chan_process_stream(sfe_chan_t h, const void *d_in, size_t n_in, siz
         return SFE_EINVAL;
     }
     const size_t isz = c->in_u8 ? 2 : 8;
-    if ((reinterpret_cast<uintptr_t>(d_in) & (isz - 1)) || (reinterpret_cast<uintptr_t>(d_out) & 7)) {
-        set_error("chan_process_stream: buffers must be aligned to their element (cf32 8 B, u8 (I,Q) pairs 2 B)");
-        return SFE_EINVAL;
-    }
     const size_t in_b = ((size_t)(c->n_streams - 1) * in_stride + n_in) * isz;
     const size_t out_b = ((size_t)c->n_streams * c->M - 1) * out_stride * sizeof(v2f) + no * sizeof(v2f);
-    if (ranges_overlap(d_in, in_b, d_out, out_b)) {
-        set_error("chan_process_stream: input and output ranges overlap (in-place operation is not supported)");
-        return SFE_EINVAL;
-    }
+    const Span in{d_in, in_b, isz}, out{d_out, out_b, sizeof(v2f)};
     hipStream_t s = (hipStream_t)stream;
-    if (stream_is_capturing(s)) {
-        // the output counter (the D = M/2 parity) and the history buffer pair advance on the host
-        set_error("chan_process_stream: graph capture is not supported (the output counter lives on the host)");
-        return SFE_ESTATE;
-    }
+    if ((rc = refuse_misaligned(who, "cf32 8 B, u8 (I,Q) pairs 2 B", {in, out})) != SFE_OK || (rc = refuse_overlap(who, in, {out})) != SFE_OK ||
+        (rc = refuse_capture(who, "output", s)) != SFE_OK)     // the counter: the D = M/2 parity
+        return rc;
     SFE_ON_DEVICE(c->device);
-    const int rc = launch_chan(c->logm, c->D != c->M, c->in_u8, d_in, (long long)in_stride, c->d_hist[c->cur], c->d_hist[c->cur ^ 1],
-                               c->d_taps, c->d_tw, static_cast<v2f *>(d_out), (long long)out_stride, (long long)n_in, (long long)no,
-                               c->Ppad, c->H, (int)(c->m_count & 1), c->n_streams, s);
+    rc = launch_chan(c->logm, c->D != c->M, c->in_u8, d_in, (long long)in_stride, c->hist.cur<v2f>(), c->hist.next<v2f>(), c->d_taps,
+                     c->d_tw, static_cast<v2f *>(d_out), (long long)out_stride, (long long)n_in, (long long)no, c->Ppad, c->H,
+                     (int)(c->m_count & 1), c->n_streams, s);
     if (rc != SFE_OK) return rc;
-    c->cur ^= 1;
+    c->hist.flip();
     c->m_count += no;
     *n_out = no;
     return SFE_OK;
@@ -207,23 +155,11 @@ int sfe_dsp_chan_reset(sfe_chan_t h)
 {
     Chan *c = as_chan(h);
     if (!c) return SFE_EINVAL;
-    SFE_ON_DEVICE(c->device);
-    SFE_HIP(hipDeviceSynchronize());
-    for (auto *p : c->d_hist) SFE_HIP(hipMemset(p, 0, c->hist_bytes()));
-    SFE_HIP(hipDeviceSynchronize());
-    c->cur = 0;
-    c->m_count = 0;
-    return SFE_OK;
+    const int rc = reset_pairs(c->device, {&c->hist});
+    if (rc == SFE_OK) c->m_count = 0;
+    return rc;
 }
 
-int sfe_dsp_chan_destroy(sfe_chan_t h)
-{
-    Chan *c = as_chan(h);
-    if (!c) return SFE_OK;
-    DeviceGuard g(c->device);
-    (void)hipDeviceSynchronize();
-    chan_free(c);
-    return SFE_OK;
-}
+int sfe_dsp_chan_destroy(sfe_chan_t h) { return destroy_handle(as_chan(h)); }
 
 }  // extern "C"

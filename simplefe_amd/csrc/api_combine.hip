@@ -1,6 +1,7 @@
 // api_combine.hip -- the synthesis filter bank handle behind sfe_combine_t, sfe_dsp_combine_* (include/sfe_dsp.h).  Host
 // code only; the kernels are in combine.hip.
 #include "host.h"
+#include "block.h"
 
 namespace sfe {
 
@@ -13,39 +14,18 @@ int launch_combine(int logm, int half, int logj, int tx10, const v2f *in, long l
 
 namespace {
 
-constexpr uint32_t COMBINE_MAGIC = 0x434d4231u;   // 'CMB1'
-
 struct Combiner {
-    uint32_t magic = COMBINE_MAGIC;
+    static constexpr uint32_t MAGIC = 0x434d4231u;   // 'CMB1'
+    uint32_t magic = MAGIC;
     int M = 0, logm = 0, D = 0, n_taps = 0, P = 0, logj = 0, Hr = 0, n_streams = 1, device = 0, out_tx10 = 0;
-    float *d_taps = nullptr;        // [J][D]: g zero-padded
-    v2f *d_tw = nullptr;            // [M]: exp(+j 2 pi q / M)
-    v2f *d_hist[2] = {nullptr, nullptr};   // [n_streams][M][Hr] each: the current history and the next call's
-    int cur = 0;
+    DevBuf<float> d_taps;           // [J][D]: g zero-padded
+    DevBuf<v2f> d_tw;               // [M]: exp(+j 2 pi q / M)
+    CarriedPair hist;               // [n_streams][M][Hr] cf32 each
     unsigned long long m_count = 0; // instants since create / reset
     size_t hist_bytes() const { return (size_t)n_streams * M * Hr * sizeof(v2f); }
 };
 
-Combiner *as_combiner(void *h)
-{
-    Combiner *c = static_cast<Combiner *>(h);
-    if (c && c->magic != COMBINE_MAGIC) {
-        set_error("not a live combiner handle");
-        return nullptr;
-    }
-    return c;
-}
-
-void combiner_free(Combiner *c)
-{
-    if (!c) return;
-    if (c->d_taps) (void)hipFree(c->d_taps);
-    if (c->d_tw) (void)hipFree(c->d_tw);
-    for (auto *p : c->d_hist)
-        if (p) (void)hipFree(p);
-    c->magic = 0;
-    delete c;
-}
+Combiner *as_combiner(void *h) { return as_handle<Combiner>(h, "combiner"); }
 
 // P = ceil(L / D) taps per output phase; the kernel's delay line is J = the power of two >= max(8, P) long
 int combine_check_shape(int n_taps, int M, int D, int *logm, int *P, int *logj)
@@ -101,12 +81,9 @@ int sfe_dsp_combine_create(const float *taps, int n_taps, int n_chans, int inter
         set_error("combine_create: need taps and n_streams >= 1");
         return SFE_EINVAL;
     }
-    int prev_dev = -1;
-    (void)hipGetDevice(&prev_dev);
-    rc = use_device(device);
-    if (rc != SFE_OK) return rc;
-    struct Restore { int d; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore__{prev_dev};
-    Combiner *c = new (std::nothrow) Combiner;
+    CreateScope scope(device);
+    if (scope.rc != SFE_OK) return scope.rc;
+    std::unique_ptr<Combiner> c(new (std::nothrow) Combiner);
     if (!c) return SFE_ENOMEM;
     c->M = n_chans;
     c->logm = logm;
@@ -117,30 +94,13 @@ int sfe_dsp_combine_create(const float *taps, int n_taps, int n_chans, int inter
     c->Hr = (1 << logj) - 1;
     c->n_streams = n_streams;
     c->device = device;
-    auto fail = [&](int code) { combiner_free(c); return code; };
-#define TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail(hip_fail(e__, #call)); } while (0)
     std::vector<float> gp((size_t)interp << logj, 0.0f);
     std::copy(taps, taps + n_taps, gp.begin());
-    std::vector<v2f> tw(n_chans);
-    for (int q = 0; q < n_chans; q++) {
-        const double a = 2.0 * M_PI * q / n_chans;
-        tw[q] = v2f{(float)cos(a), (float)sin(a)};
-        if (q % (n_chans / 4) == 0) {       // the quarter turns exactly
-            static const float cq[4] = {1.0f, 0.0f, -1.0f, 0.0f}, sq[4] = {0.0f, 1.0f, 0.0f, -1.0f};
-            tw[q] = v2f{cq[q / (n_chans / 4)], sq[q / (n_chans / 4)]};
-        }
-    }
-    TRY(hipMalloc(&c->d_taps, gp.size() * sizeof(float)));
-    TRY(hipMemcpy(c->d_taps, gp.data(), gp.size() * sizeof(float), hipMemcpyHostToDevice));
-    TRY(hipMalloc(&c->d_tw, tw.size() * sizeof(v2f)));
-    TRY(hipMemcpy(c->d_tw, tw.data(), tw.size() * sizeof(v2f), hipMemcpyHostToDevice));
-    for (auto &p : c->d_hist) {
-        TRY(hipMalloc(&p, c->hist_bytes()));
-        TRY(hipMemset(p, 0, c->hist_bytes()));
-    }
-    TRY(hipDeviceSynchronize());
-#undef TRY
-    *out = c;
+    if ((rc = c->d_taps.upload(gp)) != SFE_OK || (rc = c->d_tw.upload(unit_circle(n_chans, +1))) != SFE_OK ||
+        (rc = c->hist.alloc_zero(c->hist_bytes())) != SFE_OK)
+        return rc;
+    SFE_HIP(hipDeviceSynchronize());
+    *out = c.release();
     return SFE_OK;
 }
 
@@ -158,18 +118,13 @@ int sfe_dsp_combine_set_output_format(sfe_combine_t h, int fmt)
 int sfe_dsp_combine_process_stream(sfe_combine_t h, const void *d_in, size_t n_in, size_t in_stride, void *d_out, size_t out_stride,
                                    size_t *n_out, sfe_stream_t stream)
 {
-    Combiner *c = as_combiner(h);
-    if (n_out) *n_out = 0;
-    if (!c || !n_out) {
-        set_error("combine_process_stream: null handle or n_out");
-        return SFE_EINVAL;
-    }
+    static const char who[] = "combine_process_stream";
+    Combiner *c = stream_handle(as_combiner(h), who, n_out);
+    if (!c) return SFE_EINVAL;
     if (n_in == 0) return SFE_OK;
     const size_t no = n_in * (size_t)c->D;
-    if (!d_in || !d_out) {
-        set_error("combine_process_stream: null buffer");
-        return SFE_EINVAL;
-    }
+    int rc = refuse_null(who, {d_in, d_out});
+    if (rc != SFE_OK) return rc;
     if (out_stride < no) {
         set_error("combine_process_stream: out_stride %zu < n_out %zu", out_stride, no);
         return SFE_ERANGE;
@@ -182,28 +137,20 @@ int sfe_dsp_combine_process_stream(sfe_combine_t h, const void *d_in, size_t n_i
         set_error("combine_process_stream: out_stride %zu must be even with SFE_FMT_TX10 (whole 5-byte groups per stream)", out_stride);
         return SFE_EINVAL;
     }
-    if ((reinterpret_cast<uintptr_t>(d_in) & 7) || (!c->out_tx10 && (reinterpret_cast<uintptr_t>(d_out) & 7))) {
-        set_error("combine_process_stream: cf32 buffers must be 8-byte aligned");
-        return SFE_EINVAL;
-    }
+    const size_t in_b = ((size_t)c->n_streams * c->M - 1) * in_stride * sizeof(v2f) + n_in * sizeof(v2f);
+    const size_t out_b = c->out_tx10 ? ((size_t)(c->n_streams - 1) * (out_stride / 2) + no / 2) * 5
+                                     : ((size_t)(c->n_streams - 1) * out_stride + no) * sizeof(v2f);
+    const Span in{d_in, in_b, sizeof(v2f)}, out{d_out, out_b, c->out_tx10 ? 1 : sizeof(v2f)};
+    rc = refuse_misaligned(who, "cf32 8 B", {in, out});
+    if (rc != SFE_OK) return rc;
     // the kernel indexes within one stream in 32 bits
     if ((size_t)(c->M - 1) * in_stride + n_in >= (1ull << 31) || no >= (1ull << 31)) {
         set_error("combine_process_stream: a stream's input (%d x %zu) or output (%zu) reaches 2^31 samples", c->M, in_stride, no);
         return SFE_EINVAL;
     }
-    const size_t in_b = ((size_t)c->n_streams * c->M - 1) * in_stride * sizeof(v2f) + n_in * sizeof(v2f);
-    const size_t out_b = c->out_tx10 ? ((size_t)(c->n_streams - 1) * (out_stride / 2) + no / 2) * 5
-                                     : ((size_t)(c->n_streams - 1) * out_stride + no) * sizeof(v2f);
-    if (ranges_overlap(d_in, in_b, d_out, out_b)) {
-        set_error("combine_process_stream: input and output ranges overlap (in-place operation is not supported)");
-        return SFE_EINVAL;
-    }
     hipStream_t s = (hipStream_t)stream;
-    if (stream_is_capturing(s)) {
-        // the instant counter (the D = M/2 parity) and the history buffer pair advance on the host
-        set_error("combine_process_stream: graph capture is not supported (the instant counter lives on the host)");
-        return SFE_ESTATE;
-    }
+    if ((rc = refuse_overlap(who, in, {out})) != SFE_OK || (rc = refuse_capture(who, "instant", s)) != SFE_OK)   // the D = M/2 parity
+        return rc;
     SFE_ON_DEVICE(c->device);
     // instants per segment: whole chunks, long enough that the J - 1 warm-up rows stay a small part of the work, and
     // short enough to give every compute unit several workgroups
@@ -214,11 +161,11 @@ int sfe_dsp_combine_process_stream(sfe_combine_t h, const void *d_in, size_t n_i
     run = std::max(run, 4LL * (1 << c->logj));
     run = std::min(run, (long long)n_in);
     run = (run + rg - 1) / rg * rg;
-    const int rc = launch_combine(c->logm, c->D != c->M, c->logj, c->out_tx10, static_cast<const v2f *>(d_in), (long long)in_stride,
-                                  c->d_hist[c->cur], c->d_hist[c->cur ^ 1], c->d_taps, c->d_tw, d_out, (long long)out_stride,
-                                  (long long)n_in, run, c->Hr, (int)(c->m_count & 1), c->n_streams, s);
+    rc = launch_combine(c->logm, c->D != c->M, c->logj, c->out_tx10, static_cast<const v2f *>(d_in), (long long)in_stride,
+                        c->hist.cur<v2f>(), c->hist.next<v2f>(), c->d_taps, c->d_tw, d_out, (long long)out_stride, (long long)n_in, run,
+                        c->Hr, (int)(c->m_count & 1), c->n_streams, s);
     if (rc != SFE_OK) return rc;
-    c->cur ^= 1;
+    c->hist.flip();
     c->m_count += n_in;
     *n_out = no;
     return SFE_OK;
@@ -228,23 +175,11 @@ int sfe_dsp_combine_reset(sfe_combine_t h)
 {
     Combiner *c = as_combiner(h);
     if (!c) return SFE_EINVAL;
-    SFE_ON_DEVICE(c->device);
-    SFE_HIP(hipDeviceSynchronize());
-    for (auto *p : c->d_hist) SFE_HIP(hipMemset(p, 0, c->hist_bytes()));
-    SFE_HIP(hipDeviceSynchronize());
-    c->cur = 0;
-    c->m_count = 0;
-    return SFE_OK;
+    const int rc = reset_pairs(c->device, {&c->hist});
+    if (rc == SFE_OK) c->m_count = 0;
+    return rc;
 }
 
-int sfe_dsp_combine_destroy(sfe_combine_t h)
-{
-    Combiner *c = as_combiner(h);
-    if (!c) return SFE_OK;
-    DeviceGuard g(c->device);
-    (void)hipDeviceSynchronize();
-    combiner_free(c);
-    return SFE_OK;
-}
+int sfe_dsp_combine_destroy(sfe_combine_t h) { return destroy_handle(as_combiner(h)); }
 
 }  // extern "C"

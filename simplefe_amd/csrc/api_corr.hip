@@ -4,6 +4,7 @@
 #include <complex>
 
 #include "host.h"
+#include "block.h"
 
 namespace sfe {
 
@@ -18,44 +19,21 @@ namespace {
 constexpr int CORR_FFT = 4096;
 
 struct Corr {
-    uint32_t magic = 0x434f5231u;   // 'COR1'
+    static constexpr uint32_t MAGIC = 0x434f5231u;   // 'COR1'
+    uint32_t magic = MAGIC;
     int L = 0, K = 0, V = 0, ov = 0, B = 0, n_streams = 1, device = 0, in_u8 = 0;
     float min_energy = 0.0f;
-    v2f *d_spec = nullptr;          // [K][4096]: conj(DFT of conj(s_k) reversed) / 4096
-    v2f *d_tpl = nullptr;           // [K][L]: the templates themselves (the time-domain form of short templates)
-    v2f *d_tw = nullptr;            // [4096]: exp(-j 2 pi q / 4096)
-    float *d_energy = nullptr;      // [K]: E_k
-    v2f *d_hist[2] = {nullptr, nullptr};    // the ov samples before the next call, per stream: the current one and the next call's
-    int cur = 0;
-    void *d_part = nullptr;         // the slot peaks of one call (B > V): values, then indices; grows with the largest call seen
-    size_t part_slots = 0;
+    DevBuf<v2f> d_spec;             // [K][4096]: conj(DFT of conj(s_k) reversed) / 4096
+    DevBuf<v2f> d_tpl;              // [K][L]: the templates themselves (the time-domain form of short templates)
+    DevBuf<v2f> d_tw;               // [4096]: exp(-j 2 pi q / 4096)
+    DevBuf<float> d_energy;         // [K]: E_k
+    CarriedPair hist;               // the ov samples (cf32) before the next call, per stream
+    GrowScratch part;               // the slot peaks of one call (B > V): values (float), then indices (unsigned)
     unsigned long long samples = 0; // per stream since create / reset
     size_t hist_bytes() const { return std::max<size_t>((size_t)n_streams * ov, 1) * sizeof(v2f); }
 };
 
-Corr *as_corr(void *h)
-{
-    Corr *p = static_cast<Corr *>(h);
-    if (p && p->magic != 0x434f5231u) {
-        set_error("not a live correlator handle");
-        return nullptr;
-    }
-    return p;
-}
-
-void corr_free(Corr *p)
-{
-    if (!p) return;
-    if (p->d_spec) (void)hipFree(p->d_spec);
-    if (p->d_tpl) (void)hipFree(p->d_tpl);
-    if (p->d_tw) (void)hipFree(p->d_tw);
-    if (p->d_energy) (void)hipFree(p->d_energy);
-    if (p->d_part) (void)hipFree(p->d_part);
-    for (int i = 0; i < 2; i++)
-        if (p->d_hist[i]) (void)hipFree(p->d_hist[i]);
-    p->magic = 0;
-    delete p;
-}
+Corr *as_corr(void *h) { return as_handle<Corr>(h, "correlator"); }
 
 int corr_check_shape(int L, int K, int B, int *advance)
 {
@@ -142,12 +120,9 @@ int sfe_dsp_corr_create(const float *templates, int len, int n_templates, int bl
             return SFE_EINVAL;
         }
     }
-    int prev_dev = -1;
-    (void)hipGetDevice(&prev_dev);
-    rc = use_device(device);
-    if (rc != SFE_OK) return rc;
-    struct Restore { int d; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore__{prev_dev};
-    Corr *p = new (std::nothrow) Corr;
+    CreateScope scope(device);
+    if (scope.rc != SFE_OK) return scope.rc;
+    std::unique_ptr<Corr> p(new (std::nothrow) Corr);
     if (!p) return SFE_ENOMEM;
     p->L = len;
     p->K = n_templates;
@@ -157,8 +132,6 @@ int sfe_dsp_corr_create(const float *templates, int len, int n_templates, int bl
     p->min_energy = min_energy;
     p->n_streams = n_streams;
     p->device = device;
-    auto fail = [&](int code) { corr_free(p); return code; };
-#define TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail(hip_fail(e__, #call)); } while (0)
     // c_k = x convolved with h_k[n] = conj(s_k[L-1-n]); the kernel runs the inverse transform as a forward one of the
     // conjugated product, so it is handed conj(DFT h_k) / 4096
     std::vector<v2f> spec((size_t)n_templates * CORR_FFT);
@@ -171,30 +144,13 @@ int sfe_dsp_corr_create(const float *templates, int len, int n_templates, int bl
         for (int j = 0; j < CORR_FFT; j++)
             spec[(size_t)k * CORR_FFT + j] = v2f{(float)(h[j].real() / CORR_FFT), (float)(-h[j].imag() / CORR_FFT)};
     }
-    std::vector<v2f> tw(CORR_FFT);
-    for (int q = 0; q < CORR_FFT; q++) {
-        const double a = 2.0 * M_PI * q / CORR_FFT;
-        tw[q] = v2f{(float)cos(a), (float)-sin(a)};
-        if (q % (CORR_FFT / 4) == 0) {      // the quarter turns exactly
-            static const float cq[4] = {1.0f, 0.0f, -1.0f, 0.0f}, sq[4] = {0.0f, -1.0f, 0.0f, 1.0f};
-            tw[q] = v2f{cq[q / (CORR_FFT / 4)], sq[q / (CORR_FFT / 4)]};
-        }
-    }
-    TRY(hipMalloc(&p->d_spec, spec.size() * sizeof(v2f)));
-    TRY(hipMemcpy(p->d_spec, spec.data(), spec.size() * sizeof(v2f), hipMemcpyHostToDevice));
-    TRY(hipMalloc(&p->d_tpl, (size_t)n_templates * len * sizeof(v2f)));
-    TRY(hipMemcpy(p->d_tpl, templates, (size_t)n_templates * len * sizeof(v2f), hipMemcpyHostToDevice));
-    TRY(hipMalloc(&p->d_tw, tw.size() * sizeof(v2f)));
-    TRY(hipMemcpy(p->d_tw, tw.data(), tw.size() * sizeof(v2f), hipMemcpyHostToDevice));
-    TRY(hipMalloc(&p->d_energy, energy.size() * sizeof(float)));
-    TRY(hipMemcpy(p->d_energy, energy.data(), energy.size() * sizeof(float), hipMemcpyHostToDevice));
-    for (int i = 0; i < 2; i++) {
-        TRY(hipMalloc(&p->d_hist[i], p->hist_bytes()));
-        TRY(hipMemset(p->d_hist[i], 0, p->hist_bytes()));
-    }
-    TRY(hipDeviceSynchronize());
-#undef TRY
-    *out = p;
+    if ((rc = p->d_spec.upload(spec)) != SFE_OK ||
+        (rc = p->d_tpl.upload(reinterpret_cast<const v2f *>(templates), (size_t)n_templates * len)) != SFE_OK ||
+        (rc = p->d_tw.upload(unit_circle(CORR_FFT, -1))) != SFE_OK || (rc = p->d_energy.upload(energy)) != SFE_OK ||
+        (rc = p->hist.alloc_zero(p->hist_bytes())) != SFE_OK)
+        return rc;
+    SFE_HIP(hipDeviceSynchronize());
+    *out = p.release();
     return SFE_OK;
 }
 
@@ -212,26 +168,19 @@ int sfe_dsp_corr_set_input_format(sfe_corr_t h, int fmt)
 int sfe_dsp_corr_process_stream(sfe_corr_t h, const void *d_in, size_t n_in, size_t in_stride, void *d_peak_val, void *d_peak_idx,
                                 size_t peak_stride, void *d_metric, size_t metric_stride, size_t *n_blocks, sfe_stream_t stream)
 {
-    Corr *p = as_corr(h);
-    if (n_blocks) *n_blocks = 0;
-    if (!p || !n_blocks) {
-        set_error("corr_process_stream: null handle or n_blocks");
-        return SFE_EINVAL;
-    }
+    static const char who[] = "corr_process_stream";
+    Corr *p = stream_handle(as_corr(h), who, n_blocks, "n_blocks");
+    if (!p) return SFE_EINVAL;
     if (n_in % (size_t)p->B) {
         set_error("corr_process_stream: n_in = %zu is not a multiple of block = %d", n_in, p->B);
         return SFE_EINVAL;
     }
-    if (n_in >= ((size_t)1 << 31)) {
-        set_error("corr_process_stream: n_in = %zu must be below 2^31", n_in);
-        return SFE_EINVAL;
-    }
+    int rc = refuse_2_31(who, n_in);
+    if (rc != SFE_OK) return rc;
     if (n_in == 0) return SFE_OK;
     const size_t blocks = n_in / p->B, rows = (size_t)p->n_streams * p->K;
-    if (!d_in || !d_peak_val || !d_peak_idx) {
-        set_error("corr_process_stream: null buffer");
-        return SFE_EINVAL;
-    }
+    rc = refuse_null(who, {d_in, d_peak_val, d_peak_idx});
+    if (rc != SFE_OK) return rc;
     if (peak_stride < blocks) {
         set_error("corr_process_stream: peak_stride %zu < n_blocks = %zu", peak_stride, blocks);
         return SFE_ERANGE;
@@ -245,50 +194,34 @@ int sfe_dsp_corr_process_stream(sfe_corr_t h, const void *d_in, size_t n_in, siz
         return SFE_EINVAL;
     }
     const size_t isz = p->in_u8 ? 2 : 8;
-    if ((reinterpret_cast<uintptr_t>(d_in) & (isz - 1)) || (reinterpret_cast<uintptr_t>(d_peak_val) & 3) ||
-        (reinterpret_cast<uintptr_t>(d_peak_idx) & 3) || (reinterpret_cast<uintptr_t>(d_metric) & 3)) {
-        set_error("corr_process_stream: buffers must be aligned to their element (cf32 8 B, u8 (I,Q) pairs 2 B, outputs 4 B)");
-        return SFE_EINVAL;
-    }
     const size_t in_b = ((size_t)(p->n_streams - 1) * in_stride + n_in) * isz;
     const size_t peak_b = ((rows - 1) * peak_stride + blocks) * 4;
     const size_t met_b = d_metric ? ((rows - 1) * metric_stride + n_in) * 4 : 0;
-    if (ranges_overlap(d_in, in_b, d_peak_val, peak_b) || ranges_overlap(d_in, in_b, d_peak_idx, peak_b) ||
-        (met_b && ranges_overlap(d_in, in_b, d_metric, met_b))) {
-        set_error("corr_process_stream: input and output ranges overlap (in-place operation is not supported)");
-        return SFE_EINVAL;
-    }
+    const Span in{d_in, in_b, isz}, val{d_peak_val, peak_b, 4}, idx{d_peak_idx, peak_b, 4}, met{d_metric, met_b, 4};
+    if ((rc = refuse_misaligned(who, "cf32 8 B, u8 (I,Q) pairs 2 B, outputs 4 B", {in, val, idx, met})) != SFE_OK ||
+        (rc = refuse_overlap(who, in, {val, idx, met})) != SFE_OK)
+        return rc;
     if (ranges_overlap(d_peak_val, peak_b, d_peak_idx, peak_b) ||
         (met_b && (ranges_overlap(d_metric, met_b, d_peak_val, peak_b) || ranges_overlap(d_metric, met_b, d_peak_idx, peak_b)))) {
         set_error("corr_process_stream: the output ranges overlap one another");
         return SFE_EINVAL;
     }
     hipStream_t s = (hipStream_t)stream;
-    if (stream_is_capturing(s)) {
-        // the sample counter and the history pair advance on the host
-        set_error("corr_process_stream: graph capture is not supported (the sample counter lives on the host)");
-        return SFE_ESTATE;
-    }
+    rc = refuse_capture(who, "sample", s);
+    if (rc != SFE_OK) return rc;
     SFE_ON_DEVICE(p->device);
     // B > V: the table of slot peaks grows when a larger call than any before arrives; with B = V there is none
     const size_t slots = n_in / p->V, need = p->B > p->V ? rows * slots : 0;
-    if (need > p->part_slots) {
-        SFE_HIP(hipDeviceSynchronize());
-        if (p->d_part) (void)hipFree(p->d_part);
-        p->d_part = nullptr;
-        p->part_slots = 0;
-        SFE_HIP(hipMalloc(&p->d_part, need * 8));
-        p->part_slots = need;
-    }
-    const int c = p->cur;
-    float *part_val = static_cast<float *>(p->d_part);
-    unsigned *part_idx = p->d_part ? reinterpret_cast<unsigned *>(part_val + p->part_slots) : nullptr;
-    const int rc = launch_corr(p->in_u8, d_in, (long long)in_stride, p->d_hist[c], p->d_hist[c ^ 1], p->d_spec, p->d_tpl, p->d_tw, p->d_energy,
-                               static_cast<float *>(d_peak_val), static_cast<unsigned *>(d_peak_idx), (long long)peak_stride, part_val,
-                               part_idx, static_cast<float *>(d_metric), (long long)metric_stride, (long long)n_in, p->L, p->K, p->V,
-                               (long long)p->B, p->min_energy, p->n_streams, s);
+    rc = p->part.reserve(need * 8);
     if (rc != SFE_OK) return rc;
-    p->cur ^= 1;
+    float *part_val = p->part.as<float>();
+    unsigned *part_idx = part_val ? reinterpret_cast<unsigned *>(part_val + p->part.bytes / 8) : nullptr;
+    rc = launch_corr(p->in_u8, d_in, (long long)in_stride, p->hist.cur<v2f>(), p->hist.next<v2f>(), p->d_spec, p->d_tpl, p->d_tw,
+                     p->d_energy, static_cast<float *>(d_peak_val), static_cast<unsigned *>(d_peak_idx), (long long)peak_stride, part_val,
+                     part_idx, static_cast<float *>(d_metric), (long long)metric_stride, (long long)n_in, p->L, p->K, p->V,
+                     (long long)p->B, p->min_energy, p->n_streams, s);
+    if (rc != SFE_OK) return rc;
+    p->hist.flip();
     p->samples += n_in;
     *n_blocks = blocks;
     return SFE_OK;
@@ -298,23 +231,11 @@ int sfe_dsp_corr_reset(sfe_corr_t h)
 {
     Corr *p = as_corr(h);
     if (!p) return SFE_EINVAL;
-    SFE_ON_DEVICE(p->device);
-    SFE_HIP(hipDeviceSynchronize());
-    for (int i = 0; i < 2; i++) SFE_HIP(hipMemset(p->d_hist[i], 0, p->hist_bytes()));
-    SFE_HIP(hipDeviceSynchronize());
-    p->cur = 0;
-    p->samples = 0;
-    return SFE_OK;
+    const int rc = reset_pairs(p->device, {&p->hist});
+    if (rc == SFE_OK) p->samples = 0;
+    return rc;
 }
 
-int sfe_dsp_corr_destroy(sfe_corr_t h)
-{
-    Corr *p = as_corr(h);
-    if (!p) return SFE_OK;
-    DeviceGuard g(p->device);
-    (void)hipDeviceSynchronize();
-    corr_free(p);
-    return SFE_OK;
-}
+int sfe_dsp_corr_destroy(sfe_corr_t h) { return destroy_handle(as_corr(h)); }
 
 }  // extern "C"

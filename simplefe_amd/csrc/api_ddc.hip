@@ -1,6 +1,7 @@
 // api_ddc.hip -- the down-converter bank handle behind sfe_ddc_t, sfe_dsp_ddc_* (include/sfe_dsp.h).  Host code only; the
 // kernels are in ddc.hip.
 #include "host.h"
+#include "block.h"
 
 namespace sfe {
 
@@ -15,37 +16,18 @@ namespace {
 constexpr int DDC_RU = 4;       // tap rows per chunk of the kernel (ddc.hip): P is padded to a multiple of it
 
 struct Ddc {
-    uint32_t magic = 0x44444331u;   // 'DDC1'
+    static constexpr uint32_t MAGIC = 0x44444331u;   // 'DDC1'
+    uint32_t magic = MAGIC;
     int D = 0, n_taps = 0, P = 0, Ppad = 0, H = 0, K = 0, Kpad = 0, KT = 1, n_streams = 1, device = 0, complex_in = 1, in_u8 = 0;
     std::vector<float> h;           // the prototype, for the tables of set_freqs
-    v2f *d_taps = nullptr;          // [Kpad / KT][Ppad][D][KT]: g_k[n] = h[n] exp(+j 2 pi phi_k(n) / 2^32), zero-padded
-    unsigned *d_inc = nullptr;      // [Kpad]
-    void *d_hist[2] = {nullptr, nullptr};   // [n_streams][H] each (cf32, or float for real input): current and next
-    int cur = 0;
+    DevBuf<v2f> d_taps;             // [Kpad / KT][Ppad][D][KT]: g_k[n] = h[n] exp(+j 2 pi phi_k(n) / 2^32), zero-padded
+    DevBuf<uint32_t> d_inc;         // [Kpad]
+    CarriedPair hist;               // [n_streams][H] each (cf32, or float for real input)
     unsigned long long count = 0;   // input samples per stream since create / reset
     size_t hist_bytes() const { return (size_t)n_streams * H * (complex_in ? sizeof(v2f) : sizeof(float)); }
 };
 
-Ddc *as_ddc(void *h)
-{
-    Ddc *c = static_cast<Ddc *>(h);
-    if (c && c->magic != 0x44444331u) {
-        set_error("not a live down-converter handle");
-        return nullptr;
-    }
-    return c;
-}
-
-void ddc_free(Ddc *c)
-{
-    if (!c) return;
-    if (c->d_taps) (void)hipFree(c->d_taps);
-    if (c->d_inc) (void)hipFree(c->d_inc);
-    for (auto *p : c->d_hist)
-        if (p) (void)hipFree(p);
-    c->magic = 0;
-    delete c;
-}
+Ddc *as_ddc(void *h) { return as_handle<Ddc>(h, "down-converter"); }
 
 int ddc_check_freqs(int K, const double *freqs, uint32_t *inc)
 {
@@ -133,12 +115,9 @@ int sfe_dsp_ddc_create(const float *taps, int n_taps, int decim, int n_tunings, 
         set_error("ddc_create: need taps and 1 <= n_streams <= 65535");
         return SFE_EINVAL;
     }
-    int prev_dev = -1;
-    (void)hipGetDevice(&prev_dev);
-    rc = use_device(device);
-    if (rc != SFE_OK) return rc;
-    struct Restore { int d; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore__{prev_dev};
-    Ddc *c = new (std::nothrow) Ddc;
+    CreateScope scope(device);
+    if (scope.rc != SFE_OK) return scope.rc;
+    std::unique_ptr<Ddc> c(new (std::nothrow) Ddc);
     if (!c) return SFE_ENOMEM;
     c->D = decim;
     c->n_taps = n_taps;
@@ -152,21 +131,12 @@ int sfe_dsp_ddc_create(const float *taps, int n_taps, int decim, int n_tunings, 
     c->device = device;
     c->complex_in = data_complex != 0;
     c->h.assign(taps, taps + n_taps);
-    auto fail = [&](int code) { ddc_free(c); return code; };
-#define TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail(hip_fail(e__, #call)); } while (0)
-    const std::vector<v2f> t = ddc_table(c, inc.data());
+    const std::vector<v2f> t = ddc_table(c.get(), inc.data());
     inc.resize(c->Kpad, 0u);
-    TRY(hipMalloc(&c->d_taps, t.size() * sizeof(v2f)));
-    TRY(hipMemcpy(c->d_taps, t.data(), t.size() * sizeof(v2f), hipMemcpyHostToDevice));
-    TRY(hipMalloc(&c->d_inc, inc.size() * sizeof(uint32_t)));
-    TRY(hipMemcpy(c->d_inc, inc.data(), inc.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    for (auto &p : c->d_hist) {
-        TRY(hipMalloc(&p, c->hist_bytes()));
-        TRY(hipMemset(p, 0, c->hist_bytes()));
-    }
-    TRY(hipDeviceSynchronize());
-#undef TRY
-    *out = c;
+    if ((rc = c->d_taps.upload(t)) != SFE_OK || (rc = c->d_inc.upload(inc)) != SFE_OK || (rc = c->hist.alloc_zero(c->hist_bytes())) != SFE_OK)
+        return rc;
+    SFE_HIP(hipDeviceSynchronize());
+    *out = c.release();
     return SFE_OK;
 }
 
@@ -206,26 +176,19 @@ int sfe_dsp_ddc_set_freqs(sfe_ddc_t h, const double *freqs)
 int sfe_dsp_ddc_process_stream(sfe_ddc_t h, const void *d_in, size_t n_in, size_t in_stride, void *d_out, size_t out_stride,
                                size_t *n_out, sfe_stream_t stream)
 {
-    Ddc *c = as_ddc(h);
-    if (n_out) *n_out = 0;
-    if (!c || !n_out) {
-        set_error("ddc_process_stream: null handle or n_out");
-        return SFE_EINVAL;
-    }
+    static const char who[] = "ddc_process_stream";
+    Ddc *c = stream_handle(as_ddc(h), who, n_out);
+    if (!c) return SFE_EINVAL;
     if (n_in % (size_t)c->D) {
         set_error("ddc_process_stream: n_in = %zu is not a multiple of decim = %d", n_in, c->D);
         return SFE_EINVAL;
     }
-    if (n_in >= ((size_t)1 << 31)) {
-        set_error("ddc_process_stream: n_in = %zu must be below 2^31 per call", n_in);
-        return SFE_EINVAL;
-    }
+    int rc = refuse_2_31(who, n_in);
+    if (rc != SFE_OK) return rc;
     const size_t no = n_in / c->D;
     if (n_in == 0) return SFE_OK;
-    if (!d_in || !d_out) {
-        set_error("ddc_process_stream: null buffer");
-        return SFE_EINVAL;
-    }
+    rc = refuse_null(who, {d_in, d_out});
+    if (rc != SFE_OK) return rc;
     if (out_stride < no) {
         set_error("ddc_process_stream: out_stride %zu < n_out %zu", out_stride, no);
         return SFE_ERANGE;
@@ -235,29 +198,20 @@ int sfe_dsp_ddc_process_stream(sfe_ddc_t h, const void *d_in, size_t n_in, size_
         return SFE_EINVAL;
     }
     const size_t isz = c->in_u8 ? 2 : c->complex_in ? 8 : 4;
-    if ((reinterpret_cast<uintptr_t>(d_in) & (isz - 1)) || (reinterpret_cast<uintptr_t>(d_out) & 7)) {
-        set_error("ddc_process_stream: buffers must be aligned to their element (cf32 8 B, real float 4 B, u8 (I,Q) pairs 2 B)");
-        return SFE_EINVAL;
-    }
     const size_t in_b = ((size_t)(c->n_streams - 1) * in_stride + n_in) * isz;
     const size_t out_b = ((size_t)c->n_streams * c->K - 1) * out_stride * sizeof(v2f) + no * sizeof(v2f);
-    if (ranges_overlap(d_in, in_b, d_out, out_b)) {
-        set_error("ddc_process_stream: input and output ranges overlap (in-place operation is not supported)");
-        return SFE_EINVAL;
-    }
+    const Span in{d_in, in_b, isz}, out{d_out, out_b, sizeof(v2f)};
     hipStream_t s = (hipStream_t)stream;
-    if (stream_is_capturing(s)) {
-        // the sample counter (the lead factors' phase) and the history buffer pair advance on the host
-        set_error("ddc_process_stream: graph capture is not supported (the sample counter lives on the host)");
-        return SFE_ESTATE;
-    }
+    if ((rc = refuse_misaligned(who, "cf32 8 B, real float 4 B, u8 (I,Q) pairs 2 B", {in, out})) != SFE_OK ||
+        (rc = refuse_overlap(who, in, {out})) != SFE_OK || (rc = refuse_capture(who, "sample", s)) != SFE_OK)   // the lead factors' phase
+        return rc;
     SFE_ON_DEVICE(c->device);
     const int fmt = c->in_u8 ? 1 : c->complex_in ? 0 : 2;
-    const int rc = launch_ddc(fmt, d_in, (long long)in_stride, c->d_hist[c->cur], c->d_hist[c->cur ^ 1], c->d_taps, c->d_inc,
-                              static_cast<v2f *>(d_out), (long long)out_stride, (long long)n_in, c->D, c->Ppad, c->H, c->K, c->Kpad,
-                              (unsigned)(c->count & 0xffffffffu), c->n_streams, s);
+    rc = launch_ddc(fmt, d_in, (long long)in_stride, c->hist.cur<void>(), c->hist.next<void>(), c->d_taps, c->d_inc,
+                    static_cast<v2f *>(d_out), (long long)out_stride, (long long)n_in, c->D, c->Ppad, c->H, c->K, c->Kpad,
+                    (unsigned)(c->count & 0xffffffffu), c->n_streams, s);
     if (rc != SFE_OK) return rc;
-    c->cur ^= 1;
+    c->hist.flip();
     c->count += n_in;
     *n_out = no;
     return SFE_OK;
@@ -267,23 +221,11 @@ int sfe_dsp_ddc_reset(sfe_ddc_t h)
 {
     Ddc *c = as_ddc(h);
     if (!c) return SFE_EINVAL;
-    SFE_ON_DEVICE(c->device);
-    SFE_HIP(hipDeviceSynchronize());
-    for (auto *p : c->d_hist) SFE_HIP(hipMemset(p, 0, c->hist_bytes()));
-    SFE_HIP(hipDeviceSynchronize());
-    c->cur = 0;
-    c->count = 0;
-    return SFE_OK;
+    const int rc = reset_pairs(c->device, {&c->hist});
+    if (rc == SFE_OK) c->count = 0;
+    return rc;
 }
 
-int sfe_dsp_ddc_destroy(sfe_ddc_t h)
-{
-    Ddc *c = as_ddc(h);
-    if (!c) return SFE_OK;
-    DeviceGuard g(c->device);
-    (void)hipDeviceSynchronize();
-    ddc_free(c);
-    return SFE_OK;
-}
+int sfe_dsp_ddc_destroy(sfe_ddc_t h) { return destroy_handle(as_ddc(h)); }
 
 }  // extern "C"

@@ -4,48 +4,28 @@
 #include <cmath>
 
 #include "host.h"
+#include "block.h"
 #include "iir.h"
 
 namespace sfe {
 namespace {
 
 struct Iir {
-    uint32_t magic = 0x49495231u;   // 'IIR1'
+    static constexpr uint32_t MAGIC = 0x49495231u;   // 'IIR1'
+    uint32_t magic = MAGIC;
     int S = 0, data_complex = 1, n_streams = 1, device = 0, in_u8 = 0;
-    float *d_sec = nullptr;         // [S][IIR_SEC_FLOATS]
-    float *d_phi = nullptr;         // [2][2S][2S]: the cascade's transition over one block, and over one group of blocks
-    // carried, a pair (the current one and the next call's): per stream and component the true state, the open group's
-    // partial fold and its start state (iir.hip: struct IirSpan)
-    float *d_state[2] = {nullptr, nullptr};
-    int cur = 0;
-    float *d_table = nullptr;       // the per-block and per-group states of one call; grows with the largest call seen
-    size_t table_floats = 0;
+    DevBuf<float> d_sec;            // [S][IIR_SEC_FLOATS]
+    DevBuf<float> d_phi;            // [2][2S][2S]: the cascade's transition over one block, and over one group of blocks
+    // carried (float): per stream and component the true state, the open group's partial fold and its start state
+    // (iir.hip: struct IirSpan)
+    CarriedPair state;
+    GrowScratch table;              // the per-block and per-group states of one call
     unsigned long long blocks = 0;  // per stream since create / reset: the fold's groups are counted from there
     int nc() const { return data_complex ? 2 : 1; }
     size_t state_bytes() const { return (size_t)n_streams * nc() * 3 * 2 * S * sizeof(float); }
 };
 
-Iir *as_iir(void *h)
-{
-    Iir *p = static_cast<Iir *>(h);
-    if (p && p->magic != 0x49495231u) {
-        set_error("not a live IIR-filter handle");
-        return nullptr;
-    }
-    return p;
-}
-
-void iir_free(Iir *p)
-{
-    if (!p) return;
-    if (p->d_sec) (void)hipFree(p->d_sec);
-    if (p->d_phi) (void)hipFree(p->d_phi);
-    for (int i = 0; i < 2; i++)
-        if (p->d_state[i]) (void)hipFree(p->d_state[i]);
-    if (p->d_table) (void)hipFree(p->d_table);
-    p->magic = 0;
-    delete p;
-}
+Iir *as_iir(void *h) { return as_handle<Iir>(h, "IIR-filter"); }
 
 struct Mat2 {
     double m[4];
@@ -191,33 +171,21 @@ int sfe_dsp_iir_create(const double *sos, int n_sections, int data_complex, int 
         set_error("iir: n_streams = %d must be in [1, 32767]", n_streams);
         return SFE_EINVAL;
     }
-    int prev_dev = -1;
-    (void)hipGetDevice(&prev_dev);
-    rc = use_device(device);
-    if (rc != SFE_OK) return rc;
-    struct Restore { int d; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore__{prev_dev};
-    Iir *p = new (std::nothrow) Iir;
+    CreateScope scope(device);
+    if (scope.rc != SFE_OK) return scope.rc;
+    std::unique_ptr<Iir> p(new (std::nothrow) Iir);
     if (!p) return SFE_ENOMEM;
     p->S = n_sections;
     p->data_complex = data_complex ? 1 : 0;
     p->n_streams = n_streams;
     p->device = device;
-    auto fail = [&](int code) { iir_free(p); return code; };
-#define TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail(hip_fail(e__, #call)); } while (0)
     std::vector<float> sec((size_t)n_sections * IIR_SEC_FLOATS);
     for (int q = 0; q < n_sections; q++) iir_section_table(coef + 5 * q, sec.data() + (size_t)q * IIR_SEC_FLOATS);
     const std::vector<float> phi = iir_phi(coef, n_sections, iir_block(), iir_group());
-    TRY(hipMalloc(&p->d_sec, sec.size() * sizeof(float)));
-    TRY(hipMemcpy(p->d_sec, sec.data(), sec.size() * sizeof(float), hipMemcpyHostToDevice));
-    TRY(hipMalloc(&p->d_phi, phi.size() * sizeof(float)));
-    TRY(hipMemcpy(p->d_phi, phi.data(), phi.size() * sizeof(float), hipMemcpyHostToDevice));
-    for (int i = 0; i < 2; i++) {
-        TRY(hipMalloc(&p->d_state[i], p->state_bytes()));
-        TRY(hipMemset(p->d_state[i], 0, p->state_bytes()));
-    }
-    TRY(hipDeviceSynchronize());
-#undef TRY
-    *out = p;
+    if ((rc = p->d_sec.upload(sec)) != SFE_OK || (rc = p->d_phi.upload(phi)) != SFE_OK || (rc = p->state.alloc_zero(p->state_bytes())) != SFE_OK)
+        return rc;
+    SFE_HIP(hipDeviceSynchronize());
+    *out = p.release();
     return SFE_OK;
 }
 
@@ -239,26 +207,19 @@ int sfe_dsp_iir_set_input_format(sfe_iir_t h, int fmt)
 int sfe_dsp_iir_process_stream(sfe_iir_t h, const void *d_in, size_t n_in, size_t in_stride, void *d_out, size_t out_stride,
                                size_t *n_out, sfe_stream_t stream)
 {
-    Iir *p = as_iir(h);
-    if (n_out) *n_out = 0;
-    if (!p || !n_out) {
-        set_error("iir_process_stream: null handle or n_out");
-        return SFE_EINVAL;
-    }
+    static const char who[] = "iir_process_stream";
+    Iir *p = stream_handle(as_iir(h), who, n_out);
+    if (!p) return SFE_EINVAL;
     const size_t G = (size_t)iir_block();
     if (n_in % G) {
         set_error("iir_process_stream: n_in = %zu is not a multiple of the block = %zu", n_in, G);
         return SFE_EINVAL;
     }
-    if (n_in >= ((size_t)1 << 31)) {
-        set_error("iir_process_stream: n_in = %zu must be below 2^31", n_in);
-        return SFE_EINVAL;
-    }
+    int rc = refuse_2_31(who, n_in);
+    if (rc != SFE_OK) return rc;
     if (n_in == 0) return SFE_OK;
-    if (!d_in || !d_out) {
-        set_error("iir_process_stream: null buffer");
-        return SFE_EINVAL;
-    }
+    rc = refuse_null(who, {d_in, d_out});
+    if (rc != SFE_OK) return rc;
     if (out_stride < n_in) {
         set_error("iir_process_stream: out_stride %zu < n_in = %zu", out_stride, n_in);
         return SFE_ERANGE;
@@ -268,40 +229,26 @@ int sfe_dsp_iir_process_stream(sfe_iir_t h, const void *d_in, size_t n_in, size_
         return SFE_EINVAL;
     }
     const size_t isz = p->in_u8 ? 2 : p->data_complex ? 8 : 4, osz = p->data_complex ? 8 : 4;
-    if ((reinterpret_cast<uintptr_t>(d_in) & (isz - 1)) || (reinterpret_cast<uintptr_t>(d_out) & (osz - 1))) {
-        set_error("iir_process_stream: buffers must be aligned to their element (cf32 8 B, u8 (I,Q) pairs 2 B, float32 4 B)");
-        return SFE_EINVAL;
-    }
     const size_t in_b = ((size_t)(p->n_streams - 1) * in_stride + n_in) * isz;
     const size_t out_b = ((size_t)(p->n_streams - 1) * out_stride + n_in) * osz;
-    if (ranges_overlap(d_in, in_b, d_out, out_b)) {
-        set_error("iir_process_stream: input and output ranges overlap (in-place operation is not supported)");
-        return SFE_EINVAL;
-    }
+    const Span in{d_in, in_b, isz}, out{d_out, out_b, osz};
     hipStream_t s = (hipStream_t)stream;
-    if (stream_is_capturing(s)) {
-        // the block counter and the buffer pair of the carried state advance on the host
-        set_error("iir_process_stream: graph capture is not supported (the sample counter lives on the host)");
-        return SFE_ESTATE;
-    }
+    if ((rc = refuse_misaligned(who, "cf32 8 B, u8 (I,Q) pairs 2 B, float32 4 B", {in, out})) != SFE_OK ||
+        (rc = refuse_overlap(who, in, {out})) != SFE_OK || (rc = refuse_capture(who, "sample", s)) != SFE_OK)   // counted in blocks
+        return rc;
     SFE_ON_DEVICE(p->device);
     // the one allocation a call may make: the table of block and group states grows when a larger call than any before arrives
     // (sized for the most groups a call of nb blocks can touch, wherever it starts)
     const size_t nb = n_in / G, K = (size_t)iir_group(), need = (nb + (nb + K - 2) / K + 1) * p->n_streams * p->nc() * 2 * p->S;
-    if (need > p->table_floats) {
-        SFE_HIP(hipDeviceSynchronize());
-        if (p->d_table) (void)hipFree(p->d_table);
-        p->d_table = nullptr;
-        p->table_floats = 0;
-        SFE_HIP(hipMalloc(&p->d_table, need * sizeof(float)));
-        p->table_floats = need;
-    }
-    const int fmt = p->in_u8 ? 1 : p->data_complex ? 0 : 2;
-    const int n2 = 2 * p->S, c = p->cur;
-    const int rc = launch_iir(fmt, d_in, (long long)in_stride, d_out, (long long)out_stride, p->d_sec, p->d_phi, p->d_phi + n2 * n2,
-                              p->d_table, p->d_state[c], p->d_state[c ^ 1], (long long)p->blocks, (int)nb, p->S, p->n_streams, s);
+    rc = p->table.reserve(need * sizeof(float));
     if (rc != SFE_OK) return rc;
-    p->cur ^= 1;
+    const int fmt = p->in_u8 ? 1 : p->data_complex ? 0 : 2;
+    const int n2 = 2 * p->S;
+    rc = launch_iir(fmt, d_in, (long long)in_stride, d_out, (long long)out_stride, p->d_sec, p->d_phi, p->d_phi + n2 * n2,
+                    p->table.as<float>(), p->state.cur<float>(), p->state.next<float>(), (long long)p->blocks, (int)nb, p->S, p->n_streams,
+                    s);
+    if (rc != SFE_OK) return rc;
+    p->state.flip();
     p->blocks += nb;
     *n_out = n_in;
     return SFE_OK;
@@ -311,23 +258,11 @@ int sfe_dsp_iir_reset(sfe_iir_t h)
 {
     Iir *p = as_iir(h);
     if (!p) return SFE_EINVAL;
-    SFE_ON_DEVICE(p->device);
-    SFE_HIP(hipDeviceSynchronize());
-    for (int i = 0; i < 2; i++) SFE_HIP(hipMemset(p->d_state[i], 0, p->state_bytes()));
-    SFE_HIP(hipDeviceSynchronize());
-    p->cur = 0;
-    p->blocks = 0;
-    return SFE_OK;
+    const int rc = reset_pairs(p->device, {&p->state});
+    if (rc == SFE_OK) p->blocks = 0;
+    return rc;
 }
 
-int sfe_dsp_iir_destroy(sfe_iir_t h)
-{
-    Iir *p = as_iir(h);
-    if (!p) return SFE_OK;
-    DeviceGuard g(p->device);
-    (void)hipDeviceSynchronize();
-    iir_free(p);
-    return SFE_OK;
-}
+int sfe_dsp_iir_destroy(sfe_iir_t h) { return destroy_handle(as_iir(h)); }
 
 }  // extern "C"
