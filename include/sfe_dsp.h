@@ -743,6 +743,75 @@ int sfe_dsp_iir_process_stream(sfe_iir_t h, const void *d_in, size_t n_in, size_
 int sfe_dsp_iir_reset(sfe_iir_t h);
 int sfe_dsp_iir_destroy(sfe_iir_t h);
 
+/* ------------------------------------------------- multi-stream beamformer / stream-mixing bank
+ * The one block whose streams meet: B output beams out of S input streams, in each of M bands
+ * (M = 1: narrowband).  Band k holds complex weights W_k[b][s] and, optionally, conjugate weights
+ * V_k[b][s] (absent: all zero), and
+ *     y_{b,k}[m] = sum_{s<S}  W_k[b][s] x_{s,k}[m]  +  V_k[b][s] conj(x_{s,k}[m])
+ * -- a beam, a null, a diversity combiner, a sub-band mix; with S = B = 1 and V the I/Q imbalance
+ * correction y = a x + b conj(x) of a direct-conversion receiver.
+ * Real matrix.  The host turns each band's (W, V) into one real matrix R_k of 2B x 2S float32:
+ * row 2b is Re y_b, row 2b+1 is Im y_b, column 2s is Re x_s, column 2s+1 is Im x_s, and
+ *     R[2b][2s]   =  Wr + Vr        R[2b][2s+1]   = -Wi + Vi
+ *     R[2b+1][2s] =  Wi + Vi        R[2b+1][2s+1] =  Wr - Vr
+ * each entry formed in float64 from the float32 arguments and rounded ONCE to float32; with V
+ * absent the entries are W's own floats, up to sign.  The law is stated on those rounded values:
+ * each output float is a float32 dot product of length 2S, computed on the matrix pipe
+ * (csrc/beam.hip) as a chain of fused multiply-adds from zero.  The order of the 2S terms is
+ * fixed per shape (S, B); it never depends on where a sample sits in a call, a tile or a buffer.
+ * Layouts.  There is no state across samples: no carried history and NO GRANULE, any n_in >= 1 is
+ * accepted.  x_{s,k}[m] is at d_in + (s*M + k)*in_stride + m (sfe_dsp_chan_*'s output layout);
+ * y_{b,k}[m] is at d_out + (b*M + k)*out_stride + m (sfe_dsp_combine_*'s input layout), cf32,
+ * 8-byte aligned.  Input: cf32 (8-byte aligned) or SFE_FMT_U8 (I,Q) byte pairs (2-byte aligned),
+ * converted (b-128)*(1/127) on load exactly as sfe_dsp_rx_u8_to_f32 converts them.  A non-finite
+ * input sample poisons every beam of its own instant and band (0 * NaN is NaN) and nothing else.
+ * Shapes: 1 <= S <= 64, 1 <= B <= 64, 1 <= M <= 1024, M*B*S <= 2^20, every weight finite;
+ * anything else is SFE_EINVAL with a message that starts with "beam: ".
+ * Contracts about bits:
+ *   1. cutting a stream into calls at ANY sample gives the one-call output bit for bit, and so does
+ *      moving a buffer to any element-aligned address or changing the strides (a call's tail runs
+ *      the arithmetic of its body, with masked loads and stores);
+ *   2. u8 input gives the bits of the cf32 path on the converted samples, and the format may
+ *      change between calls;
+ *   3. band k of an M-band handle gives the bits of a one-band handle of the same (S, B) holding
+ *      W_k, V_k;
+ *   4. a selection is exact: if each row of W has a single entry 1+0j, the rest 0 and V absent,
+ *      beam b is the chosen stream bit for bit on finite input; with that entry placed in V
+ *      instead, it is the stream's conjugate bit for bit (a zero comes out as +0: a sum that
+ *      starts from zero cannot return -0);
+ *   5. the same calls give the same bits on every run.
+ * Not promised: equal bits between different shapes (S, B) -- beam b of a 64-beam handle may
+ * differ in the last place from a one-beam handle holding row b -- nor the bits of any particular
+ * left fold. */
+typedef void *sfe_beam_t; /* opaque: one weight set, M bands of S streams into B beams */
+/* Host-only (no GPU): validates the shape and the weights as above; if real_matrix != NULL writes
+ * the M*2B*2S float32 of the R_k there, band-major, each row-major.
+ *   weights       [n_bands][n_beams][n_in] (re, im) float32 pairs
+ *   weights_conj  the same shape, or NULL */
+int sfe_dsp_beam_plan(int n_in, int n_beams, int n_bands, const float *weights,
+                      const float *weights_conj, float *real_matrix);
+/* The weights are copied.  Shapes and weight values are checked before the device is touched:
+ * SFE_EINVAL for a bad shape on any machine, SFE_ENODEV without a GPU. */
+int sfe_dsp_beam_create(const float *weights, const float *weights_conj, int n_in, int n_beams,
+                        int n_bands, int device, sfe_beam_t *out);
+/* SFE_FMT_F32 (cf32 input, 8-byte aligned) or SFE_FMT_U8 ((I,Q) byte pairs, 2-byte aligned,
+ * converted on load); any other format is SFE_EINVAL. */
+int sfe_dsp_beam_set_input_format(sfe_beam_t h, int fmt);
+/* New weights of the handle's shape (validated as at create), used from the next call on: the
+ * result then equals a fresh handle created with them, bit for bit.  May block until the handle's
+ * earlier calls have finished; never changes what an already enqueued call computes. */
+int sfe_dsp_beam_set_weights(sfe_beam_t h, const float *weights, const float *weights_conj);
+/* n_in samples of every band of every stream.  *n_out = n_in.  n_in = 0 is a no-op; n_in >= 2^31
+ * is SFE_EINVAL.  out_stride < n_in is SFE_ERANGE; in_stride < n_in, null or misaligned buffers
+ * and overlapping input and output byte ranges are SFE_EINVAL; nothing is launched on a refusal.
+ * Asynchronous on `stream`; allocates nothing and does not synchronise the host.  A call on a
+ * stream under graph capture is SFE_ESTATE, nothing enqueued: sfe_dsp_beam_set_weights may
+ * replace the table a captured call would have pinned.
+ * There is no reset: there is nothing to reset. */
+int sfe_dsp_beam_process_stream(sfe_beam_t h, const void *d_in, size_t n_in, size_t in_stride,
+                                void *d_out, size_t out_stride, size_t *n_out, sfe_stream_t stream);
+int sfe_dsp_beam_destroy(sfe_beam_t h);
+
 #ifdef __cplusplus
 }
 #endif

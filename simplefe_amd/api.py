@@ -9,7 +9,7 @@ Two layers, both thin:
     parity tests (sfe_dsp_*_process_stream); `Chan`, the polyphase channelizer (sfe_dsp_chan_*); `Combiner`, its
     transpose, the synthesis filter bank (sfe_dsp_combine_*); `Psd`, the streaming Welch spectrum estimator (sfe_dsp_psd_*);
     `Corr`, the streaming preamble correlator bank (sfe_dsp_corr_*); `Iir`, the streaming biquad-cascade IIR filter
-    (sfe_dsp_iir_*).
+    (sfe_dsp_iir_*); `Beam`, the multi-stream beamformer / stream-mixing bank (sfe_dsp_beam_*).
 
 Everything computes on the GPU through the C ABI; numpy is only the host container.
 """
@@ -787,6 +787,78 @@ class Iir(_Block):
             d_out.free()
         y = (y.view(np.complex64) if self.data_complex else y).reshape(S, npad)[:, :n]
         return np.ascontiguousarray(y[0] if one else y)
+
+
+def _beam_weights(W, V):
+    """(W as (M, B, S) complex64, V the same or None, their float pointers): (B, S) weights are one band."""
+    W = np.asarray(W, dtype=np.complex64)
+    W = np.ascontiguousarray(W[None] if W.ndim == 2 else W)
+    if W.ndim != 3:
+        raise ValueError("beam weights must be (n_beams, n_in) or (n_bands, n_beams, n_in) complex")
+    if V is not None:
+        V = np.ascontiguousarray(np.asarray(V, dtype=np.complex64).reshape(W.shape))
+    fp = C.POINTER(C.c_float)
+    return W, V, W.view(np.float32).ctypes.data_as(fp), (None if V is None else V.view(np.float32).ctypes.data_as(fp))
+
+
+def beam_plan(W, V=None):
+    """sfe_dsp_beam_plan (host only, no GPU): the real matrices R_k the kernel multiplies by, (M, 2B, 2S) float32.
+    Raises SfeError on a shape or weights the block refuses."""
+    W, V, pw, pv = _beam_weights(W, V)
+    M, B, S = W.shape
+    R = np.empty((M, 2 * B, 2 * S), dtype=np.float32)
+    check(_l.load().sfe_dsp_beam_plan(S, B, M, pw, pv, R.ctypes.data_as(C.POINTER(C.c_float))))
+    return R
+
+
+class Beam(_Block):
+    """Multi-stream beamformer / stream-mixing bank (sfe_dsp_beam_*): n_beams = B outputs out of n_in = S streams in each
+    of n_bands = M bands, y_b = sum_s W[b][s] x_s + V[b][s] conj(x_s).  W (and V, optional) are (M, B, S) complex, or
+    (B, S) for one band."""
+    _prefix = "beam"
+
+    def __init__(self, W, V=None, device=0):
+        W, V, pw, pv = _beam_weights(W, V)
+        self.n_bands, self.n_beams, self.n_in = (int(v) for v in W.shape)
+        self.n_streams = self.n_in * self.n_bands           # rows of an input buffer
+        self.in_u8 = False
+        self._create(pw, pv, self.n_in, self.n_beams, self.n_bands, device)
+
+    def set_input_format(self, fmt):
+        """lib.FMT_F32 (cf32) or lib.FMT_U8 ((I,Q) byte pairs, converted on load)."""
+        self._set_input_format(fmt)
+
+    def set_weights(self, W, V=None):
+        """New weights of the same shape, used from the next call on."""
+        W, V, pw, pv = _beam_weights(W, V)
+        if W.shape != (self.n_bands, self.n_beams, self.n_in):
+            raise ValueError("set_weights: shape %s for a handle of %s" % (W.shape, (self.n_bands, self.n_beams, self.n_in)))
+        check(self._fn("set_weights")(self._h, pw, pv))
+
+    def process_stream(self, d_in, n_in, d_out, in_stride=None, out_stride=None, stream=None):
+        """d_in / d_out: DeviceArray or raw device pointers; n_in >= 1 samples.  Band k of stream s is read at
+        d_in + (s*M + k)*in_stride, band k of beam b written at d_out + (b*M + k)*out_stride cf32 samples; both strides
+        default to n_in.  Returns n_out = n_in."""
+        return self._process_stream(d_in, n_in, in_stride, d_out, int(n_in) if out_stride is None else out_stride, stream)
+
+    def reset(self):
+        raise AttributeError("Beam has no reset: it carries no state")
+
+    def mix(self, x):
+        """Host convenience, computed on the GPU: x is (S, M, n) complex64 ((S, n) for one band) -- or, with FMT_U8, uint8
+        (I,Q) pairs with a last axis of 2n -- and the result (B, M, n) ((B, n)) complex64."""
+        one = self.n_bands == 1 and np.ndim(x) == 2
+        d_in, n = self._upload_input(x)
+        d_out = DeviceArray(max(1, self.n_beams * self.n_bands * n) * 2)
+        try:
+            if n:
+                self.process_stream(d_in, n, d_out)
+            y = d_out.to_numpy(self.n_beams * self.n_bands * n * 2)
+        finally:
+            d_in.free()
+            d_out.free()
+        y = y.view(np.complex64).reshape(self.n_beams, self.n_bands, n)
+        return np.ascontiguousarray(y[:, 0] if one else y)
 
 
 def rs_plan(state, upsample, n_in, out_len, rate):

@@ -6,7 +6,7 @@
 //   api_rs.hip     the resample / decimate handle: time law, run memo, kernel choice, sfe_dsp_rs_*
 //   api_pipe.hip   the pinned host pipe over either handle, sfe_dsp_*_pipe_*
 //   group.hip      channel blocks over several devices, sfe_dsp_*_group_* (over the public C ABI only)
-//   block.h        what the streaming blocks' handles share (api_chan, api_combine, api_ddc, api_psd, api_corr, api_iir .hip):
+//   block.h        what the streaming blocks' handles share (api_chan, api_combine, api_ddc, api_psd, api_corr, api_iir, api_beam .hip):
 //                  device-memory owners, the carried pair, create's device scope, the handle cast, process_stream's refusals
 #pragma once
 #include <math.h>

@@ -142,6 +142,12 @@ SIGNATURES = {
     "sfe_dsp_iir_process_stream": (i32, [vp, vp, sz, sz, vp, sz, C.POINTER(sz), vp]),
     "sfe_dsp_iir_reset": (i32, [vp]),
     "sfe_dsp_iir_destroy": (i32, [vp]),
+    "sfe_dsp_beam_plan": (i32, [i32, i32, i32, fp, fp, fp]),
+    "sfe_dsp_beam_create": (i32, [fp, fp, i32, i32, i32, i32, C.POINTER(vp)]),
+    "sfe_dsp_beam_set_input_format": (i32, [vp, i32]),
+    "sfe_dsp_beam_set_weights": (i32, [vp, fp, fp]),
+    "sfe_dsp_beam_process_stream": (i32, [vp, vp, sz, sz, vp, sz, C.POINTER(sz), vp]),
+    "sfe_dsp_beam_destroy": (i32, [vp]),
 }
 
 # the diagnostic library only (simplefe_amd/csrc/diag/sfe_dsp_diag.h; scripts/ load it by pointing LIB_PATH at it): bound when present

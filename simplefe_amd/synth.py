@@ -451,6 +451,66 @@ def iir_grid_filters():
             "dc(0.999)+butter(8,0.1)": np.vstack([iir_dc_blocker(0.999), iir_butter_lowpass(8, 0.1)])}
 
 
+# ---- the beamformer / stream-mixing bank (sfe_dsp_beam_*): weights are (M, B, S) complex64 ((B, S): one band)
+def _beam_weights(W, V):
+    W = np.asarray(W, dtype=np.complex64)
+    W = W[None] if W.ndim == 2 else W
+    if W.ndim != 3:
+        raise ValueError("beam weights must be (n_beams, n_in) or (n_bands, n_beams, n_in)")
+    if V is not None:
+        V = np.asarray(V, dtype=np.complex64).reshape(W.shape)
+    return np.ascontiguousarray(W), (None if V is None else np.ascontiguousarray(V))
+
+
+def beam_real_matrix(W, V=None):
+    """The host twin of sfe_dsp_beam_plan: the real matrices R_k, (M, 2B, 2S) float32.  Row 2b / 2b+1 is Re / Im of beam
+    b, column 2s / 2s+1 is Re / Im of stream s; every entry is formed in float64 from the float32 weights and rounded
+    once.  With V absent the entries are W's own floats up to sign."""
+    W, V = _beam_weights(W, V)
+    M, B, S = W.shape
+    R = np.empty((M, 2 * B, 2 * S), dtype=np.float32)
+    if V is None:
+        R[:, 0::2, 0::2] = W.real
+        R[:, 0::2, 1::2] = -W.imag
+        R[:, 1::2, 0::2] = W.imag
+        R[:, 1::2, 1::2] = W.real
+    else:
+        wr, wi = W.real.astype(np.float64), W.imag.astype(np.float64)
+        vr, vi = V.real.astype(np.float64), V.imag.astype(np.float64)
+        R[:, 0::2, 0::2] = wr + vr
+        R[:, 0::2, 1::2] = -wi + vi
+        R[:, 1::2, 0::2] = wi + vi
+        R[:, 1::2, 1::2] = wr - vr
+    return R
+
+
+def beam_reference(x, W, V=None, dtype=np.float64):
+    """The law of sfe_dsp_beam_* evaluated on the rounded real matrices: x is (S, M, n) complex ((S, n) for one band),
+    the result (B, M, n) ((B, n)) complex128 -- or, with dtype=np.float32, complex64 from a float32 matrix product
+    (numpy's own summation order: a yardstick, not the kernel's bits)."""
+    R = beam_real_matrix(W, V)
+    M, B2, S2 = R.shape
+    x = np.asarray(x)
+    one = x.ndim == 2
+    z = np.ascontiguousarray(x.reshape(S2 // 2, M, -1).astype(np.complex128))
+    X = np.empty((M, S2, z.shape[2]), dtype=dtype)
+    X[:, 0::2] = z.real.transpose(1, 0, 2)
+    X[:, 1::2] = z.imag.transpose(1, 0, 2)
+    Y = np.matmul(R.astype(dtype), X)                               # (M, 2B, n)
+    y = (Y[:, 0::2] + 1j * Y[:, 1::2]).transpose(1, 0, 2)
+    y = y.astype(np.complex128 if dtype == np.float64 else np.complex64)
+    return y[:, 0] if one else y
+
+
+def beam_steering_weights(n_in, n_beams):
+    """(n_beams, n_in) complex64: a uniform linear array of n_in elements at half-wavelength spacing, beam b steered to
+    sin(theta_b) = -1 + (2 b + 1) / n_beams (a sine grid), each row scaled to unit gain in its own direction:
+    W[b][s] = exp(-j pi s sin(theta_b)) / n_in."""
+    u = -1.0 + (2.0 * np.arange(n_beams) + 1.0) / n_beams
+    s = np.arange(n_in)
+    return (np.exp(-1j * np.pi * u[:, None] * s[None, :]) / n_in).astype(np.complex64)
+
+
 def offset_bytes(n_samples, bias=0, seed=SEED):
     """2 n uint8 (I,Q) bytes, uniformly random: over all 256 values with bias = 0 (the converted stream has a mean near 0),
     or over [2 bias, 256) (a mean near 128 + bias: bias = 38 gives bytes around 166, a converted mean near 0.3)."""
