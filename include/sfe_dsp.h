@@ -812,6 +812,82 @@ int sfe_dsp_beam_process_stream(sfe_beam_t h, const void *d_in, size_t n_in, siz
                                 void *d_out, size_t out_stride, size_t *n_out, sfe_stream_t stream);
 int sfe_dsp_beam_destroy(sfe_beam_t h);
 
+/* ------------------------------------------------- streaming spatial covariance estimator
+ * Where the beamformer's weights come from: the sample covariance of the S streams of each of M
+ * bands, averaged A instants at a time.  Write instant m of band k as a real column of 2S floats,
+ *     u[2s] = Re x_{s,k}[m],   u[2s+1] = Im x_{s,k}[m]
+ * (interleaved cf32 as it lies in memory, and the beamformer's column order).  Output row r of band
+ * k is the real Gram matrix
+ *     G_r[i][j] = scale * sum over m in [rA, (r + 1)A) of u_i[m] u_j[m]
+ * 2S x 2S float32, row-major, stored whole (both triangles); m the absolute instant since create /
+ * reset.  One real matrix carries the covariance C = E[x x^H] and the pseudo-covariance
+ * P = E[x x^T] that the beamformer's widely-linear weights V need:
+ *     C[s][t] = (G[2s][2t] + G[2s+1][2t+1]) + j (G[2s+1][2t] - G[2s][2t+1])
+ *     P[s][t] = (G[2s][2t] - G[2s+1][2t+1]) + j (G[2s+1][2t] + G[2s][2t+1])
+ * No implicit normalisation: the caller puts 1/A into scale.
+ * Summation order (part of the contract).  A row's instants are taken in chunks of T consecutive
+ * instants counted from the row's first; the chunk partial of entry (i, j) is the float32 fmaf
+ * chain from +0 over its T products in ascending instant order (what consecutive
+ * v_mfma_f32_16x16x4_f32 instructions compute when K is the instant index).  Chunks are taken in
+ * groups of C consecutive chunks counted from the row's first (the last group of a row may be
+ * shorter), C the smallest power of two with C C >= A/T; the group sum is the float32 left fold,
+ * from 0, of its chunk partials in ascending order; the row is the float32 left fold, from 0, of
+ * its group sums in ascending order; scale multiplies once, after the last fold.  T = 64 for every
+ * S, M and format (sfe_dsp_cov_plan reports T and C).  The order is a function of (A, m - rA)
+ * only: never of S, of where calls are cut, of the grid or of the input format.
+ * Shapes: 1 <= S <= 64, 1 <= M <= 1024, A a positive multiple of T at most 2^24, scale finite;
+ * anything else is SFE_EINVAL with a message that starts with "cov: ".
+ * Layouts: x_{s,k}[m] is at d_in + (s*M + k)*in_stride + m (sfe_dsp_chan_*'s output layout and
+ * sfe_dsp_beam_*'s input layout); cf32 (8-byte aligned) or SFE_FMT_U8 (I,Q) byte pairs (2-byte
+ * aligned), converted (b-128)*(1/127) on load exactly as sfe_dsp_rx_u8_to_f32 converts them.
+ * Contracts about bits:
+ *   1. cutting a stream into calls at any multiple of T gives the one-call rows bit for bit, cuts
+ *      in mid-group and mid-row included;
+ *   2. u8 input gives the bits of the cf32 path on the converted samples, and the format may
+ *      change between calls (the carried state is float32 sums, not samples);
+ *   3. band k of an M-band handle gives the bits of a one-band handle fed band k;
+ *   4. entry (i, j) depends on rows i and j of U only: a handle over any subset of the streams
+ *      gives the same bits for the entries they share (S = 1 handles reproduce the 2 x 2 diagonal
+ *      blocks of any larger handle);
+ *   5. G[i][j] and G[j][i] are the same bits;
+ *   6. small-integer cf32 input (every product and partial sum exact in float32) with scale a
+ *      power of two gives the exact Gram;
+ *   7. a non-finite sample poisons rows and columns 2s, 2s+1 of its own stream, in its own band
+ *      and output row, and nothing else; the next output row is clean;
+ *   8. the same calls give the same bits on every run;
+ *   9. reset makes a fresh handle.
+ * Not promised: the bits of any other fold (a plain left fold over A, a library matmul).
+ * Computed by csrc/cov.hip: a chunk of U staged in LDS, the upper-triangular 16 x 16 tiles on the
+ * f32 matrix pipe, chunk partial and group sum in registers; a second small kernel folds the
+ * group sums per row and mirrors the triangle on the store. */
+typedef void *sfe_cov_t;  /* opaque: one estimator over M bands of S streams */
+/* Host-only (no GPU): validates the shape; *chunk = T, *group = C.  Either output pointer may be
+ * NULL. */
+int sfe_dsp_cov_plan(int n_in_streams, int n_bands, int n_avg, int *chunk, int *group);
+/* Every band has its own open group and open row; one instant counter.  Shapes are checked before
+ * the device is touched: SFE_EINVAL for a bad shape on any machine, SFE_ENODEV without a GPU. */
+int sfe_dsp_cov_create(int n_in_streams, int n_bands, int n_avg, float scale, int device,
+                       sfe_cov_t *out);
+/* SFE_FMT_F32 (cf32 input, 8-byte aligned) or SFE_FMT_U8 ((I,Q) byte pairs, 2-byte aligned,
+ * converted on load); any other format is SFE_EINVAL. */
+int sfe_dsp_cov_set_input_format(sfe_cov_t h, int fmt);
+/* n_in instants of every band of every stream.  The rows this call completes are written
+ * consecutively: row j of band k at d_out + k*out_stride + j*(2S)^2 (float32, 4-byte aligned);
+ * *n_rows = floor((instants_before mod A + n_in) / A).  A call that completes no row writes
+ * nothing and returns SFE_OK with *n_rows = 0.  n_in a multiple of T below 2^31 (else
+ * SFE_EINVAL); n_in = 0 is a no-op.  out_stride < *n_rows * (2S)^2 is SFE_ERANGE; in_stride <
+ * n_in, null or misaligned buffers and overlapping input and output byte ranges are SFE_EINVAL;
+ * nothing is launched on a refusal.  Asynchronous on `stream`.  The handle owns a scratch buffer
+ * for the group sums of one call, sized on the first call and grown only when a larger call
+ * arrives (synchronise, free, allocate): that is the one allocation, and the one host
+ * synchronisation, a call may make.  The instant counter lives on the host: a call on a stream
+ * under graph capture is SFE_ESTATE, nothing enqueued. */
+int sfe_dsp_cov_process_stream(sfe_cov_t h, const void *d_in, size_t n_in, size_t in_stride,
+                               void *d_out, size_t out_stride, size_t *n_rows, sfe_stream_t stream);
+/* Zero the carried state and the instant counter (a fresh handle); an unfinished row is dropped. */
+int sfe_dsp_cov_reset(sfe_cov_t h);
+int sfe_dsp_cov_destroy(sfe_cov_t h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,8 @@ Two layers, both thin:
     parity tests (sfe_dsp_*_process_stream); `Chan`, the polyphase channelizer (sfe_dsp_chan_*); `Combiner`, its
     transpose, the synthesis filter bank (sfe_dsp_combine_*); `Psd`, the streaming Welch spectrum estimator (sfe_dsp_psd_*);
     `Corr`, the streaming preamble correlator bank (sfe_dsp_corr_*); `Iir`, the streaming biquad-cascade IIR filter
-    (sfe_dsp_iir_*); `Beam`, the multi-stream beamformer / stream-mixing bank (sfe_dsp_beam_*).
+    (sfe_dsp_iir_*); `Beam`, the multi-stream beamformer / stream-mixing bank (sfe_dsp_beam_*); `Cov`, the streaming
+    spatial covariance estimator (sfe_dsp_cov_*).
 
 Everything computes on the GPU through the C ABI; numpy is only the host container.
 """
@@ -859,6 +860,54 @@ class Beam(_Block):
             d_out.free()
         y = y.view(np.complex64).reshape(self.n_beams, self.n_bands, n)
         return np.ascontiguousarray(y[:, 0] if one else y)
+
+
+def cov_plan(n_in, n_bands, n_avg):
+    """sfe_dsp_cov_plan (host only, no GPU): (instants per chunk T, chunks per group C) of the summation order."""
+    t, c = C.c_int(0), C.c_int(0)
+    check(_l.load().sfe_dsp_cov_plan(int(n_in), int(n_bands), int(n_avg), C.byref(t), C.byref(c)))
+    return t.value, c.value
+
+
+class Cov(_Block):
+    """Streaming spatial covariance estimator (sfe_dsp_cov_*): per band, scale times the sum over n_avg instants of
+    u u^T, u the 2 n_in real floats of an instant of n_in = S complex streams; rows of (2S)^2 float32."""
+    _prefix = "cov"
+
+    def __init__(self, n_in, n_bands=1, n_avg=64, scale=1.0, device=0):
+        self.n_in, self.n_bands, self.n_avg = int(n_in), int(n_bands), int(n_avg)
+        self.n_streams = self.n_in * self.n_bands           # rows of an input buffer
+        self.in_u8 = False
+        self._create(self.n_in, self.n_bands, self.n_avg, float(scale), device)
+        self.chunk = cov_plan(self.n_in, self.n_bands, self.n_avg)[0]
+
+    def set_input_format(self, fmt):
+        """lib.FMT_F32 (cf32) or lib.FMT_U8 ((I,Q) byte pairs, converted on load)."""
+        self._set_input_format(fmt)
+
+    def process_stream(self, d_in, n_in, d_out, in_stride=None, out_stride=None, stream=None):
+        """d_in / d_out: DeviceArray or raw device pointers; n_in instants (a multiple of the chunk).  Band k of stream s
+        is read at d_in + (s*M + k)*in_stride; row j of band k that the call completes goes to
+        d_out + k*out_stride + j*(2S)^2 floats; out_stride defaults to the rows n_in instants can complete at the most.
+        Returns the number of rows written per band."""
+        most = -(-int(n_in) // self.n_avg) * 4 * self.n_in * self.n_in
+        return self._process_stream(d_in, n_in, in_stride, d_out, most if out_stride is None else out_stride, stream)
+
+    def gram(self, x):
+        """Host convenience, computed on the GPU: x is (S, M, n) complex64 ((S, n) for one band) -- or, with FMT_U8, uint8
+        (I,Q) pairs with a last axis of 2n -- n a multiple of the chunk; returns the rows the call completes,
+        (M, rows, 2S, 2S) float32."""
+        d_in, n = self._upload_input(x)
+        n2 = 2 * self.n_in
+        stride = -(-n // self.n_avg) * n2 * n2
+        d_out = DeviceArray(max(1, self.n_bands * stride))
+        try:
+            k = self.process_stream(d_in, n, d_out, out_stride=stride)
+            y = d_out.to_numpy(self.n_bands * stride).reshape(self.n_bands, -1, n2, n2)[:, :k]
+        finally:
+            d_in.free()
+            d_out.free()
+        return np.ascontiguousarray(y)
 
 
 def rs_plan(state, upsample, n_in, out_len, rate):

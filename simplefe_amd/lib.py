@@ -148,6 +148,12 @@ SIGNATURES = {
     "sfe_dsp_beam_set_weights": (i32, [vp, fp, fp]),
     "sfe_dsp_beam_process_stream": (i32, [vp, vp, sz, sz, vp, sz, C.POINTER(sz), vp]),
     "sfe_dsp_beam_destroy": (i32, [vp]),
+    "sfe_dsp_cov_plan": (i32, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
+    "sfe_dsp_cov_create": (i32, [i32, i32, i32, f32, i32, C.POINTER(vp)]),
+    "sfe_dsp_cov_set_input_format": (i32, [vp, i32]),
+    "sfe_dsp_cov_process_stream": (i32, [vp, vp, sz, sz, vp, sz, C.POINTER(sz), vp]),
+    "sfe_dsp_cov_reset": (i32, [vp]),
+    "sfe_dsp_cov_destroy": (i32, [vp]),
 }
 
 # the diagnostic library only (simplefe_amd/csrc/diag/sfe_dsp_diag.h; scripts/ load it by pointing LIB_PATH at it): bound when present

@@ -511,6 +511,64 @@ def beam_steering_weights(n_in, n_beams):
     return (np.exp(-1j * np.pi * u[:, None] * s[None, :]) / n_in).astype(np.complex64)
 
 
+# ---- the spatial covariance estimator (sfe_dsp_cov_*): x is (S, M, n) complex ((S, n): one band)
+def cov_columns(x, S, M):
+    """The real columns u of the law: (M, 2S, n) float64, row 2s / 2s+1 the real / imaginary part of stream s."""
+    z = np.asarray(x).reshape(S, M, -1).astype(np.complex128)
+    U = np.empty((M, 2 * S, z.shape[2]))
+    U[:, 0::2] = z.real.transpose(1, 0, 2)
+    U[:, 1::2] = z.imag.transpose(1, 0, 2)
+    return U
+
+
+def cov_reference(x, S, M, A, scale):
+    """The law of sfe_dsp_cov_* in float64: the rows that n instants complete, (M, n // A, 2S, 2S).  float64 sums in
+    numpy's order: the yardstick of the values, not of the kernel's bits."""
+    U = cov_columns(x, S, M)
+    rows = U.shape[2] // A
+    U = U[:, :, :rows * A].reshape(M, 2 * S, rows, A)
+    return float(scale) * np.einsum("kira,kjra->krij", U, U)
+
+
+def cov_from_gram(G):
+    """(C, P) complex128 out of real Gram matrices (..., 2S, 2S): C = E[x x^H], the covariance, and P = E[x x^T], the
+    pseudo-covariance."""
+    G = np.asarray(G, dtype=np.float64)
+    rr, ri, ir, ii = G[..., 0::2, 0::2], G[..., 0::2, 1::2], G[..., 1::2, 0::2], G[..., 1::2, 1::2]
+    return (rr + ii) + 1j * (ir - ri), (rr - ii) + 1j * (ir + ri)
+
+
+def mvdr_weights(C, steering, loading=0.0):
+    """Minimum-variance distortionless-response weights in float64: w = R^-1 a / (a^H R^-1 a) with
+    R = C + loading tr(C)/S I.  Returns the (1, 1, S) complex64 row w^H that Beam takes: y = w^H x has unit response on
+    the steering vector a."""
+    C = np.asarray(C, dtype=np.complex128)
+    a = np.asarray(steering, dtype=np.complex128).ravel()
+    S = a.size
+    R = C.reshape(S, S) + loading * np.trace(C.reshape(S, S)).real / S * np.eye(S)
+    Ra = np.linalg.solve(R, a)
+    w = Ra / (a.conj() @ Ra)
+    return w.conj().reshape(1, 1, S).astype(np.complex64)
+
+
+def cov_scene(S, n, seed):
+    """A uniform linear array of S elements at half-wavelength spacing (steering exp(j pi k sin theta)) that hears a
+    unit-power QPSK signal d from 10 degrees, a complex normal interferer 30 dB above it from -35 degrees and, per
+    element, complex normal noise 20 dB below it; the sum scaled to max |x| = 0.9.  Drawn from
+    np.random.default_rng(seed) in that order.  Returns (x, x_d, x_i, a_d): the (S, n) complex64 sum, its desired and
+    interferer parts (same scale, complex64) and the desired steering vector (complex128)."""
+    rng = np.random.default_rng(seed)
+    d = ((2.0 * rng.integers(0, 2, n) - 1.0) + 1j * (2.0 * rng.integers(0, 2, n) - 1.0)) / np.sqrt(2.0)
+    i = (rng.standard_normal(n) + 1j * rng.standard_normal(n)) * np.sqrt(10.0 ** 3.0 / 2.0)
+    noise = (rng.standard_normal((S, n)) + 1j * rng.standard_normal((S, n))) * np.sqrt(10.0 ** -2.0 / 2.0)
+    k = np.arange(S)
+    a_d = np.exp(1j * np.pi * k * np.sin(np.deg2rad(10.0)))
+    a_i = np.exp(1j * np.pi * k * np.sin(np.deg2rad(-35.0)))
+    x_d, x_i = a_d[:, None] * d[None, :], a_i[:, None] * i[None, :]
+    g = 0.9 / np.abs(x_d + x_i + noise).max()
+    return ((g * (x_d + x_i + noise)).astype(np.complex64), (g * x_d).astype(np.complex64), (g * x_i).astype(np.complex64), a_d)
+
+
 def offset_bytes(n_samples, bias=0, seed=SEED):
     """2 n uint8 (I,Q) bytes, uniformly random: over all 256 values with bias = 0 (the converted stream has a mean near 0),
     or over [2 bias, 256) (a mean near 128 + bias: bias = 38 gives bytes around 166, a converted mean near 0.3)."""
