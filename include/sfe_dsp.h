@@ -888,6 +888,109 @@ int sfe_dsp_cov_process_stream(sfe_cov_t h, const void *d_in, size_t n_in, size_
 int sfe_dsp_cov_reset(sfe_cov_t h);
 int sfe_dsp_cov_destroy(sfe_cov_t h);
 
+/* ------------------------------------------------- adaptive beamforming weight solver (MVDR)
+ * The step between the covariance estimator and the beamformer, on the device: one regularised
+ * minimum-variance distortionless-response problem per (output row j of sfe_dsp_cov_*, band k),
+ * read where the estimator wrote it and written as the real matrix the beamformer multiplies by.
+ * With the B steering vectors taken as scan directions the per-beam power is the Capon spectrum.
+ * The law, on real matrices (n = 2S; G the n x n float32 Gram matrix; float32 on the device):
+ *   1. Read.  Only G[i][j] with i <= j is read; the lower triangle is taken as its mirror
+ *      (sfe_dsp_cov_* writes both with the same bits).
+ *   2. Structure.  widely_linear = 1: G^ = G.  widely_linear = 0 (the covariance C alone, the
+ *      pseudo-covariance ignored):
+ *          G^[2s][2t]   =  G^[2s+1][2t+1] = (G[2s][2t] + G[2s+1][2t+1]) / 2
+ *          G^[2s+1][2t] = -G^[2s][2t+1]   = (G[2s+1][2t] - G[2s][2t+1]) / 2
+ *      (half the realification of C: trace G^ = trace G in both modes).
+ *   3. Loading.  lambda = load_abs + load_rel * trace(G^) / n, G^[i][i] += lambda; in the linear
+ *      mode that is the complex diagonal loading load_rel * tr(C) / S.
+ *   4. Factor.  G^ = L L^T (Cholesky, no pivoting).  A pivot that is not finite or not > 0 fails
+ *      the whole problem.
+ *   5. Per beam b, a its steering vector (S complex values), u(a)[2s] = Re a_s, u(a)[2s+1] = Im a_s:
+ *      linear:  z = G^^-1 u(a), q = u(a)^T z; row 2b of R is z / q and row 2b+1 its rotation,
+ *          R[2b+1][2s] = -R[2b][2s+1],  R[2b+1][2s+1] = R[2b][2s]
+ *      -- exactly the matrix of a complex W with V absent (sfe_dsp_beam_plan) -- and
+ *      power_b = 2 / q = 1 / (a^H C_lambda^-1 a).
+ *      widely linear:  A2 = [u(a), u(ja)] (n x 2), Z = G^^-1 A2, Q = A2^T Z (2 x 2, Q[0][1] used
+ *      for both off-diagonal entries); rows 2b, 2b+1 of R are Q^-1 Z^T by the explicit 2 x 2
+ *      inverse and power_b = trace(Q^-1).  (S = 1: A2 is square, so the constraint alone fixes
+ *      R = A2^-1 -- the conventional beamformer of step 6, whatever G is -- and
+ *      power_b = trace(G^) / |a|^2; that closed form is what is computed, not the cancellation
+ *      the general formula would reach it through.)
+ *      A q or det Q that is not finite or not > 0 fails that beam.  In both modes R_b A2 = I_2
+ *      (unit response on the steering vector) at minimum output power.
+ *   6. Failure never produces a NaN weight: a failed beam gets the conventional beamformer
+ *      W = conj(a) / |a|^2, V = 0 -- formed on the host in float64 at create / set_steering,
+ *      rounded once and kept on the device, so its bits are defined -- and a quiet NaN power.
+ *      status of a problem: 0 all good, 1 the factorisation failed (every beam fell back), 2 the
+ *      factorisation succeeded and at least one beam fell back.
+ * Layouts.  Input: row j of band k at d_gram + k*in_stride + j*(2S)^2 floats (sfe_dsp_cov_*'s
+ * output layout; in_stride is its out_stride).  Output: R of row j, band k at
+ * d_real_matrix + j*out_stride + k*4BS; one row's block is [M][2B][2S], the layout of
+ * sfe_dsp_beam_plan's real_matrix.  power (float32, optional) at d_power + j*power_stride + k*B + b;
+ * status (int32, optional) at d_status + j*status_stride + k.  All 4-byte aligned.
+ * Shapes: 1 <= S <= 64, 1 <= B <= 64, 1 <= M <= 1024, M*B*S <= 2^20 (the beamformer's), every
+ * steering value finite and every steering vector non-zero, load_rel and load_abs finite and
+ * >= 0, widely_linear 0 or 1; anything else is SFE_EINVAL with a message that starts with
+ * "mvdr: ".
+ * Contracts about bits:
+ *   1. the same calls give the same bits on every run;
+ *   2. a problem's output depends on its own G, its band's steering and the loading only: never
+ *      on M, n_rows, j, addresses or strides; band k of an M-band handle gives the bits of a
+ *      one-band handle holding band k's steering;
+ *   3. beam b's two rows, its power and its fallback depend on a_b only: a B-beam handle
+ *      reproduces B one-beam handles;
+ *   4. in the linear mode R has the exact W-only structure of step 5;
+ *   5. nothing of the strict lower triangle of G is read;
+ *   6. a failed problem or beam gets the exact fallback bits and its status, its neighbours are
+ *      untouched;
+ *   7. nothing outside the rows written is touched.
+ * Not promised: the bits of the host plan or of LAPACK, equal bits between different S, equal
+ * bits under a permutation of the streams.
+ * Computed by csrc/mvdr.hip: one workgroup per problem, the loaded matrix factored in LDS as a
+ * packed triangle, the right-hand sides substituted eight lanes apiece. */
+typedef void *sfe_mvdr_t; /* opaque: M bands of B steering vectors over S streams, a mode, a loading */
+/* Host-only (no GPU): validates the arguments as above.  If gram != NULL it solves ONE row -- M
+ * matrices [M][2S][2S], band-major -- by the law in float64 and rounds once to float32 into
+ * real_matrix [M][2B][2S], power [M][B] and status [M], each of which may be NULL: the CPU
+ * fallback, and the reference of the device's values (not of its bits).
+ *   steering  [n_bands][n_beams][n_in] (re, im) float32 pairs */
+int sfe_dsp_mvdr_plan(int n_in, int n_beams, int n_bands, const float *steering, int widely_linear,
+                      float load_rel, float load_abs, const float *gram, float *real_matrix,
+                      float *power, int *status);
+/* The steering vectors are copied.  Arguments are checked before the device is touched:
+ * SFE_EINVAL for a bad one on any machine, SFE_ENODEV without a GPU. */
+int sfe_dsp_mvdr_create(const float *steering, int n_in, int n_beams, int n_bands,
+                        int widely_linear, float load_rel, float load_abs, int device,
+                        sfe_mvdr_t *out);
+/* New steering vectors of the handle's shape / a new loading (validated as at create), used from
+ * the next call on: the result then equals a fresh handle created with them, bit for bit.  May
+ * block until the handle's earlier calls have finished; never changes what an already enqueued
+ * call computes. */
+int sfe_dsp_mvdr_set_steering(sfe_mvdr_t h, const float *steering);
+int sfe_dsp_mvdr_set_loading(sfe_mvdr_t h, float load_rel, float load_abs);
+/* n_rows rows of every band, layouts as above.  *n_out = n_rows.  n_rows = 0 is a no-op;
+ * n_rows >= 2^31 / (2S)^2 is SFE_EINVAL.  out_stride < M*4BS, power_stride < M*B (with d_power)
+ * and status_stride < M (with d_status) are SFE_ERANGE; in_stride < n_rows*(2S)^2, a null d_gram
+ * or d_real_matrix, misaligned buffers and an output byte range that overlaps the input's are
+ * SFE_EINVAL; nothing is launched on a refusal.  Asynchronous on `stream`; allocates nothing,
+ * does not synchronise the host, carries no state (there is no reset).  A call on a stream under
+ * graph capture is SFE_ESTATE, nothing enqueued: sfe_dsp_mvdr_set_steering may replace the tables
+ * a captured call would have pinned. */
+int sfe_dsp_mvdr_process_stream(sfe_mvdr_t h, const void *d_gram, size_t n_rows, size_t in_stride,
+                                void *d_real_matrix, size_t out_stride, void *d_power,
+                                size_t power_stride, void *d_status, size_t status_stride,
+                                size_t *n_out, sfe_stream_t stream);
+/* Hands a device matrix to a live beamformer: enqueues on `stream` a small kernel that rewrites
+ * the handle's weight table from d_real_matrix, [M][2B][2S] float32 of the handle's own shape
+ * (one row block of sfe_dsp_mvdr_process_stream's output, or sfe_dsp_beam_plan's real_matrix).
+ * Beamformer calls enqueued later on the same stream use it, calls enqueued before it keep the
+ * old weights; calls on other streams are the caller's to order.  The host touches nothing and
+ * does not wait.  Values are not checked: a non-finite entry poisons as the beamformer documents.
+ * A handle that is not a live beamformer, a null or misaligned matrix: SFE_EINVAL; a stream under
+ * graph capture: SFE_ESTATE; nothing enqueued either way. */
+int sfe_dsp_mvdr_load_beam(sfe_beam_t beam, const float *d_real_matrix, sfe_stream_t stream);
+int sfe_dsp_mvdr_destroy(sfe_mvdr_t h);
+
 #ifdef __cplusplus
 }
 #endif

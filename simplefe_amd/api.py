@@ -910,6 +910,98 @@ class Cov(_Block):
         return np.ascontiguousarray(y)
 
 
+def _mvdr_steering(steering):
+    """(steering as (M, B, S) complex64, its float pointer): (B, S) is one band."""
+    a = np.asarray(steering, dtype=np.complex64)
+    a = np.ascontiguousarray(a[None] if a.ndim == 2 else a)
+    if a.ndim != 3:
+        raise ValueError("steering must be (n_beams, n_in) or (n_bands, n_beams, n_in) complex")
+    return a, a.view(np.float32).ctypes.data_as(C.POINTER(C.c_float))
+
+
+def mvdr_plan(steering, G=None, widely_linear=False, load_rel=0.0, load_abs=0.0):
+    """sfe_dsp_mvdr_plan (host only, no GPU): validates, and with G -- one row of Gram matrices, (M, 2S, 2S) or (2S, 2S)
+    float32 -- solves it by the law in float64: returns (R (M, 2B, 2S) float32, power (M, B) float32, status (M,) int32),
+    or None without G.  Raises SfeError on arguments the block refuses."""
+    a, pa = _mvdr_steering(steering)
+    M, B, S = a.shape
+    fp, L = C.POINTER(C.c_float), _l.load()
+    if G is None:
+        check(L.sfe_dsp_mvdr_plan(S, B, M, pa, int(widely_linear), load_rel, load_abs, None, None, None, None))
+        return None
+    G = np.ascontiguousarray(np.asarray(G, dtype=np.float32).reshape(M, 2 * S, 2 * S))
+    R, pw, st = np.empty((M, 2 * B, 2 * S), np.float32), np.empty((M, B), np.float32), np.empty(M, np.int32)
+    check(L.sfe_dsp_mvdr_plan(S, B, M, pa, int(widely_linear), load_rel, load_abs, G.ctypes.data_as(fp), R.ctypes.data_as(fp),
+                              pw.ctypes.data_as(fp), st.ctypes.data_as(C.POINTER(C.c_int))))
+    return R, pw, st
+
+
+class Mvdr(_Block):
+    """Adaptive beamforming weight solver (sfe_dsp_mvdr_*): per row of Cov's output and band, the regularised MVDR weights
+    of n_beams = B steering vectors over n_in = S streams as the real matrix Beam multiplies by, the per-beam output power
+    (the Capon spectrum) and a status.  steering is (M, B, S) complex, or (B, S) for one band."""
+    _prefix = "mvdr"
+
+    def __init__(self, steering, widely_linear=False, load_rel=0.0, load_abs=0.0, device=0):
+        a, pa = _mvdr_steering(steering)
+        self.n_bands, self.n_beams, self.n_in = (int(v) for v in a.shape)
+        self.widely_linear = bool(widely_linear)
+        self._create(pa, self.n_in, self.n_beams, self.n_bands, int(self.widely_linear), load_rel, load_abs, device)
+
+    def set_steering(self, steering):
+        """New steering vectors of the same shape, used from the next call on."""
+        a, pa = _mvdr_steering(steering)
+        if a.shape != (self.n_bands, self.n_beams, self.n_in):
+            raise ValueError("set_steering: shape %s for a handle of %s" % (a.shape, (self.n_bands, self.n_beams, self.n_in)))
+        check(self._fn("set_steering")(self._h, pa))
+
+    def set_loading(self, load_rel, load_abs=0.0):
+        """A new diagonal loading, used from the next call on."""
+        check(self._fn("set_loading")(self._h, load_rel, load_abs))
+
+    def process_stream(self, d_gram, n_rows, d_R, d_power=None, d_status=None, in_stride=None, out_stride=None, power_stride=None,
+                       status_stride=None, stream=None):
+        """d_*: DeviceArray or raw device pointers.  Row j of band k is read at d_gram + k*in_stride + j*(2S)^2 floats
+        (Cov's output; in_stride defaults to n_rows*(2S)^2); its matrix goes to d_R + j*out_stride + k*4BS, its powers to
+        d_power + j*power_stride + k*B, its status (int32) to d_status + j*status_stride + k; the output strides default
+        to one row's block.  Returns the number of rows solved."""
+        M, B, n2 = self.n_bands, self.n_beams, 2 * self.n_in
+        k = C.c_size_t(0)
+        check(self._fn("process_stream")(
+            self._h, self._ptr(d_gram), int(n_rows), int(n_rows) * n2 * n2 if in_stride is None else int(in_stride), self._ptr(d_R),
+            M * 2 * B * n2 if out_stride is None else int(out_stride), self._ptr(d_power), M * B if power_stride is None else int(power_stride),
+            self._ptr(d_status), M if status_stride is None else int(status_stride), C.byref(k), stream))
+        return k.value
+
+    def load_beam(self, beam, d_R, stream=None):
+        """Hand one row's matrices (M, 2B, 2S), on the device, to a live Beam of the same shape: Beam calls enqueued later
+        on `stream` use them.  No host copy and no wait."""
+        check(self._L.sfe_dsp_mvdr_load_beam(getattr(beam, "_h", beam), self._ptr(d_R), stream))
+
+    def reset(self):
+        raise AttributeError("Mvdr has no reset: it carries no state")
+
+    def solve(self, G):
+        """Host convenience, computed on the GPU: G is (M, rows, 2S, 2S) float32 (Cov.gram's result; (M, 2S, 2S) and, for
+        one band, (2S, 2S) are one row); returns (R (rows, M, 2B, 2S) float32, power (rows, M, B) float32,
+        status (rows, M) int32)."""
+        M, B, n2 = self.n_bands, self.n_beams, 2 * self.n_in
+        G = np.ascontiguousarray(np.asarray(G, dtype=np.float32).reshape(M, -1, n2, n2))
+        rows = G.shape[1]
+        d_g, d_R = DeviceArray.from_numpy(G.ravel()), DeviceArray(max(1, rows * M * 2 * B * n2))
+        d_p, d_s = DeviceArray(max(1, rows * M * B)), DeviceArray(max(1, rows * M))
+        try:
+            if rows:
+                self.process_stream(d_g, rows, d_R, d_p, d_s)
+            R = d_R.to_numpy(rows * M * 2 * B * n2).reshape(rows, M, 2 * B, n2)
+            pw = d_p.to_numpy(rows * M * B).reshape(rows, M, B)
+            st = d_s.to_numpy(rows * M).view(np.int32).reshape(rows, M)
+        finally:
+            for d in (d_g, d_R, d_p, d_s):
+                d.free()
+        return np.ascontiguousarray(R), np.ascontiguousarray(pw), np.ascontiguousarray(st)
+
+
 def rs_plan(state, upsample, n_in, out_len, rate):
     """Host-only replay of one process() call's time law (sfe_dsp_rs_plan).
     state: lib.TimeState (updated in place).  Returns (rel_pos int32[], mu float32[])."""

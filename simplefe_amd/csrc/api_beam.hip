@@ -6,6 +6,7 @@
 #include "host.h"
 #include "block.h"
 #include "beam.h"
+#include "beam_view.h"
 
 namespace sfe {
 namespace {
@@ -95,6 +96,15 @@ std::vector<float> beam_frags(int S, int B, int M, const float *w, const float *
 }
 
 }  // namespace
+
+bool beam_view(void *h, BeamView *out)
+{
+    Beam *p = as_beam(h);
+    if (!p) return false;
+    *out = BeamView{p->S, p->B, p->M, p->device, p->d_frag};
+    return true;
+}
+
 }  // namespace sfe
 
 using namespace sfe;

@@ -569,6 +569,103 @@ def cov_scene(S, n, seed):
     return ((g * (x_d + x_i + noise)).astype(np.complex64), (g * x_d).astype(np.complex64), (g * x_i).astype(np.complex64), a_d)
 
 
+def mvdr_scene_rectilinear(S, n, seed):
+    """cov_scene with the interferer replaced by sqrt(10^3) exp(0.7j) standard_normal(n): a real-valued interferer on a
+    fixed phase, 30 dB above the signal, whose pseudo-covariance is not zero -- what the widely-linear solver can use and
+    the linear one cannot.  Drawn from np.random.default_rng(seed) in cov_scene's order (signal, interferer, noise).
+    Returns (x, x_d, x_i, a_d) as cov_scene does."""
+    rng = np.random.default_rng(seed)
+    d = ((2.0 * rng.integers(0, 2, n) - 1.0) + 1j * (2.0 * rng.integers(0, 2, n) - 1.0)) / np.sqrt(2.0)
+    i = np.sqrt(10.0 ** 3.0) * np.exp(0.7j) * rng.standard_normal(n)
+    noise = (rng.standard_normal((S, n)) + 1j * rng.standard_normal((S, n))) * np.sqrt(10.0 ** -2.0 / 2.0)
+    k = np.arange(S)
+    a_d = np.exp(1j * np.pi * k * np.sin(np.deg2rad(10.0)))
+    a_i = np.exp(1j * np.pi * k * np.sin(np.deg2rad(-35.0)))
+    x_d, x_i = a_d[:, None] * d[None, :], a_i[:, None] * i[None, :]
+    g = 0.9 / np.abs(x_d + x_i + noise).max()
+    return ((g * (x_d + x_i + noise)).astype(np.complex64), (g * x_d).astype(np.complex64), (g * x_i).astype(np.complex64), a_d)
+
+
+def mvdr_loaded_matrix(G, widely_linear=False, load_rel=0.0, load_abs=0.0, dtype=np.float64):
+    """Steps 1-3 of the law of sfe_dsp_mvdr_* on one Gram matrix (2S, 2S): the upper triangle mirrored, the mode's
+    structure, the diagonal loading; in `dtype`."""
+    G = np.asarray(G).astype(dtype)
+    G = np.triu(G) + np.triu(G, 1).T
+    if not widely_linear:
+        h = (G[0::2, 0::2] + G[1::2, 1::2]) / dtype(2)
+        x = (G[1::2, 0::2] - G[0::2, 1::2]) / dtype(2)
+        G = np.empty_like(G)
+        G[0::2, 0::2], G[1::2, 1::2], G[1::2, 0::2], G[0::2, 1::2] = h, h, x, -x
+    n = G.shape[0]
+    lam = dtype(load_abs) + dtype(load_rel) * np.trace(G) / dtype(n)
+    return G + lam * np.eye(n, dtype=dtype)
+
+
+def mvdr_rhs(a, dtype=np.float64):
+    """A2 = [u(a), u(ja)], (2S, 2), of one steering vector."""
+    a = np.asarray(a, dtype=np.complex128).ravel()
+    A2 = np.empty((2 * a.size, 2), dtype=dtype)
+    A2[0::2, 0], A2[1::2, 0], A2[0::2, 1], A2[1::2, 1] = a.real, a.imag, -a.imag, a.real
+    return A2
+
+
+def mvdr_fallback(steering):
+    """The conventional beamformer W = conj(a) / |a|^2, V = 0 of every steering vector as Beam's real matrices,
+    (M, 2B, 2S) float64 ((B, S) steering is one band)."""
+    a = np.asarray(steering, dtype=np.complex64).astype(np.complex128)
+    a = a[None] if a.ndim == 2 else a
+    W = a.conj() / (np.abs(a) ** 2).sum(axis=2, keepdims=True)
+    R = np.empty((a.shape[0], 2 * a.shape[1], 2 * a.shape[2]))
+    R[:, 0::2, 0::2], R[:, 0::2, 1::2], R[:, 1::2, 0::2], R[:, 1::2, 1::2] = W.real, -W.imag, W.imag, W.real
+    return R
+
+
+def mvdr_reference(G, steering, widely_linear=False, load_rel=0.0, load_abs=0.0):
+    """The law of sfe_dsp_mvdr_* in float64 numpy, independent of the C code: G is (M, 2S, 2S) ((2S, 2S): one band),
+    steering (M, B, S) ((B, S)) complex, taken at complex64.  Returns (R (M, 2B, 2S), power (M, B), status (M,)) in
+    float64 / int: a failed beam holds the fallback rows and a NaN power."""
+    a = np.asarray(steering, dtype=np.complex64).astype(np.complex128)
+    a = a[None] if a.ndim == 2 else a
+    M, B, S = a.shape
+    G = np.asarray(G, dtype=np.float64).reshape(M, 2 * S, 2 * S)
+    R, power, status = mvdr_fallback(a), np.full((M, B), np.nan), np.zeros(M, dtype=np.int32)
+    for k in range(M):
+        Gh = mvdr_loaded_matrix(G[k], widely_linear, load_rel, load_abs)
+        try:
+            if not np.isfinite(Gh).all():
+                raise np.linalg.LinAlgError
+            L = np.linalg.cholesky(Gh)
+        except np.linalg.LinAlgError:
+            status[k] = 1
+            continue
+        for b in range(B):
+            A2 = mvdr_rhs(a[k, b])
+            if widely_linear and S == 1:        # A2 is square: R = A2^-1 (the fallback's own value), Q^-1 = A2^-1 G^ A2^-T
+                power[k, b] = np.trace(Gh) / (np.abs(a[k, b, 0]) ** 2)
+                continue
+            Z = np.linalg.solve(L.T, np.linalg.solve(L, A2))
+            if widely_linear:
+                Q = A2.T @ Z
+                q00, q01, q11 = Q[0, 0], Q[0, 1], Q[1, 1]
+                det = q00 * q11 - q01 * q01
+                if not (np.isfinite(det) and det > 0):
+                    status[k] = 2
+                    continue
+                R[k, 2 * b] = (q11 * Z[:, 0] - q01 * Z[:, 1]) / det
+                R[k, 2 * b + 1] = (q00 * Z[:, 1] - q01 * Z[:, 0]) / det
+                power[k, b] = (q00 + q11) / det
+            else:
+                q = A2[:, 0] @ Z[:, 0]
+                if not (np.isfinite(q) and q > 0):
+                    status[k] = 2
+                    continue
+                r = Z[:, 0] / q
+                R[k, 2 * b] = r
+                R[k, 2 * b + 1, 0::2], R[k, 2 * b + 1, 1::2] = -r[1::2], r[0::2]
+                power[k, b] = 2.0 / q
+    return R, power, status
+
+
 def offset_bytes(n_samples, bias=0, seed=SEED):
     """2 n uint8 (I,Q) bytes, uniformly random: over all 256 values with bias = 0 (the converted stream has a mean near 0),
     or over [2 bias, 256) (a mean near 128 + bias: bias = 38 gives bytes around 166, a converted mean near 0.3)."""
