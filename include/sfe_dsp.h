@@ -991,6 +991,130 @@ int sfe_dsp_mvdr_process_stream(sfe_mvdr_t h, const void *d_gram, size_t n_rows,
 int sfe_dsp_mvdr_load_beam(sfe_beam_t beam, const float *d_real_matrix, sfe_stream_t stream);
 int sfe_dsp_mvdr_destroy(sfe_mvdr_t h);
 
+/* --------------------------------- symmetric eigen-decomposition / MUSIC direction finder
+ * What stands at the head of the array chain, on the device: per (output row j of sfe_dsp_cov_*,
+ * band k) the eigenvalues of the Gram matrix (how many signals there are, and how strong), the
+ * MUSIC null spectrum of B scan steering vectors (where they are: the directions the weight
+ * solver above is then given), and the E leading eigenvectors as a real matrix the beamformer
+ * multiplies by (a signal-subspace beamformer).
+ * The law, on real matrices (n = 2S; G the n x n float32 Gram matrix; float32 on the device):
+ *   1. Read.  Only G[i][j] with i <= j is read; the lower triangle is taken as its mirror.
+ *   2. Structure.  widely_linear = 1: G^ = G.  widely_linear = 0 (the covariance C alone, the
+ *      pseudo-covariance ignored):
+ *          G^[2s][2t]   =  G^[2s+1][2t+1] = (G[2s][2t] + G[2s+1][2t+1]) / 2
+ *          G^[2s+1][2t] = -G^[2s][2t+1]   = (G[2s+1][2t] - G[2s][2t+1]) / 2
+ *      (half the realification of C: its eigenvalues are those of C, halved, each twice).  There
+ *      is no diagonal loading.
+ *   3. Decompose.  G^ = V diag(lambda) V^T by the two-sided cyclic Jacobi method: right for every
+ *      finite symmetric G^, singular (fewer snapshots than n) and indefinite ones included.  G^ is
+ *      first scaled by the power of two that brings its largest |entry| into [1, 2) -- exactly,
+ *      subnormal entries included; the eigenvalues are scaled back (exactly, unless the result
+ *      is subnormal: then rounded once).
+ *      Widely linear: the method runs on the n x n matrix A = G^.  A sweep is n - 1 steps of
+ *      n / 2 disjoint pairs in round-robin order, a function of n alone: step r pairs n - 1 with
+ *      r, and (r + a) mod (n - 1) with (r - a) mod (n - 1) for a = 1 .. n / 2 - 1.  A pair (p, q),
+ *      p < q, whose coupling A[p][q] is exactly zero is NOT rotated (a diagonal G^ comes out
+ *      exact); any other is rotated by theta = (A[q][q] - A[p][p]) / (2 A[p][q]),
+ *      t = sign(theta) / (|theta| + sqrt(theta^2 + 1)), c = 1 / sqrt(t^2 + 1), s = t c: A[p][p]
+ *      -= t A[p][q], A[q][q] += t A[p][q], the coupling set to exactly zero, every other entry of
+ *      rows and columns p, q and the accumulated V (which starts as I) rotated by (c, s).
+ *      Linear: G^ is the realification of the S x S Hermitian Z, Z[s][t] = G^[2s][2t] +
+ *      j G^[2s+1][2t], and the method runs on Z with the same order over S indices (an odd S gets
+ *      one more, whose row and column are zero: never rotated, never reported): the coupling
+ *      Z[p][q] = m w, |w| = 1, is annihilated by the unitary diag(1, conj w) times the rotation
+ *      above for the coupling m.  A complex eigenvector w stands for the two real ones u(w) and
+ *      u(jw) of G^, and its eigenvalue is written twice.  This is what makes the eigenvectors of a
+ *      repeated or clustered eigenvalue come out as exact (u(w), u(jw)) pairs; a real method on
+ *      G^ cannot promise that.
+ *      Either way the method stops after the first sweep in which no coupling it met exceeded
+ *      2^-27 in magnitude (after the scaling; float64 plan: 2^-56) -- that sweep's rotations are
+ *      still applied; a sweep that rotates nothing is one such -- and after 30 sweeps at the
+ *      latest.  Eigenvalues in descending algebraic order, equal ones in
+ *      the order of their position on the diagonal.  Each eigenvector is divided by its computed
+ *      norm and signed so that its largest-magnitude real component (the first of equals) is
+ *      positive.
+ *   4. Null spectrum.  The signal subspace is spanned by the first D = signal_dim eigenvectors
+ *      (REAL dimensions: a circular source takes 2, a rectilinear source takes 1 in the
+ *      widely-linear mode; D is even in the linear mode); N = V[:, D:].  Per beam b, a its steering
+ *      vector, u(a)[2s] = Re a_s, u(a)[2s+1] = Im a_s, A2 = [u(a), u(ja)]:
+ *      Q = (N^T A2)^T (N^T A2), 2 x 2, Q[0][1] used for both off-diagonal entries -- sums of
+ *      squares and products over the noise eigenvectors, so nothing cancels (linear mode: the
+ *      pair u(w), u(jw) contributes |w^H a|^2 to both diagonal entries and nothing beside them,
+ *      and that is how Q = q I is formed) -- and
+ *          null_b = max(lambda_min(Q), 0) / |a|^2,   in [0, 1] up to rounding,
+ *      lambda_min by the closed form (Q00 + Q11) / 2 - sqrt(((Q00 - Q11) / 2)^2 + Q01^2).
+ *      The MUSIC pseudo-spectrum is 1 / null_b: left to the caller, because null_b may be 0.
+ *   5. Eigen-beams.  The E = n_vec leading vectors as one [2E][2S] block per band, the layout of
+ *      sfe_dsp_beam_plan's real_matrix for E beams (sfe_dsp_mvdr_load_beam takes it as it is).
+ *      Widely linear: rows 2e, 2e+1 are eigenvectors 2e, 2e+1.  Linear: row 2e is eigenvector 2e
+ *      (u(w) of the e-th complex eigenvector) and row 2e+1 its exact rotation u(jw),
+ *      R[2e+1][2s] = -R[2e][2s+1], R[2e+1][2s+1] = R[2e][2s]: the matrix of the complex W = w^H
+ *      with V absent.
+ *   6. Failure never writes a NaN weight.  A problem fails if an entry of G^ (linear mode: or the
+ *      sum or difference of step 2 before its halving) is not finite in float32, or at the sweep
+ *      limit: status 1, its eigenvalues and null spectrum quiet NaN, its eigen-beams the
+ *      selection matrix of streams 0 .. E-1 (R[r][r] = 1, zero elsewhere).  Status 0 otherwise.
+ * Layouts.  Input as sfe_dsp_mvdr_*: row j of band k at d_gram + k*in_stride + j*(2S)^2 floats.
+ * Outputs: values [n_rows][M][2S] at d_values + j*values_stride + k*2S; null [n_rows][M][B] at
+ * d_null + j*null_stride + k*B + b; vectors [n_rows][M][2E][2S] at d_vectors + j*vectors_stride +
+ * k*4ES; status (int32) at d_status + j*status_stride + k.  null, vectors and status may each be
+ * NULL.  All 4-byte aligned.
+ * Shapes: 1 <= S <= 64, 0 <= B <= 64, 0 <= E <= S, 1 <= M <= 1024, M*max(B,E,1)*S <= 2^20,
+ * 0 <= D < 2S (even in the linear mode), every steering value finite and every steering vector
+ * non-zero (steering may be NULL with B = 0), widely_linear 0 or 1; anything else is SFE_EINVAL
+ * with a message that starts with "eig: ".
+ * Contracts about bits:
+ *   1. the same calls give the same bits on every run;
+ *   2. a problem's output depends on its own G, its band's steering and the parameters only:
+ *      never on M, n_rows, j, addresses or strides; band k of an M-band handle gives the bits of
+ *      a one-band handle holding band k's steering;
+ *   3. null_b depends on a_b only: a B-beam handle reproduces B one-beam handles;
+ *   4. nothing of the strict lower triangle of G is read;
+ *   5. in the linear mode the eigen-beams have the exact W-only structure of step 5;
+ *   6. a diagonal G^ of distinct powers of two, negative ones included, gives its exact sorted
+ *      eigenvalues, exact unit vectors, and exact 0 / 1 null values on selection steering vectors;
+ *   7. a failed problem gets exactly the fallback bits, its neighbours are untouched;
+ *   8. nothing outside the rows written is touched.
+ * Not promised: the bits of the host plan or of LAPACK, equal bits between different S, the basis
+ * inside a degenerate eigenvalue's plane (in the linear mode: the phase of a complex
+ * eigenvector).
+ * Computed by csrc/eig.hip: one workgroup per problem, the matrix and V^T in LDS (up to 131 KB
+ * widely linear, 67 KB linear, taken per launch), two barriers per step. */
+typedef void *sfe_eig_t; /* opaque: M bands of B scan vectors over S streams, a mode, D and E */
+/* Host-only (no GPU): validates the arguments as above.  If gram != NULL it decomposes ONE row --
+ * M matrices [M][2S][2S], band-major -- by the law in float64 and rounds once to float32 into
+ * values [M][2S] (required then), null_spectrum [M][B], vectors [M][2E][2S] and status [M], each
+ * of which may be NULL: the CPU fallback, and the reference of the device's values (not of its
+ * bits).
+ *   steering  [n_bands][n_beams][n_in] (re, im) float32 pairs */
+int sfe_dsp_eig_plan(int n_in, int n_beams, int n_vec, int n_bands, const float *steering,
+                     int widely_linear, int signal_dim, const float *gram, float *values,
+                     float *null_spectrum, float *vectors, int *status);
+/* The steering vectors are copied.  Arguments are checked before the device is touched:
+ * SFE_EINVAL for a bad one on any machine, SFE_ENODEV without a GPU. */
+int sfe_dsp_eig_create(const float *steering, int n_in, int n_beams, int n_vec, int n_bands,
+                       int widely_linear, int signal_dim, int device, sfe_eig_t *out);
+/* New scan vectors of the handle's shape / a new signal dimension (validated as at create), used
+ * from the next call on: the result then equals a fresh handle created with them, bit for bit.
+ * set_steering may block until the handle's earlier calls have finished; neither changes what an
+ * already enqueued call computes. */
+int sfe_dsp_eig_set_steering(sfe_eig_t h, const float *steering);
+int sfe_dsp_eig_set_signal_dim(sfe_eig_t h, int signal_dim);
+/* n_rows rows of every band, layouts as above.  *n_out = n_rows.  n_rows = 0 is a no-op;
+ * n_rows >= 2^31 / (2S)^2 is SFE_EINVAL.  values_stride < M*2S, null_stride < M*B (with d_null),
+ * vectors_stride < M*4ES (with d_vectors) and status_stride < M (with d_status) are SFE_ERANGE;
+ * in_stride < n_rows*(2S)^2, a null d_gram or d_values, misaligned buffers and an output byte
+ * range that overlaps the input's are SFE_EINVAL; nothing is launched on a refusal.  Asynchronous
+ * on `stream`; allocates nothing, does not synchronise the host, carries no state (there is no
+ * reset).  A call on a stream under graph capture is SFE_ESTATE, nothing enqueued:
+ * sfe_dsp_eig_set_steering may replace the table a captured call would have pinned. */
+int sfe_dsp_eig_process_stream(sfe_eig_t h, const void *d_gram, size_t n_rows, size_t in_stride,
+                               void *d_values, size_t values_stride, void *d_null,
+                               size_t null_stride, void *d_vectors, size_t vectors_stride,
+                               void *d_status, size_t status_stride, size_t *n_out,
+                               sfe_stream_t stream);
+int sfe_dsp_eig_destroy(sfe_eig_t h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1002,6 +1002,99 @@ class Mvdr(_Block):
         return np.ascontiguousarray(R), np.ascontiguousarray(pw), np.ascontiguousarray(st)
 
 
+def _eig_steering(steering, n_in, n_bands):
+    """(steering as (M, B, S) complex64 -- None: (n_bands, 0, n_in) -- and its float pointer, null without beams)."""
+    if steering is None:
+        return np.zeros((int(n_bands), 0, int(n_in)), np.complex64), None
+    return _mvdr_steering(steering)
+
+
+def eig_plan(steering, G=None, widely_linear=False, signal_dim=0, n_vec=0, n_in=None, n_bands=1):
+    """sfe_dsp_eig_plan (host only, no GPU): validates, and with G -- one row of Gram matrices, (M, 2S, 2S) or (2S, 2S)
+    float32 -- decomposes it by the law in float64: returns (values (M, 2S), null (M, B), vectors (M, 2E, 2S), all
+    float32, status (M,) int32), or None without G.  steering is (M, B, S) or (B, S) complex, or None (no beams: n_in and
+    n_bands give the shape).  Raises SfeError on arguments the block refuses."""
+    a, pa = _eig_steering(steering, n_in, n_bands)
+    M, B, S = a.shape
+    fp, L = C.POINTER(C.c_float), _l.load()
+    if G is None:
+        check(L.sfe_dsp_eig_plan(S, B, int(n_vec), M, pa, int(widely_linear), int(signal_dim), None, None, None, None, None))
+        return None
+    G = np.ascontiguousarray(np.asarray(G, dtype=np.float32).reshape(M, 2 * S, 2 * S))
+    E = max(int(n_vec), 0)
+    val, nul = np.empty((M, 2 * S), np.float32), np.empty((M, B), np.float32)
+    vec, st = np.empty((M, 2 * E, 2 * S), np.float32), np.empty(M, np.int32)
+    check(L.sfe_dsp_eig_plan(S, B, int(n_vec), M, pa, int(widely_linear), int(signal_dim), G.ctypes.data_as(fp), val.ctypes.data_as(fp),
+                             nul.ctypes.data_as(fp), vec.ctypes.data_as(fp), st.ctypes.data_as(C.POINTER(C.c_int))))
+    return val, nul, vec, st
+
+
+class Eig(_Block):
+    """Symmetric eigen-decomposition / MUSIC direction finder (sfe_dsp_eig_*): per row of Cov's output and band, the
+    eigenvalues of the Gram matrix (descending), the MUSIC null spectrum of n_beams = B scan steering vectors against the
+    noise subspace left by signal_dim real dimensions, and the n_vec = E leading eigenvectors as the real matrix Beam
+    multiplies by.  steering is (M, B, S) complex, (B, S) for one band, or None (no beams: n_in and n_bands give the shape)."""
+    _prefix = "eig"
+
+    def __init__(self, steering, widely_linear=False, signal_dim=0, n_vec=0, n_in=None, n_bands=1, device=0):
+        a, pa = _eig_steering(steering, n_in, n_bands)
+        self.n_bands, self.n_beams, self.n_in = (int(v) for v in a.shape)
+        self.widely_linear, self.n_vec = bool(widely_linear), int(n_vec)
+        self._create(pa, self.n_in, self.n_beams, self.n_vec, self.n_bands, int(self.widely_linear), int(signal_dim), device)
+
+    def set_steering(self, steering):
+        """New scan vectors of the same shape, used from the next call on."""
+        a, pa = _mvdr_steering(steering)
+        if a.shape != (self.n_bands, self.n_beams, self.n_in):
+            raise ValueError("set_steering: shape %s for a handle of %s" % (a.shape, (self.n_bands, self.n_beams, self.n_in)))
+        check(self._fn("set_steering")(self._h, pa))
+
+    def set_signal_dim(self, signal_dim):
+        """A new signal-subspace dimension, used from the next call on."""
+        check(self._fn("set_signal_dim")(self._h, int(signal_dim)))
+
+    def process_stream(self, d_gram, n_rows, d_values, d_null=None, d_vectors=None, d_status=None, in_stride=None, values_stride=None,
+                       null_stride=None, vectors_stride=None, status_stride=None, stream=None):
+        """d_*: DeviceArray or raw device pointers.  Row j of band k is read at d_gram + k*in_stride + j*(2S)^2 floats
+        (Cov's output; in_stride defaults to n_rows*(2S)^2); its eigenvalues go to d_values + j*values_stride + k*2S, its
+        null spectrum to d_null + j*null_stride + k*B, its eigen-beams to d_vectors + j*vectors_stride + k*4ES, its status
+        (int32) to d_status + j*status_stride + k; the output strides default to one row's block.  Returns the number of
+        rows decomposed."""
+        M, B, E, n2 = self.n_bands, self.n_beams, self.n_vec, 2 * self.n_in
+        k = C.c_size_t(0)
+        check(self._fn("process_stream")(
+            self._h, self._ptr(d_gram), int(n_rows), int(n_rows) * n2 * n2 if in_stride is None else int(in_stride),
+            self._ptr(d_values), M * n2 if values_stride is None else int(values_stride),
+            self._ptr(d_null), M * B if null_stride is None else int(null_stride),
+            self._ptr(d_vectors), M * 2 * E * n2 if vectors_stride is None else int(vectors_stride),
+            self._ptr(d_status), M if status_stride is None else int(status_stride), C.byref(k), stream))
+        return k.value
+
+    def reset(self):
+        raise AttributeError("Eig has no reset: it carries no state")
+
+    def decompose(self, G):
+        """Host convenience, computed on the GPU: G is (M, rows, 2S, 2S) float32 (Cov.gram's result; (M, 2S, 2S) and, for
+        one band, (2S, 2S) are one row); returns (values (rows, M, 2S), null (rows, M, B), vectors (rows, M, 2E, 2S), all
+        float32, status (rows, M) int32)."""
+        M, B, E, n2 = self.n_bands, self.n_beams, self.n_vec, 2 * self.n_in
+        G = np.ascontiguousarray(np.asarray(G, dtype=np.float32).reshape(M, -1, n2, n2))
+        rows = G.shape[1]
+        d_g, d_v = DeviceArray.from_numpy(G.ravel()), DeviceArray(max(1, rows * M * n2))
+        d_n, d_e, d_s = DeviceArray(max(1, rows * M * B)), DeviceArray(max(1, rows * M * 2 * E * n2)), DeviceArray(max(1, rows * M))
+        try:
+            if rows:
+                self.process_stream(d_g, rows, d_v, d_n, d_e, d_s)
+            val = d_v.to_numpy(rows * M * n2).reshape(rows, M, n2)
+            nul = d_n.to_numpy(rows * M * B).reshape(rows, M, B)
+            vec = d_e.to_numpy(rows * M * 2 * E * n2).reshape(rows, M, 2 * E, n2)
+            st = d_s.to_numpy(rows * M).view(np.int32).reshape(rows, M)
+        finally:
+            for d in (d_g, d_v, d_n, d_e, d_s):
+                d.free()
+        return np.ascontiguousarray(val), np.ascontiguousarray(nul), np.ascontiguousarray(vec), np.ascontiguousarray(st)
+
+
 def rs_plan(state, upsample, n_in, out_len, rate):
     """Host-only replay of one process() call's time law (sfe_dsp_rs_plan).
     state: lib.TimeState (updated in place).  Returns (rel_pos int32[], mu float32[])."""

@@ -161,6 +161,12 @@ SIGNATURES = {
     "sfe_dsp_mvdr_process_stream": (i32, [vp, vp, sz, sz, vp, sz, vp, sz, vp, sz, C.POINTER(sz), vp]),
     "sfe_dsp_mvdr_load_beam": (i32, [vp, vp, vp]),
     "sfe_dsp_mvdr_destroy": (i32, [vp]),
+    "sfe_dsp_eig_plan": (i32, [i32, i32, i32, i32, fp, i32, i32, fp, fp, fp, fp, C.POINTER(i32)]),
+    "sfe_dsp_eig_create": (i32, [fp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
+    "sfe_dsp_eig_set_steering": (i32, [vp, fp]),
+    "sfe_dsp_eig_set_signal_dim": (i32, [vp, i32]),
+    "sfe_dsp_eig_process_stream": (i32, [vp, vp, sz, sz, vp, sz, vp, sz, vp, sz, vp, sz, C.POINTER(sz), vp]),
+    "sfe_dsp_eig_destroy": (i32, [vp]),
 }
 
 # the diagnostic library only (simplefe_amd/csrc/diag/sfe_dsp_diag.h; scripts/ load it by pointing LIB_PATH at it): bound when present

@@ -666,6 +666,50 @@ def mvdr_reference(G, steering, widely_linear=False, load_rel=0.0, load_abs=0.0)
     return R, power, status
 
 
+def eig_reference(G, steering, widely_linear=False, signal_dim=0, n_vec=0):
+    """The law of sfe_dsp_eig_* in float64 numpy (numpy.linalg.eigh), independent of the C code: G is (M, 2S, 2S)
+    ((2S, 2S): one band), steering (M, B, S) ((B, S)) complex, taken at complex64, or None (no beams).  Returns
+    (values (M, 2S), null (M, B), vectors (M, 2 n_vec, 2S), status (M,), V (M, 2S, 2S)): V holds every eigenvector as a
+    column, in the order of the values, signed by the law's rule.  A failed problem (a non-finite G^) holds NaN values
+    and null spectrum and the selection matrix."""
+    G = np.asarray(G, dtype=np.float64)
+    G = G[None] if G.ndim == 2 else G
+    M, n = G.shape[0], G.shape[1]
+    S, E, D = n // 2, int(n_vec), int(signal_dim)
+    if steering is None:
+        a = np.zeros((M, 0, S), np.complex128)
+    else:
+        a = np.asarray(steering, dtype=np.complex64).astype(np.complex128)
+        a = a[None] if a.ndim == 2 else a
+    B = a.shape[1]
+    values, null, status = np.full((M, n), np.nan), np.full((M, B), np.nan), np.zeros(M, dtype=np.int32)
+    vectors, Vall = np.tile(np.eye(2 * E, n), (M, 1, 1)), np.tile(np.eye(n), (M, 1, 1))
+    for k in range(M):
+        with np.errstate(invalid="ignore", over="ignore"):
+            Gh = mvdr_loaded_matrix(G[k], widely_linear)
+        if not np.isfinite(Gh.astype(np.float32)).all():
+            status[k] = 1
+            continue
+        lam, V = np.linalg.eigh(Gh)
+        lam, V = lam[::-1], V[:, ::-1]
+        lead = np.abs(V).argmax(axis=0)
+        V = V * np.where(V[lead, np.arange(n)] < 0, -1.0, 1.0)[None, :]
+        values[k], Vall[k] = lam, V
+        if widely_linear:
+            vectors[k] = V[:, :2 * E].T
+        else:
+            r = V[:, 0:2 * E:2].T
+            vectors[k, 0::2] = r
+            vectors[k, 1::2, 0::2], vectors[k, 1::2, 1::2] = -r[:, 1::2], r[:, 0::2]
+        N = V[:, D:]
+        for b in range(B):
+            P = N.T @ mvdr_rhs(a[k, b])
+            q00, q11, q01 = P[:, 0] @ P[:, 0], P[:, 1] @ P[:, 1], P[:, 0] @ P[:, 1]
+            lmin = 0.5 * (q00 + q11) - np.hypot(0.5 * (q00 - q11), q01)
+            null[k, b] = max(lmin, 0.0) / (np.abs(a[k, b]) ** 2).sum()
+    return values, null, vectors, status, Vall
+
+
 def offset_bytes(n_samples, bias=0, seed=SEED):
     """2 n uint8 (I,Q) bytes, uniformly random: over all 256 values with bias = 0 (the converted stream has a mean near 0),
     or over [2 bias, 256) (a mean near 128 + bias: bias = 38 gives bytes around 166, a converted mean near 0.3)."""
