@@ -1115,6 +1115,99 @@ int sfe_dsp_eig_process_stream(sfe_eig_t h, const void *d_gram, size_t n_rows, s
                                sfe_stream_t stream);
 int sfe_dsp_eig_destroy(sfe_eig_t h);
 
+/* ------------------------------------------------- feed-forward burst demodulator
+ * What follows the correlator: for each burst a window of one stream, whose start offset lies in
+ * device memory where sfe_dsp_corr_* wrote it, becomes N symbol-rate samples that are timing-,
+ * frequency-, phase- and amplitude-corrected, with a record of the estimates and a status.  Nothing
+ * is carried from burst to burst; no host read or copy lies between the two blocks.
+ * Shapes: sps (samples per symbol) in [4, 64]; n_sym = N in [2, 4096], the preamble included; the
+ * preamble p[0..Lp), 2 <= Lp <= N, every value finite, E_p = sum |p|^2 (float64, rounded once) > 0;
+ * lag = D in [1, Lp); timing_mode 0 (estimate) or 1 (tau = 0); min_gate finite; n_streams >= 1;
+ * anything else is SFE_EINVAL with a message that starts with "burst: ".
+ * Burst b of stream s starts at o = start_base + b*start_step + idx (signed 64-bit), idx the uint32
+ * at d_idx + s*idx_stride + b (0 with d_idx NULL).  Behind a one-template correlator of block B and
+ * template length L: d_idx = its d_peak_idx, start_step = B, start_base = -(L-1) + the index of the
+ * correlator's block 0 within the input buffer, d_gate = its d_peak_val.  With x stream s, float32
+ * except where float64 is named:
+ *   0  gate, range   with d_gate, a burst whose gate value is not >= min_gate (a NaN is not) has
+ *                    status 2; a burst whose reach [o - sps, o + (N+1) sps) is not inside [0, n_in)
+ *                    has status 3.  Neither reads a sample.
+ *   1  timing        c = sum_{i < N sps} |x[o+i]|^2 w[i mod sps], w[r] = exp(-j 2 pi r / sps) from a
+ *                    table made in float64 and rounded once; tau = -sps arg(c) / (2 pi) samples, in
+ *                    (-sps/2, sps/2] (Oerder-Meyr).  timing_mode 1: tau = 0.
+ *   2  interpolate   m = floor(tau), mu = tau - m, cubic Lagrange once per burst:
+ *                    L-1 = -mu(mu-1)(mu-2)/6, L0 = (mu+1)(mu-1)(mu-2)/2, L1 = -(mu+1)mu(mu-2)/2,
+ *                    L2 = (mu+1)mu(mu-1)/6;  y[k] = sum_{q=-1..2} L_q x[o + k sps + m + q], k < N,
+ *                    an fmaf chain from +0 in that order of q, per component.
+ *   3  carrier       z[k] = y[k] conj(p[k]), k < Lp;  R = sum_{k < Lp-D} z[k+D] conj(z[k]);
+ *                    f = arg(R) / (2 pi D) turns per symbol, |f| <= 1/(2D);
+ *                    S = sum_{k < Lp} z[k] exp(-j 2 pi f k);  theta = arg(S) / (2 pi) turns;
+ *                    a = |S| / E_p.
+ *   4  phase         wherever exp(-j 2 pi (theta + f k)) is needed (in S with theta = 0, and in 5)
+ *                    the turn count is formed in float64 from the float32 f and theta, reduced to
+ *                    [-1/2, 1/2] by subtracting rint, and only then taken to float32.
+ *   5  output        y^[k] = y[k] exp(-j 2 pi (theta + f k)) / a, k < N, cf32 at
+ *                    d_out + (s*n_bursts + b)*out_stride + k.  The record, 8 float32 at
+ *                    d_rec + (s*n_bursts + b)*8: tau, f, theta, a, q = |S|^2 / (E_p sum_{k<Lp} |y[k]|^2),
+ *                    evm = sum_{k<Lp} |y^[k] - p[k]|^2 / E_p, +0, +0.  The status, int32 at
+ *                    d_status + s*status_stride + b: 0.
+ *   6  failure       a c, R or S that is zero or not finite, an a that is not > 0 and finite, or a
+ *                    non-finite sample in the reach: status 1.  A burst of status 1, 2 or 3 gets N
+ *                    symbols of +0 and a record of quiet NaN whose words 6 and 7 are still +0.
+ * Promised about bits: the same calls give the same bits on every run (no floating-point atomics); a
+ * burst's output depends on its reach, the preamble and the parameters only -- never on b, s,
+ * n_bursts, addresses, strides or whether windows overlap, which they may; u8 input gives the bits
+ * of the cf32 path on the converted samples; with timing_mode 1, p all ones and x = 1+0j constant,
+ * f = theta = +0, a = q = 1, evm = 0 and y^ is exactly 1+0j; nothing outside the slots named is
+ * written.  Not promised: the order of the three sums (fixed per (sps, N, Lp, D)), equal bits
+ * between shapes, the bits of the host plan. */
+typedef void *sfe_burst_t;  /* opaque: one demodulator over n_streams streams */
+/* Host-only (no GPU): validates what create validates (one stream).  With x != NULL -- n_in cf32
+ * samples of ONE stream -- it runs n_bursts bursts by the law in float64 (idx [n_bursts] and gate
+ * [n_bursts] host arrays, either may be NULL), each estimate rounded to float32 where the law hands
+ * it on, and rounds once to float32 into symbols [n_bursts][N] cf32 (required then), record
+ * [n_bursts][8] and status [n_bursts] (each may be NULL): the CPU fallback, and the reference of the
+ * device's values (not of its bits).  With given != NULL, [n_bursts][8] float32, steps 1 and 3 are
+ * skipped and tau, f, theta, a are words 0..3 of given; a burst whose given words are not usable
+ * (not finite, |tau| > sps/2, a not > 0) has status 1.  n_in or n_bursts >= 2^31, or a
+ * start_base + b*start_step beyond +-(2^63 - 2^33) for some burst, is SFE_EINVAL. */
+int sfe_dsp_burst_plan(const float *preamble, int n_pre, int sps, int n_sym, int lag,
+                       int timing_mode, float min_gate, const float *x, size_t n_in,
+                       const uint32_t *idx, const float *gate, size_t n_bursts, int64_t start_base,
+                       int64_t start_step, const float *given, float *symbols, float *record,
+                       int *status);
+/*   preamble  [n_pre] complex float32 as (re, im) pairs (copied)
+ * Arguments are checked before the device is touched: SFE_EINVAL for a bad one on any machine,
+ * SFE_ENODEV without a GPU. */
+int sfe_dsp_burst_create(const float *preamble, int n_pre, int sps, int n_sym, int lag,
+                         int timing_mode, float min_gate, int n_streams, int device,
+                         sfe_burst_t *out);
+/* SFE_FMT_F32 (cf32 input, 8-byte aligned) or SFE_FMT_U8 ((I,Q) byte pairs, 2-byte aligned,
+ * converted (b-128)*(1/127) on load exactly as sfe_dsp_rx_u8_to_f32); any other format is
+ * SFE_EINVAL. */
+int sfe_dsp_burst_set_input_format(sfe_burst_t h, int fmt);
+/* A new min_gate (finite), used from the next call on; an enqueued call keeps the one it took. */
+int sfe_dsp_burst_set_gate(sfe_burst_t h, float min_gate);
+/* n_bursts bursts of every stream: stream s at d_in + s*in_stride (samples of the input format),
+ * n_in samples long; the other layouts as above.  d_idx, d_gate, d_rec and d_status may each be
+ * NULL.  *n_out = n_bursts; n_bursts = 0 is a no-op.  out_stride < N, or status_stride < n_bursts
+ * with d_status, is SFE_ERANGE; a null d_in or d_out, misaligned buffers (cf32 8 bytes, u8 pairs 2,
+ * the rest 4), in_stride < n_in with more than one stream, n_in >= 2^31, n_streams*n_bursts >= 2^31,
+ * a start_base + b*start_step beyond +-(2^63 - 2^33) for some burst, a stride that takes a
+ * buffer's byte range to 2^62
+ * and any output byte range that overlaps the input's, the index table's, the gate table's or
+ * another output's are SFE_EINVAL; nothing is launched on a refusal.  Asynchronous on `stream`;
+ * allocates nothing, does not synchronise the host, carries no state (there is no reset).  A call on
+ * a stream under graph capture is SFE_ESTATE, nothing enqueued: sfe_dsp_burst_set_gate may change
+ * what a captured call would have pinned. */
+int sfe_dsp_burst_process_stream(sfe_burst_t h, const void *d_in, size_t n_in, size_t in_stride,
+                                 const void *d_idx, size_t idx_stride, const void *d_gate,
+                                 size_t gate_stride, size_t n_bursts, int64_t start_base,
+                                 int64_t start_step, void *d_out, size_t out_stride, void *d_rec,
+                                 void *d_status, size_t status_stride, size_t *n_out,
+                                 sfe_stream_t stream);
+int sfe_dsp_burst_destroy(sfe_burst_t h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1095,6 +1095,119 @@ class Eig(_Block):
         return np.ascontiguousarray(val), np.ascontiguousarray(nul), np.ascontiguousarray(vec), np.ascontiguousarray(st)
 
 
+def _burst_preamble(preamble):
+    """(preamble as a 1-D complex64 array, its float pointer)."""
+    p = np.ascontiguousarray(np.asarray(preamble, dtype=np.complex64).ravel())
+    return p, p.view(np.float32).ctypes.data_as(C.POINTER(C.c_float))
+
+
+def burst_plan(preamble, sps, n_sym, lag, timing_mode=0, min_gate=0.0, x=None, idx=None, gate=None, n_bursts=None, start_base=0,
+               start_step=0, given=None):
+    """sfe_dsp_burst_plan (host only, no GPU): validates, and with x -- the complex samples of ONE stream -- demodulates
+    n_bursts bursts by the law in float64: returns (symbols (n_bursts, n_sym) complex64, record (n_bursts, 8) float32,
+    status (n_bursts,) int32), or None without x.  idx (uint32) and gate (float32) are host arrays of n_bursts entries or
+    None; n_bursts defaults to len(idx), else 1.  given, (n_bursts, 8) float32: tau, f, theta, a are taken from it and the
+    estimators are skipped.  Raises SfeError on arguments the block refuses."""
+    p, pp = _burst_preamble(preamble)
+    fp, L = C.POINTER(C.c_float), _l.load()
+    head = (pp, p.size, int(sps), int(n_sym), int(lag), int(timing_mode), float(min_gate))
+    if x is None:
+        check(L.sfe_dsp_burst_plan(*head, None, 0, None, None, 0, 0, 0, None, None, None, None))
+        return None
+    x = np.ascontiguousarray(np.asarray(x, dtype=np.complex64).ravel())
+    if idx is not None:
+        idx = np.ascontiguousarray(idx, dtype=np.uint32).ravel()
+    nb = int(n_bursts) if n_bursts is not None else (idx.size if idx is not None else 1)
+    if gate is not None:
+        gate = np.ascontiguousarray(gate, dtype=np.float32).ravel()
+    if given is not None:
+        given = np.ascontiguousarray(given, dtype=np.float32).reshape(nb, 8)
+    for name, v in (("idx", idx), ("gate", gate)):
+        if v is not None and v.size != nb:
+            raise ValueError("burst_plan: %s has %d entries for %d bursts" % (name, v.size, nb))
+    N = max(int(n_sym), 0)
+    sym, rec, st = np.empty((nb, N), np.complex64), np.empty((nb, 8), np.float32), np.empty(nb, np.int32)
+    check(L.sfe_dsp_burst_plan(*head, x.view(np.float32).ctypes.data_as(fp), x.size,
+                               None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_uint32)),
+                               None if gate is None else gate.ctypes.data_as(fp), nb, int(start_base), int(start_step),
+                               None if given is None else given.ctypes.data_as(fp), sym.view(np.float32).ctypes.data_as(fp),
+                               rec.ctypes.data_as(fp), st.ctypes.data_as(C.POINTER(C.c_int))))
+    return sym, rec, st
+
+
+class Burst(_Block):
+    """Feed-forward burst demodulator (sfe_dsp_burst_*): per burst, a window of one stream that starts where the
+    correlator's peak says becomes n_sym symbol-rate samples -- timing (Oerder-Meyr), carrier frequency and phase
+    (data-aided on the preamble) and amplitude corrected -- with a record (tau, f, theta, a, q, evm, 0, 0) and a status."""
+    _prefix = "burst"
+
+    def __init__(self, preamble, sps, n_sym, lag, timing_mode=0, min_gate=0.0, n_streams=1, device=0):
+        p, pp = _burst_preamble(preamble)
+        self.sps, self.n_sym, self.n_pre, self.lag = int(sps), int(n_sym), p.size, int(lag)
+        self.timing_mode, self.n_streams = int(timing_mode), int(n_streams)
+        self.in_u8 = False
+        self._create(pp, p.size, self.sps, self.n_sym, self.lag, self.timing_mode, float(min_gate), self.n_streams, device)
+
+    def set_input_format(self, fmt):
+        """lib.FMT_F32 (cf32) or lib.FMT_U8 ((I,Q) byte pairs, converted on load)."""
+        self._set_input_format(fmt)
+
+    def set_gate(self, min_gate):
+        """A new min_gate, used from the next call on."""
+        check(self._fn("set_gate")(self._h, float(min_gate)))
+
+    def process_stream(self, d_in, n_in, n_bursts, d_out, d_idx=None, d_gate=None, d_rec=None, d_status=None, start_base=0, start_step=0,
+                       in_stride=None, idx_stride=None, gate_stride=None, out_stride=None, status_stride=None, stream=None):
+        """d_*: DeviceArray or raw device pointers.  Burst b of stream s starts at start_base + b*start_step + the uint32
+        at d_idx + s*idx_stride + b (0 without d_idx) of the n_in samples at d_in + s*in_stride, is gated by the float32 at
+        d_gate + s*gate_stride + b, and writes n_sym cf32 symbols at d_out + (s*n_bursts + b)*out_stride, 8 float32 at
+        d_rec + (s*n_bursts + b)*8 and an int32 at d_status + s*status_stride + b.  in_stride defaults to n_in, out_stride
+        to n_sym and the other strides to n_bursts.  Returns n_bursts."""
+        nb = int(n_bursts)
+        k = C.c_size_t(0)
+        check(self._fn("process_stream")(
+            self._h, self._ptr(d_in), int(n_in), int(n_in) if in_stride is None else int(in_stride),
+            self._ptr(d_idx), nb if idx_stride is None else int(idx_stride), self._ptr(d_gate), nb if gate_stride is None else int(gate_stride),
+            nb, int(start_base), int(start_step), self._ptr(d_out), self.n_sym if out_stride is None else int(out_stride),
+            self._ptr(d_rec), self._ptr(d_status), nb if status_stride is None else int(status_stride), C.byref(k), stream))
+        return k.value
+
+    def reset(self):
+        raise AttributeError("Burst has no reset: it carries no state")
+
+    def demodulate(self, x, idx=None, gate=None, n_bursts=None, start_base=0, start_step=0):
+        """Host convenience, computed on the GPU: x is (n_streams, n) complex -- or, with FMT_U8, (n_streams, 2n) uint8
+        (I,Q) pairs -- idx (uint32) and gate (float32) are (n_streams, n_bursts) or None; returns (symbols (n_streams,
+        n_bursts, n_sym) complex64, record (n_streams, n_bursts, 8) float32, status (n_streams, n_bursts) int32)."""
+        S, N = self.n_streams, self.n_sym
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(S, -1)
+        if gate is not None:
+            gate = np.ascontiguousarray(gate, dtype=np.float32).reshape(S, -1)
+        nb = int(n_bursts) if n_bursts is not None else (idx.shape[1] if idx is not None else (gate.shape[1] if gate is not None else 1))
+        d_in, n = self._upload_input(x)
+        held = [d_in]
+        try:
+            d_idx = d_gate = None
+            if idx is not None:
+                d_idx = DeviceArray.from_numpy(idx.view(np.float32).ravel())
+                held.append(d_idx)
+            if gate is not None:
+                d_gate = DeviceArray.from_numpy(gate.ravel())
+                held.append(d_gate)
+            d_out, d_rec, d_st = DeviceArray(max(1, S * nb * N * 2)), DeviceArray(max(1, S * nb * 8)), DeviceArray(max(1, S * nb))
+            held += [d_out, d_rec, d_st]
+            if nb:
+                self.process_stream(d_in, n, nb, d_out, d_idx, d_gate, d_rec, d_st, start_base, start_step)
+            sym = d_out.to_numpy(S * nb * N * 2).view(np.complex64).reshape(S, nb, N)
+            rec = d_rec.to_numpy(S * nb * 8).reshape(S, nb, 8)
+            st = d_st.to_numpy(S * nb).view(np.int32).reshape(S, nb)
+        finally:
+            for d in held:
+                d.free()
+        return np.ascontiguousarray(sym), np.ascontiguousarray(rec), np.ascontiguousarray(st)
+
+
 def rs_plan(state, upsample, n_in, out_len, rate):
     """Host-only replay of one process() call's time law (sfe_dsp_rs_plan).
     state: lib.TimeState (updated in place).  Returns (rel_pos int32[], mu float32[])."""

@@ -167,6 +167,13 @@ SIGNATURES = {
     "sfe_dsp_eig_set_signal_dim": (i32, [vp, i32]),
     "sfe_dsp_eig_process_stream": (i32, [vp, vp, sz, sz, vp, sz, vp, sz, vp, sz, vp, sz, C.POINTER(sz), vp]),
     "sfe_dsp_eig_destroy": (i32, [vp]),
+    "sfe_dsp_burst_plan": (i32, [fp, i32, i32, i32, i32, i32, f32, fp, sz, C.POINTER(C.c_uint32), fp, sz, C.c_int64, C.c_int64, fp, fp, fp,
+                                 C.POINTER(i32)]),
+    "sfe_dsp_burst_create": (i32, [fp, i32, i32, i32, i32, i32, f32, i32, i32, C.POINTER(vp)]),
+    "sfe_dsp_burst_set_input_format": (i32, [vp, i32]),
+    "sfe_dsp_burst_set_gate": (i32, [vp, f32]),
+    "sfe_dsp_burst_process_stream": (i32, [vp, vp, sz, sz, vp, sz, vp, sz, sz, C.c_int64, C.c_int64, vp, sz, vp, vp, sz, C.POINTER(sz), vp]),
+    "sfe_dsp_burst_destroy": (i32, [vp]),
 }
 
 # the diagnostic library only (simplefe_amd/csrc/diag/sfe_dsp_diag.h; scripts/ load it by pointing LIB_PATH at it): bound when present

@@ -720,3 +720,52 @@ def offset_bytes(n_samples, bias=0, seed=SEED):
 def u8_to_cf32(b):
     """The receive converter's law (sfe_dsp_rx_u8_to_f32) in float32: (b - 128) * (1/127)."""
     return ((np.asarray(b, dtype=np.uint8).astype(np.float32) - np.float32(128.0)) * np.float32(1.0 / 127.0)).view(np.complex64)
+
+
+# ---- the burst demodulator (sfe_dsp_burst_*): a pulse-shaped PSK burst whose timing, carrier and amplitude are known exactly
+def raised_cosine(t, beta=0.35):
+    """The raised-cosine pulse at times t (in symbols), float64: 1 at 0, 0 at every other integer."""
+    t = np.asarray(t, dtype=np.float64)
+    den = 1.0 - (2.0 * beta * t) ** 2
+    edge = np.abs(den) < 1e-12
+    h = np.sinc(t) * np.cos(np.pi * beta * t) / np.where(edge, 1.0, den)
+    return np.where(edge, (np.pi / 4.0) * np.sinc(1.0 / (2.0 * beta)), h)
+
+
+def psk_symbols(n, order=4, seed=SEED):
+    """n unit-modulus symbols, float64: BPSK (order 2: +-1) or QPSK (order 4: the odd multiples of pi/4)."""
+    rng = np.random.default_rng(seed)
+    k = rng.integers(0, order, size=int(n))
+    return np.exp(1j * (2.0 * np.pi * k / order + (np.pi / 4.0 if order == 4 else 0.0)))
+
+
+def burst_signal(symbols, sps, n, start, tau=0.0, f=0.0, phase=0.0, amp=1.0, beta=0.35, span=32):
+    """n complex64 samples holding one burst: symbol k of `symbols` peaks at sample start + k sps + tau (tau in samples,
+    any real number: the pulse is evaluated analytically at the shifted times), shaped by a raised cosine of roll-off
+    beta cut at +-span symbols, then turned by a carrier of f turns per symbol whose phase is `phase` radians at symbol
+    0, and scaled by amp.  No noise.  Computed in float64, rounded once."""
+    a = np.asarray(symbols, dtype=np.complex128)
+    t = (np.arange(int(n), dtype=np.float64) - start - tau) / sps        # in symbols, 0 at symbol 0's peak
+    k0 = np.floor(t).astype(np.int64)
+    x = np.zeros(int(n), np.complex128)
+    for d in range(-span, span + 2):
+        k = k0 + d
+        ok = (k >= 0) & (k < a.size)
+        x[ok] += a[k[ok]] * raised_cosine(t[ok] - k[ok], beta)
+    return (amp * x * np.exp(1j * (2.0 * np.pi * f * t + phase))).astype(np.complex64)
+
+
+def burst_cases(sps, n_sym, lag, seed=SEED):
+    """The bursts the burst demodulator's tests and DESIGN.md 4.16 measure: per true tau in {-0.49 sps, -1.25, 0, 0.5,
+    +0.49 sps} samples and true f in {0, +-0.02, 0.4 / lag} turns per symbol, (x complex64, o, the n_sym transmitted
+    symbols, tau, f, phase, amp): an isolated burst whose symbol 0 peaks at sample o + tau of x.  QPSK and BPSK by turns
+    (one sequence of each, drawn from `seed`); phase and amplitude differ from case to case."""
+    out = []
+    o, n = 3 * sps + 5, (n_sym + 8) * sps + 11
+    for i, tau in enumerate((-0.49 * sps, -1.25, 0.0, 0.5, 0.49 * sps)):
+        for j, f in enumerate((0.0, 0.02, -0.02, 0.4 / lag)):
+            c = 4 * i + j
+            a = psk_symbols(n_sym, 2 if c & 1 else 4, seed=seed)
+            phase, amp = 0.7 * c - 2.9, 0.25 + 0.125 * c
+            out.append((burst_signal(a, sps, n, o, tau, f, phase, amp), o, a, tau, f, phase, amp))
+    return out
