@@ -1208,6 +1208,100 @@ int sfe_dsp_burst_process_stream(sfe_burst_t h, const void *d_in, size_t n_in, s
                                  sfe_stream_t stream);
 int sfe_dsp_burst_destroy(sfe_burst_t h);
 
+/* ------------------------------------------------- soft-decision Viterbi decoder
+ * What follows the burst demodulator on a coded link: per burst, n_soft soft values -- float32, or
+ * the components of the symbols sfe_dsp_burst_* wrote, where they lie on the device -- become the
+ * ceil(n_info / 8) bytes of the payload, a record and a status.  Bursts are independent; nothing is
+ * carried.  All arithmetic is float32, and every operation is ONE IEEE addition or comparison: no
+ * product, no fused operation.
+ * Code: constraint length K in [3, 9]; n_gen = n generators, n in {2, 3, 4}, 0 < g_j < 2^K;
+ * S = 2^(K-1) states; a state is the K-1 latest input bits, newest in bit 0.  Input bit u from state
+ * s: reg = (s << 1 | u) mod 2^K, coded bit c_j = parity(reg & g_j) for j = 0 .. n-1 in that order,
+ * next state reg mod S.  The encoder starts in state 0.  terminated = 1: K-1 zero bits follow the
+ * n_info payload bits, T = n_info + K-1 steps, the decoder ends in state 0; terminated = 0:
+ * T = n_info, the decoder ends in the state of the largest metric, the lowest index among equals.
+ * n_info in [1, 8192].
+ * Puncturing: keep[P][n] bytes of 0 / 1, period P in [1, 32] steps, at least one position kept;
+ * keep = NULL: every position is kept (P is then ignored).  Position (t, j) is transmitted iff
+ * keep[t mod P][j]; the kept positions, numbered in the order of (t, j), are the indices of the
+ * burst's soft values: n_soft of them over the T steps (a pattern that keeps none of them is
+ * refused).  A punctured position has the soft value +0 and consumes no input.
+ * Soft input: r > 0 favours coded bit 0.  SFE_VIT_IN_SOFT: n_soft float32 per burst at
+ * d_in + b*in_stride (skip must be 0).  SFE_VIT_IN_BPSK: d_in is rows of cf32 as sfe_dsp_burst_*
+ * writes them, soft value i is Re of symbol skip + i.  SFE_VIT_IN_QPSK: soft value 2i is Re and
+ * 2i+1 is Im of symbol skip + i.  skip in [0, 2^24] is the preamble's length; in_stride counts
+ * elements of the mode's type.  Behind a burst demodulator: its d_out, its out_stride, skip = Lp and
+ * its d_status as d_status_in are the whole glue.
+ * Metrics: pm[0] = +0, pm[s] = -inf elsewhere.  Step t, state s', u = s' & 1: the predecessors are
+ * p0 = s' >> 1 and p1 = p0 | S/2; the branch value bm(p) = ((+-r_0) + (+-r_1)) + ..., left to right
+ * over the step's n positions, minus (the sign bit flipped) where the branch's c_j is 1;
+ * cand0 = pm[p0] + bm(p0), cand1 = pm[p1] + bm(p1); decision d = (cand1 > cand0);
+ * pm'[s'] = d ? cand1 : cand0 -- equal candidates take p0.  No normalisation, no renormalising
+ * subtraction: T n max|r| stays far inside float32's range.
+ * Traceback: from the end state, for t = T-1 .. 0: bit_t = s & 1, s = (s >> 1) | (d_t[s] << (K-2)).
+ * Output per burst: bits 0 .. n_info-1 packed MSB-first into ceil(n_info / 8) bytes at
+ * d_bits + b*out_stride (bytes), pad bits 0; a record of two 32-bit words at d_rec + 2b -- the end
+ * state's metric as float32, and a uint32 count of the kept positions whose re-encoded bit disagrees
+ * with the sign of r (r = +-0 agrees with either bit); an int32 status at d_status + b:
+ *   0  decoded
+ *   1  a non-finite soft value among the burst's n_soft: the bytes are 0, the record (quiet NaN
+ *      0x7fc00000, 0)
+ *   2  d_status_in is given and its word for this burst is not 0 (the table sfe_dsp_burst_* wrote):
+ *      no input is read; bytes and record as for status 1
+ * Promised about bits: the same call gives the same bits on every run; a burst's output depends on
+ * its n_soft values and the code only -- never on b, n_bursts, addresses, strides or the input mode
+ * (BPSK and QPSK input give the bits of SOFT input on the extracted components); the device's
+ * bytes, metric word, count and status EQUAL sfe_dsp_vit_plan's, for every input whose partial sums
+ * are zero or normal numbers; nothing outside the slots named is written.  Not promised: anything
+ * when a partial sum is subnormal or leaves float32's range.
+ * A bad argument is SFE_EINVAL on any machine, with a message that starts with "vit: ". */
+#define SFE_VIT_IN_SOFT 0
+#define SFE_VIT_IN_BPSK 1
+#define SFE_VIT_IN_QPSK 2
+typedef void *sfe_vit_t;  /* opaque: one decoder; it owns no device memory and nothing in it changes after create */
+/* Host-only, the transmit half: bits[n_info] (one 0 / 1 byte per bit) -> the kept coded bits, one
+ * 0 / 1 byte each, in coded[*n_coded], termination and puncturing applied.  *n_coded = n_soft is
+ * reported with coded = NULL too. */
+int sfe_dsp_vit_encode(int K, int n_gen, const uint32_t *gen, const uint8_t *keep, int P,
+                       int terminated, const uint8_t *bits, size_t n_info, uint8_t *coded,
+                       size_t *n_coded);
+/* Host-only: the LDS one burst needs on the device whatever its soft values do -- survivors,
+ * T * max(S, 64) / 8 bytes, plus the packed bits, ceil(n_info / 8) rounded up to 8 -- whether the
+ * T n soft values are staged beside them (all three within 134 400 bytes), and how many bursts
+ * share a workgroup (0: create refuses the shape, the first two exceed 134 400 bytes). */
+int sfe_dsp_vit_footprint(int K, int n_gen, int terminated, int n_info, size_t *lds_bytes,
+                          int *staged, int *bursts_per_group);
+/* Host-only (no GPU): validates what create validates and reports n_soft.  With in != NULL -- host
+ * memory laid out as d_in of process_stream, status_in [n_bursts] or NULL likewise -- it decodes
+ * n_bursts bursts by the law above, exactly as stated, into bytes (required then; burst b at
+ * bytes + b*out_stride), record [n_bursts][2] and status [n_bursts] (each may be NULL): the CPU
+ * fallback, and the reference of the device's bits.  Short strides are SFE_ERANGE. */
+int sfe_dsp_vit_plan(int K, int n_gen, const uint32_t *gen, const uint8_t *keep, int P,
+                     int terminated, int n_info, int in_mode, int skip, const float *in,
+                     size_t in_stride, const int *status_in, size_t n_bursts, uint8_t *bytes,
+                     size_t out_stride, uint32_t *record, int *status, size_t *n_soft);
+/* Arguments are checked before the device is touched: SFE_EINVAL for a bad one on any machine
+ * (a burst whose survivors and bits exceed the launch's LDS among them: K = 9 beyond T = 4183),
+ * SFE_ENODEV without a GPU.  gen and keep are copied. */
+int sfe_dsp_vit_create(int K, int n_gen, const uint32_t *gen, const uint8_t *keep, int P,
+                       int terminated, int n_info, int in_mode, int skip, int device,
+                       sfe_vit_t *out);
+/* n_bursts bursts; d_status_in, d_rec and d_status may each be NULL.  *n_out = n_bursts;
+ * n_bursts = 0 is a no-op.  in_stride below the row a burst reads (n_soft floats; skip + n_soft or
+ * skip + ceil(n_soft / 2) symbols) or out_stride < ceil(n_info / 8) is SFE_ERANGE; a null d_in or
+ * d_bits, misaligned buffers (soft values, records, statuses 4 bytes, symbols 8), n_bursts >= 2^31,
+ * a stride that takes a buffer's byte range to 2^62, and any output byte range that overlaps an
+ * input's or another output's are SFE_EINVAL; nothing is launched on a refusal.  Asynchronous on
+ * `stream`; one kernel launch and nothing else: allocates nothing, does not synchronise the host,
+ * carries no state (there is no reset).  Everything a call uses travels with it by value and a
+ * handle has no setter, so a call on a stream under graph capture IS supported: the captured node
+ * replays the same decoder on the same buffers. */
+int sfe_dsp_vit_process_stream(sfe_vit_t h, const void *d_in, size_t in_stride,
+                               const void *d_status_in, size_t n_bursts, void *d_bits,
+                               size_t out_stride, void *d_rec, void *d_status, size_t *n_out,
+                               sfe_stream_t stream);
+int sfe_dsp_vit_destroy(sfe_vit_t h);
+
 #ifdef __cplusplus
 }
 #endif

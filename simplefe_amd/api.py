@@ -1208,6 +1208,120 @@ class Burst(_Block):
         return np.ascontiguousarray(sym), np.ascontiguousarray(rec), np.ascontiguousarray(st)
 
 
+def _vit_code(gen, keep):
+    """(n_gen, the generators' pointer, the pattern's pointer or None, its period P, what keeps them alive)."""
+    g = np.ascontiguousarray(np.asarray(gen, dtype=np.uint32).ravel())
+    if keep is None:
+        return g.size, g.ctypes.data_as(C.POINTER(C.c_uint32)), None, 1, (g,)
+    k = np.ascontiguousarray(np.asarray(keep, dtype=np.uint8))
+    if k.ndim != 2 or k.shape[1] != g.size:
+        raise ValueError("vit: keep must be (P, n_gen) = (P, %d), not %s" % (g.size, k.shape))
+    return g.size, g.ctypes.data_as(C.POINTER(C.c_uint32)), k.ctypes.data_as(C.POINTER(C.c_uint8)), k.shape[0], (g, k)
+
+
+def vit_encode(K, gen, bits, keep=None, terminated=True):
+    """sfe_dsp_vit_encode (host only): the payload bits (0 / 1, one per item) through the convolutional encoder of constraint
+    length K and generators gen, K - 1 zero bits appended when terminated, the positions keep[t mod P][j] == 0 left out:
+    the kept coded bits as a uint8 array of 0 / 1."""
+    n, gp, kp, P, _alive = _vit_code(gen, keep)
+    b = np.ascontiguousarray(np.asarray(bits, dtype=np.uint8).ravel())
+    L, u8p, k = _l.load(), C.POINTER(C.c_uint8), C.c_size_t(0)
+    check(L.sfe_dsp_vit_encode(int(K), n, gp, kp, P, int(bool(terminated)), b.ctypes.data_as(u8p), b.size, None, C.byref(k)))
+    coded = np.empty(k.value, np.uint8)
+    check(L.sfe_dsp_vit_encode(int(K), n, gp, kp, P, int(bool(terminated)), b.ctypes.data_as(u8p), b.size, coded.ctypes.data_as(u8p), C.byref(k)))
+    return coded
+
+
+def vit_footprint(K, n_gen, n_info, terminated=True):
+    """sfe_dsp_vit_footprint (host only): (LDS bytes of one burst's survivors and packed bits, whether its soft values are
+    staged in LDS beside them, bursts per workgroup -- 0 where create refuses the shape)."""
+    by, st, w = C.c_size_t(0), C.c_int(0), C.c_int(0)
+    check(_l.load().sfe_dsp_vit_footprint(int(K), int(n_gen), int(bool(terminated)), int(n_info), C.byref(by), C.byref(st), C.byref(w)))
+    return by.value, bool(st.value), w.value
+
+
+def vit_plan(K, gen, n_info, keep=None, terminated=True, in_mode=_l.VIT_IN_SOFT, skip=0, x=None, status_in=None):
+    """sfe_dsp_vit_plan (host only, no GPU): validates and, without x, returns n_soft.  With x -- (n_bursts, row) float32
+    soft values with VIT_IN_SOFT, complex symbols with VIT_IN_BPSK / VIT_IN_QPSK -- it decodes every row by the law in
+    float32: returns (bytes (n_bursts, ceil(n_info / 8)) uint8, record (n_bursts, 2) uint32 -- the metric's float32 word,
+    the disagreement count -- and status (n_bursts,) int32).  These are the device's bits.  status_in: int32 per burst or
+    None.  Raises SfeError on arguments the block refuses."""
+    n, gp, kp, P, _alive = _vit_code(gen, keep)
+    L, ns = _l.load(), C.c_size_t(0)
+    head = (int(K), n, gp, kp, P, int(bool(terminated)), int(n_info), int(in_mode), int(skip))
+    if x is None:
+        check(L.sfe_dsp_vit_plan(*head, None, 0, None, 0, None, 0, None, None, C.byref(ns)))
+        return ns.value
+    x = np.asarray(x)
+    x = np.ascontiguousarray(x.reshape(1, -1) if x.ndim == 1 else x, dtype=np.float32 if in_mode == _l.VIT_IN_SOFT else np.complex64)
+    nb, nbytes = x.shape[0], (max(int(n_info), 0) + 7) // 8
+    if status_in is not None:
+        status_in = np.ascontiguousarray(status_in, dtype=np.int32).ravel()
+        if status_in.size != nb:
+            raise ValueError("vit_plan: status_in has %d entries for %d bursts" % (status_in.size, nb))
+    by, rec, st = np.empty((nb, nbytes), np.uint8), np.empty((nb, 2), np.uint32), np.empty(nb, np.int32)
+    check(L.sfe_dsp_vit_plan(*head, x.view(np.float32).ctypes.data_as(C.POINTER(C.c_float)), x.shape[1],
+                             None if status_in is None else status_in.ctypes.data_as(C.POINTER(C.c_int)), nb,
+                             by.ctypes.data_as(C.POINTER(C.c_uint8)), nbytes, rec.ctypes.data_as(C.POINTER(C.c_uint32)),
+                             st.ctypes.data_as(C.POINTER(C.c_int)), C.byref(ns)))
+    return by, rec, st
+
+
+class Vit(_Block):
+    """Soft-decision Viterbi decoder (sfe_dsp_vit_*): per burst, n_soft soft values -- float32, or the components of the
+    symbols a Burst wrote -- become ceil(n_info / 8) payload bytes, a record (the end state's metric word, the count of
+    positions that disagree with the decoded word) and a status.  The device's bits are vit_plan's."""
+    _prefix = "vit"
+
+    def __init__(self, K, gen, n_info, keep=None, terminated=True, in_mode=_l.VIT_IN_SOFT, skip=0, device=0):
+        n, gp, kp, P, _alive = _vit_code(gen, keep)
+        self.K, self.n_gen, self.n_info, self.in_mode, self.skip = int(K), n, int(n_info), int(in_mode), int(skip)
+        self.n_bytes = (max(self.n_info, 0) + 7) // 8
+        self._create(self.K, n, gp, kp, P, int(bool(terminated)), self.n_info, self.in_mode, self.skip, device)
+        self.n_soft = vit_plan(K, gen, n_info, keep, terminated, in_mode, skip)
+        # elements of the mode's type a burst's row holds at least
+        self.row = self.n_soft if self.in_mode == _l.VIT_IN_SOFT else self.skip + (self.n_soft if self.in_mode == _l.VIT_IN_BPSK else (self.n_soft + 1) // 2)
+
+    def process_stream(self, d_in, n_bursts, d_bits, d_rec=None, d_status=None, d_status_in=None, in_stride=None, out_stride=None, stream=None):
+        """d_*: DeviceArray or raw device pointers.  Burst b reads its row at d_in + b*in_stride (elements of the input
+        mode's type; default: the row's own length) and, with d_status_in, the int32 at d_status_in + b; it writes n_bytes
+        bytes at d_bits + b*out_stride (bytes; default n_bytes), two words at d_rec + 2b and an int32 at d_status + b.
+        Returns n_bursts."""
+        k = C.c_size_t(0)
+        check(self._fn("process_stream")(self._h, self._ptr(d_in), self.row if in_stride is None else int(in_stride), self._ptr(d_status_in),
+                                         int(n_bursts), self._ptr(d_bits), self.n_bytes if out_stride is None else int(out_stride),
+                                         self._ptr(d_rec), self._ptr(d_status), C.byref(k), stream))
+        return k.value
+
+    def reset(self):
+        raise AttributeError("Vit has no reset: it carries no state")
+
+    def decode(self, x, status_in=None):
+        """Host convenience, computed on the GPU: x is (n_bursts, row) -- float32 soft values, or complex symbols with
+        VIT_IN_BPSK / VIT_IN_QPSK; returns (bytes (n_bursts, n_bytes) uint8, record (n_bursts, 2) uint32, status (n_bursts,)
+        int32), as vit_plan does."""
+        x = np.asarray(x)
+        x = np.ascontiguousarray(x.reshape(1, -1) if x.ndim == 1 else x, dtype=np.float32 if self.in_mode == _l.VIT_IN_SOFT else np.complex64)
+        nb = x.shape[0]
+        held = [DeviceArray.from_numpy(x.view(np.float32))]
+        try:
+            d_si = None
+            if status_in is not None:
+                d_si = DeviceArray.from_numpy(np.ascontiguousarray(status_in, dtype=np.int32).reshape(nb).view(np.float32))
+                held.append(d_si)
+            d_by, d_rec, d_st = DeviceArray(max(1, (nb * self.n_bytes + 3) // 4)), DeviceArray(max(1, 2 * nb)), DeviceArray(max(1, nb))
+            held += [d_by, d_rec, d_st]
+            if nb:
+                self.process_stream(held[0], nb, d_by, d_rec, d_st, d_si, in_stride=x.shape[1])
+            by = d_by.to_numpy().view(np.uint8)[:nb * self.n_bytes].reshape(nb, self.n_bytes)
+            rec = d_rec.to_numpy(2 * nb).view(np.uint32).reshape(nb, 2)
+            st = d_st.to_numpy(nb).view(np.int32)
+        finally:
+            for d in held:
+                d.free()
+        return np.ascontiguousarray(by), np.ascontiguousarray(rec), np.ascontiguousarray(st)
+
+
 def rs_plan(state, upsample, n_in, out_len, rate):
     """Host-only replay of one process() call's time law (sfe_dsp_rs_plan).
     state: lib.TimeState (updated in place).  Returns (rel_pos int32[], mu float32[])."""

@@ -93,17 +93,6 @@ int burst_check_starts(const char *who, int64_t start_base, int64_t start_step, 
     return SFE_OK;
 }
 
-// bytes = (rows_less_1 * stride + tail) * elem, false where that is not below 2^62
-bool span_bytes(size_t rows_less_1, size_t stride, size_t tail, size_t elem, size_t *bytes)
-{
-    size_t v;
-    if (__builtin_mul_overflow(rows_less_1, stride, &v) || __builtin_add_overflow(v, tail, &v) || __builtin_mul_overflow(v, elem, &v) ||
-        v >= ((size_t)1 << 62))
-        return false;
-    *bytes = v;
-    return true;
-}
-
 bool usable(double re, double im) { return std::isfinite(re) && std::isfinite(im) && (re != 0.0 || im != 0.0); }
 
 void unturn(double t, double *c, double *s)     // exp(-j 2 pi t) as (c, s)

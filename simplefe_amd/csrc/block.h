@@ -1,5 +1,5 @@
 // block.h -- what the handles of the streaming blocks share (api_chan.hip, api_combine.hip, api_ddc.hip, api_psd.hip,
-// api_corr.hip, api_iir.hip, api_beam.hip, api_cov.hip, api_mvdr.hip, api_eig.hip, api_burst.hip): owners of their device memory, the device scope of a create, the handle cast, the table
+// api_corr.hip, api_iir.hip, api_beam.hip, api_cov.hip, api_mvdr.hip, api_eig.hip, api_burst.hip, api_vit.hip): owners of their device memory, the device scope of a create, the handle cast, the table
 // of the unit circle, and the checks every process_stream opens with.  HOST CODE ONLY, like host.h; include it after
 // host.h.  A block's struct names its magic as `static constexpr uint32_t MAGIC` and carries `magic` and `device`.
 #pragma once
@@ -206,6 +206,17 @@ inline int refuse_overlap(const char *who, Span in, std::initializer_list<Span> 
             return SFE_EINVAL;
         }
     return SFE_OK;
+}
+
+// bytes = (rows_less_1 * stride + tail) * elem, false where that is not below 2^62
+inline bool span_bytes(size_t rows_less_1, size_t stride, size_t tail, size_t elem, size_t *bytes)
+{
+    size_t v;
+    if (__builtin_mul_overflow(rows_less_1, stride, &v) || __builtin_add_overflow(v, tail, &v) || __builtin_mul_overflow(v, elem, &v) ||
+        v >= ((size_t)1 << 62))
+        return false;
+    *bytes = v;
+    return true;
 }
 
 // the counter named advances on the host with the carried pair, so a captured call could not be replayed

@@ -17,6 +17,7 @@ FIR_VARIANT_NAMES = {-1: "auto", 0: "register loads", 1: "LDS-DMA", 2: "LDS-DMA,
 RS_RESAMPLE, RS_DECIMATE = 0, 1
 RS_ALGO_AUTO, RS_ALGO_DIRECT, RS_ALGO_FFT, RS_ALGO_MFMA = 0, 1, 2, 3
 FMT_F32, FMT_U8, FMT_TX10 = 0, 1, 2
+VIT_IN_SOFT, VIT_IN_BPSK, VIT_IN_QPSK = 0, 1, 2      # sfe_dsp_vit_*: what d_in holds
 
 
 class TimeState(C.Structure):
@@ -174,6 +175,14 @@ SIGNATURES = {
     "sfe_dsp_burst_set_gate": (i32, [vp, f32]),
     "sfe_dsp_burst_process_stream": (i32, [vp, vp, sz, sz, vp, sz, vp, sz, sz, C.c_int64, C.c_int64, vp, sz, vp, vp, sz, C.POINTER(sz), vp]),
     "sfe_dsp_burst_destroy": (i32, [vp]),
+    "sfe_dsp_vit_encode": (i32, [i32, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), i32, i32, C.POINTER(C.c_uint8), sz, C.POINTER(C.c_uint8),
+                                 C.POINTER(sz)]),
+    "sfe_dsp_vit_footprint": (i32, [i32, i32, i32, i32, C.POINTER(sz), C.POINTER(i32), C.POINTER(i32)]),
+    "sfe_dsp_vit_plan": (i32, [i32, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), i32, i32, i32, i32, i32, fp, sz, C.POINTER(i32), sz,
+                               C.POINTER(C.c_uint8), sz, C.POINTER(C.c_uint32), C.POINTER(i32), C.POINTER(sz)]),
+    "sfe_dsp_vit_create": (i32, [i32, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), i32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
+    "sfe_dsp_vit_process_stream": (i32, [vp, vp, sz, vp, sz, vp, sz, vp, vp, C.POINTER(sz), vp]),
+    "sfe_dsp_vit_destroy": (i32, [vp]),
 }
 
 # the diagnostic library only (simplefe_amd/csrc/diag/sfe_dsp_diag.h; scripts/ load it by pointing LIB_PATH at it): bound when present

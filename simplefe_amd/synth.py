@@ -769,3 +769,35 @@ def burst_cases(sps, n_sym, lag, seed=SEED):
             phase, amp = 0.7 * c - 2.9, 0.25 + 0.125 * c
             out.append((burst_signal(a, sps, n, o, tau, f, phase, amp), o, a, tau, f, phase, amp))
     return out
+
+
+# ---- the Viterbi decoder (sfe_dsp_vit_*): payloads, the channel's soft values, and coded bits as symbols
+def vit_bits(n, seed=SEED):
+    """n payload bits (uint8 0 / 1) drawn from `seed`."""
+    return np.random.default_rng(seed).integers(0, 2, size=int(n)).astype(np.uint8)
+
+
+def vit_pack(bits):
+    """Bits packed MSB-first into bytes, pad bits 0: what the decoder writes for them."""
+    return np.packbits(np.asarray(bits, dtype=np.uint8))
+
+
+def vit_soft(coded, ebn0_db=None, rate=0.5, seed=SEED):
+    """The soft values of coded bits sent as BPSK, float32: 1 - 2c, plus -- with ebn0_db -- white Gaussian noise of
+    variance 1 / (2 rate Eb/N0) drawn from `seed`.  A positive value favours bit 0."""
+    r = 1.0 - 2.0 * np.asarray(coded, dtype=np.float64)
+    if ebn0_db is not None:
+        sigma = np.sqrt(1.0 / (2.0 * rate * 10.0 ** (ebn0_db / 10.0)))
+        r = r + sigma * np.random.default_rng(seed).standard_normal(r.shape)
+    return r.astype(np.float32)
+
+
+def vit_symbols(coded, order=2):
+    """Coded bits as unit-modulus symbols, complex128: BPSK (order 2: 1 - 2c) or Gray QPSK (order 4: bits 2i and 2i+1 on
+    the real and the imaginary part, each (1 - 2c) / sqrt 2; an odd count is padded with a 0 bit)."""
+    c = np.asarray(coded, dtype=np.float64).ravel()
+    if order == 2:
+        return (1.0 - 2.0 * c).astype(np.complex128)
+    if c.size & 1:
+        c = np.concatenate([c, [0.0]])
+    return ((1.0 - 2.0 * c[0::2]) + 1j * (1.0 - 2.0 * c[1::2])) / np.sqrt(2.0)
