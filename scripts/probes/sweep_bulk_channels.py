@@ -44,7 +44,7 @@ for (U, rate), plen, cplx, exact, mode, shift in itertools.product(RATES, (7, 32
             ref, _ = (orc.Resample if mode == "resample" else orc.Decimate)(taps, U, B).stream(np.ascontiguousarray(x[c, part::w]), rate)
             got = y[c, part::w]
             key = None
-            if len(ref) - len(got) not in (0, 1):
+            if len(ref) != len(got):                  # the oracle's total already leaves a pending leftover out: no slack
                 key = "output count differs"
             elif exact and not np.array_equal(got.view(np.uint32), ref[: len(got)].view(np.uint32)):
                 key = "exact mode: bits differ"

@@ -32,7 +32,7 @@ for (U, rate), plen, B, cplx, exact in itertools.product(RATES, (1, 7, 32, 127),
         for part in range(w):
             ref, _ = orc.Resample(taps, U, B).stream(np.ascontiguousarray(x[part::w]), rate)
             got = y[part::w]
-            if len(ref) - len(got) not in (0, 1):
+            if len(ref) != len(got):                  # the oracle's total already leaves a pending leftover out: no slack
                 bad.setdefault("output count differs", []).append((U, round(rate, 4), plen, B, cplx, exact, len(got), len(ref)))
                 break
             if exact:

@@ -6,6 +6,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import stream_checks as sc
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIBDIR = os.path.join(ROOT, "simplefe_amd")
@@ -170,12 +172,9 @@ def test_gr_fir_batching_is_5x_the_round_trip_per_call_and_bit_exact(gr_exe, tmp
     y = np.fromfile(tmp_path / "y.f32", dtype=np.float32)
     f = api.Fir(taps, data_complex=True)
     B = 1 << 18
-    d_in, d_out = api.DeviceArray(2 * B), api.DeviceArray(2 * B)
     for off in range(0, n, B):
-        seg = np.ascontiguousarray(x[2 * off: 2 * (off + B)])
-        api.check(lib.load().sfe_dsp_memcpy_h2d(d_in.ptr, seg.ctypes.data, seg.nbytes, None))
-        f.process_stream(d_in, d_out, B)
-        assert np.array_equal(d_out.to_numpy(2 * B), y[2 * off: 2 * (off + B)]), off
+        got = sc.run_fir(api, f, x[2 * off: 2 * (off + B)])[0]
+        assert np.array_equal(got, y[2 * off: 2 * (off + B)]), off
 
 
 def test_gr_decimate_and_resampler_blocks_bit_exact(gr_exe, tmp_path, g5, orc):
@@ -188,12 +187,14 @@ def test_gr_decimate_and_resampler_blocks_bit_exact(gr_exe, tmp_path, g5, orc):
     for part in (0, 1):
         ref, _ = orc.Decimate(g5["cfg4_taps"], 1, 4096).stream(x[part::2], 8.0)
         got = y[part::2]
-        assert len(ref) - len(got) <= 1 and np.array_equal(got, ref[: len(got)])
+        sc.check_total(len(got), len(ref), n, 1, 8.0)
+        assert np.array_equal(got, ref)
     y = _run_gr(gr_exe, tmp_path, "resample", g5["cfg3_taps"], x, 5, 3)
     for part in (0, 1):
         ref, _ = orc.Resample(g5["cfg3_taps"], 3, 4096).stream(x[part::2], 5.0 / 3.0)
         got = y[part::2]
-        assert len(ref) - len(got) <= 2 and np.array_equal(got, ref[: len(got)])
+        sc.check_total(len(got), len(ref), n, 3, 5.0 / 3.0)
+        assert np.array_equal(got, ref)
 
 
 def test_gr_float_item_blocks_bit_exact(gr_exe, tmp_path, g5, orc):
@@ -204,10 +205,12 @@ def test_gr_float_item_blocks_bit_exact(gr_exe, tmp_path, g5, orc):
     x = synth.synth_f32(n, ch=9)
     y = _run_gr(gr_exe, tmp_path, "decimate_f", g5["cfg4_taps"], x, 8)
     ref, _ = orc.Decimate(g5["cfg4_taps"], 1, 4096).stream(x, 8.0)
-    assert len(ref) - len(y) <= 1 and np.array_equal(y, ref[: len(y)])
+    sc.check_total(len(y), len(ref), n, 1, 8.0)
+    assert np.array_equal(y, ref)
     y = _run_gr(gr_exe, tmp_path, "resample_f", g5["cfg3_taps"], x, 5, 3)
     ref, _ = orc.Resample(g5["cfg3_taps"], 3, 4096).stream(x, 5.0 / 3.0)
-    assert len(ref) - len(y) <= 2 and np.array_equal(y, ref[: len(y)])
+    sc.check_total(len(y), len(ref), n, 3, 5.0 / 3.0)
+    assert np.array_equal(y, ref)
 
 
 def test_gr_wire_format_blocks(gr_exe, tmp_path, orc):

@@ -5,6 +5,7 @@ advance; 512-m polyphase tiles).  `-m gpu`."""
 import numpy as np
 import pytest
 
+import stream_checks as sc
 from simplefe_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -20,6 +21,13 @@ def api():
 def L():
     from simplefe_amd import lib
     return lib
+
+
+@pytest.fixture(autouse=True)
+def _guards():
+    """every buffer of a test (stream_checks.Guarded): guards still poison, inputs still what was uploaded"""
+    yield
+    sc.check_guarded()
 
 
 def _cuts(rng, n, k):
@@ -48,8 +56,8 @@ def test_fir_random_shapes(api, L, seed):
     y = np.zeros((nch, wo * n), np.float32)
     for a, b in _cuts(rng, n, int(rng.integers(0, 4))):
         m = b - a
-        d_in = api.DeviceArray.from_numpy(np.ascontiguousarray(x[:, w * a: w * a + w * stride - w * a][:, : w * (stride - a)]))
-        d_out = api.DeviceArray(nch * wo * (m + 3))
+        d_in = sc.from_numpy(api, np.ascontiguousarray(x[:, w * a: w * a + w * stride - w * a][:, : w * (stride - a)]))
+        d_out = sc.device_array(api, nch * wo * (m + 3))
         f.process_stream(d_in, d_out, m, in_stride=stride - a, out_stride=m + 3)
         y[:, wo * a: wo * b] = d_out.to_numpy().reshape(nch, wo * (m + 3))[:, : wo * m]
     from scipy.signal import fftconvolve
@@ -83,12 +91,12 @@ def test_rs_random_shapes_bit_exact(api, L, orc, seed):
     r = api.Rs(taps, U, B, mode=L.RS_RESAMPLE, data_complex=cplx)
     r.set_exact(True)
     chunk = None if seed % 3 else int(rng.integers(1, 40)) * B       # bulk calls of whole blksize multiples
-    y = r.resample_array(x, rate, chunk=chunk)[0]
+    y = sc.resample_array(api, r, x, rate, chunk=chunk)[0]
     for part in range(w):
         ref, _ = orc.Resample(taps, U, B).stream(x[part::w], rate)
         got = y[part::w]
-        assert len(ref) - len(got) in (0, 1), (seed, U, n_taps, B, rate, len(ref), len(got))
-        assert np.array_equal(got, ref[: len(got)]), (seed, U, n_taps, B, rate, cplx, chunk)
+        sc.check_counts([len(got)], len(ref), r.get_state(), n, U, sc.int_step(rate, U))
+        assert np.array_equal(got, ref), (seed, U, n_taps, B, rate, cplx, chunk)
 
 
 @pytest.mark.parametrize("seed", range(40))
@@ -114,12 +122,12 @@ def test_general_rate_random_shapes_every_bit(api, L, orc, seed):
     r = api.Rs(taps, U, B, mode=L.RS_RESAMPLE, data_complex=cplx)
     r.set_exact(True)
     chunk = int(rng.integers(1, 12)) * B       # bulk calls of whole blksize multiples: the run-length (poly_seg) path
-    y = r.resample_array(x, rate, chunk=chunk)[0]
+    y = sc.resample_array(api, r, x, rate, chunk=chunk)[0]
     for part in range(w):
         ref, _ = orc.Resample(taps, U, B).stream(x[part::w], rate)
         got = np.ascontiguousarray(y[part::w])
-        assert len(ref) - len(got) in (0, 1), (seed, U, n_taps, B, rate, len(ref), len(got))
-        assert np.array_equal(got.view(np.uint32), np.ascontiguousarray(ref[: len(got)]).view(np.uint32)), (seed, U, n_taps, B, rate, cplx, chunk)
+        sc.check_counts([len(got)], len(ref), r.get_state(), n, U, sc.int_step(rate, U))
+        sc.check_values(got, ref, exact=True, label=str((seed, U, n_taps, B, rate, cplx, chunk)))
 
 
 @pytest.mark.parametrize("seed", range(48))
@@ -150,8 +158,8 @@ def test_integer_step_fused_kernels_random_shapes(api, L, orc, seed):
         buf = np.zeros(w * (offset_samples + stride * nch), np.float32)
         for c in range(nch):
             buf[w * (offset_samples + stride * c): w * (offset_samples + stride * c) + w * n] = x[c]
-        d = api.DeviceArray.from_numpy(buf)
-        d_out = api.DeviceArray(w * cap * nch)
+        d = sc.from_numpy(api, buf)
+        d_out = sc.device_array(api, w * cap * nch)
         r = api.Rs(taps, U, B, mode=L.RS_RESAMPLE, data_complex=cplx, n_channels=nch)
         r.set_algo(L.RS_ALGO_DIRECT)
         ks, k = [], 0
@@ -170,8 +178,8 @@ def test_integer_step_fused_kernels_random_shapes(api, L, orc, seed):
     for part in range(w):
         ref, _ = orc.Resample(taps, U, B).stream(np.ascontiguousarray(x[c, part::w]), rate)
         got = y[c, part::w]
-        assert len(ref) - len(got) in (0, 1), (seed, U, step, len(ref), len(got))
-        assert synth.rel_rms(got, ref[: len(got)]) <= 1e-5, (seed, U, step, n_taps, cplx)
+        sc.check_counts(ks, len(ref), None, n, U, step)
+        assert len(got) == len(ref) and synth.rel_rms(got, ref) <= 1e-5, (seed, U, step, n_taps, cplx)
 
 
 @pytest.mark.parametrize("seed", range(16))
@@ -198,7 +206,7 @@ def test_rs_fft_path_random_shapes(api, L, monkeypatch, seed):
         r.set_exact(exact)
         parts = []
         for a, b in zip(cuts[:-1], cuts[1:]):
-            parts.append(r.resample_array(np.ascontiguousarray(x[:, 2 * a: 2 * b]), rate))
+            parts.append(sc.resample_array(api, r, np.ascontiguousarray(x[:, 2 * a: 2 * b]), rate))
         outs[exact] = np.concatenate(parts, axis=1)
         r.close()
     assert outs[False].shape == outs[True].shape, (U, S, n_taps, n, cuts)
@@ -249,10 +257,10 @@ def test_two_thousand_launches_on_one_handle_keep_the_work_counters_clean(api, L
         lens = [int(v) for v in rng.choice([1, 17, 3839, 3840, 3841, 9000, 30721, 100000], size=1000)]
         n = sum(lens)
         x = np.stack([synth.synth_cf32(n, ch=30 + c) for c in range(nch)])
-        whole = api.Fir(taps, data_complex=True, n_channels=nch, algo=L.FIR_ALGO_FFT).filter(x)
+        whole = sc.fir_filter(api, api.Fir(taps, data_complex=True, n_channels=nch, algo=L.FIR_ALGO_FFT), x)
         f = api.Fir(taps, data_complex=True, n_channels=nch, algo=L.FIR_ALGO_FFT)
-        d_in = api.DeviceArray.from_numpy(x)
-        d_out = api.DeviceArray(2 * n * nch)
+        d_in = sc.from_numpy(api, x)
+        d_out = sc.device_array(api, 2 * n * nch)
         off = 0
         for m in lens:                                       # every launch: its own slice of the resident stream
             f.process_stream(d_in.ptr + 8 * off, d_out.ptr + 8 * off, m, in_stride=n, out_stride=n)
@@ -267,14 +275,14 @@ def test_two_thousand_launches_on_one_handle_keep_the_work_counters_clean(api, L
     n = sum(lens)
     x = synth.synth_cf32(n, ch=40)
     r0 = api.Rs(taps3, 3, 4096, mode=L.RS_RESAMPLE, data_complex=True)
-    whole = r0.resample_array(x[None, :], 5.0 / 3.0)[0]
+    whole = sc.resample_array(api, r0, x[None, :], 5.0 / 3.0)[0]
     r = api.Rs(taps3, 3, 4096, mode=L.RS_RESAMPLE, data_complex=True)
-    d_in = api.DeviceArray.from_numpy(x)
-    d_out = api.DeviceArray(2 * (n * 3 // 5 + 16))
+    d_in = sc.from_numpy(api, x)
+    d_out = sc.device_array(api, 2 * (n * 3 // 5 + 16))
     off = k = 0
     for m in lens:
         k += r.process_stream(d_in.ptr + 8 * off, m, d_out.ptr + 8 * k, m * 3 // 5 + 8, 5.0 / 3.0)
         off += m
-    assert abs(k - len(whole) // 2) <= 1
-    got = d_out.to_numpy(2 * min(k, len(whole) // 2))
-    assert synth.rel_rms(got, whole[: len(got)]) <= 2e-6
+    sc.check_counts([k], len(whole) // 2, r.get_state(), n, 3, 5)
+    got = d_out.to_numpy(2 * k)
+    assert synth.rel_rms(got, whole) <= 2e-6

@@ -8,6 +8,7 @@ oracle on the shapes the reference's own driver uses."""
 import numpy as np
 import pytest
 
+import stream_checks as sc
 from simplefe_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -63,21 +64,15 @@ def test_transform_domain_general_rate_random_shapes(api, L, seed):
     x = np.stack([(synth.synth_cf32 if cplx else synth.synth_f32)(n, ch=300 + seed * 4 + c) for c in range(nch)])
     exact, fast = _pair(api, L, taps, U, B, cplx=cplx, nch=nch)
     cuts = sorted(set([0, n] + [int(v) // B * B for v in rng.integers(1, n, size=2)]))     # whole reference calls per piece
-    for a0, a1 in zip(cuts[:-1], cuts[1:]):
-        if a1 == a0:
-            continue
-        m = a1 - a0
-        seg = np.ascontiguousarray(x[:, w * a0: w * a1])
-        d_in = api.DeviceArray.from_numpy(seg)
-        cap = int(m / rate) + 16 + 2 * (m // B + 1)
-        de, df = api.DeviceArray(w * cap * nch), api.DeviceArray(w * cap * nch)
-        ke = exact.process_stream(d_in, m, de, cap, rate)
-        kf = fast.process_stream(d_in, m, df, cap, rate)
-        assert ke == kf, (seed, U, plen, rate, n, a0, ke, kf)
+    ye_all, kes = sc.run_rs(api, exact, x, rate, cuts=cuts)
+    yf_all, kfs = sc.run_rs(api, fast, x, rate, cuts=cuts)
+    assert kes == kfs, (seed, U, plen, rate, n, cuts, kes, kfs)
+    k0 = 0
+    for a0, ke in zip(cuts[:-1], kes):
         if ke == 0:
             continue
-        ye = de.to_numpy().reshape(nch, w * cap)[:, : w * ke]
-        yf = df.to_numpy().reshape(nch, w * cap)[:, : w * kf]
+        ye, yf = ye_all[:, w * k0: w * (k0 + ke)], yf_all[:, w * k0: w * (k0 + ke)]
+        k0 += ke
         for c in range(nch):
             assert synth.rel_rms(yf[c], ye[c]) <= TOL, (seed, U, plen, rate, n, a0, c, synth.rel_rms(yf[c], ye[c]))
             assert np.abs(yf[c] - ye[c]).max() <= 2e-5 * max(1.0, float(np.abs(ye[c]).max())), (seed, U, plen, rate)
@@ -92,7 +87,7 @@ def test_transform_domain_general_rate_against_the_oracle(api, L, orc, g4, rate)
     x = synth.synth_cf32(n, ch=77)
     r = api.Rs(taps, U, 4096, mode=L.RS_RESAMPLE, data_complex=True)
     r.set_algo(L.RS_ALGO_FFT)
-    y = r.resample_array(x, float(np.float32(rate)))[0]
+    y = sc.resample_array(api, r, x, float(np.float32(rate)))[0]
     for part in (0, 1):
         ref, _ = orc.Resample(taps, U, 4096).stream(np.ascontiguousarray(x[part::2]), float(np.float32(rate)))
         got = y[part::2]
@@ -109,17 +104,17 @@ def test_default_dispatch_takes_the_transform_kernel_for_bulk_calls_only(api, L)
     x = synth.synth_cf32(n, ch=5)
     ref = api.Rs(taps, U, 4096, mode=L.RS_RESAMPLE, data_complex=True)
     ref.set_exact(True)
-    want = ref.resample_array(x, rate)[0]
+    want = sc.resample_array(api, ref, x, rate)[0]
     for algo in (L.RS_ALGO_AUTO, L.RS_ALGO_DIRECT, L.RS_ALGO_FFT):
         r = api.Rs(taps, U, 4096, mode=L.RS_RESAMPLE, data_complex=True)
         r.set_algo(algo)
-        got = r.resample_array(x, rate)[0]
+        got = sc.resample_array(api, r, x, rate)[0]
         assert len(got) == len(want) and synth.rel_rms(got, want) <= TOL, algo
     below = float(np.float32(0.77))
     r = api.Rs(taps, U, 4096, mode=L.RS_RESAMPLE, data_complex=True)
     e = api.Rs(taps, U, 4096, mode=L.RS_RESAMPLE, data_complex=True)
     e.set_exact(True)
-    a, b = r.resample_array(x[: 2 << 16], below)[0], e.resample_array(x[: 2 << 16], below)[0]
+    a, b = sc.resample_array(api, r, x[: 2 << 16], below)[0], sc.resample_array(api, e, x[: 2 << 16], below)[0]
     assert len(a) == len(b) and synth.rel_rms(a, b) <= TOL
 
 
@@ -139,15 +134,7 @@ def test_transform_domain_general_rate_u8_input(api, L, orc, cplx, rate):
         r.set_algo(L.RS_ALGO_FFT)
         if fmt == "u8":
             r.set_input_format(L.FMT_U8)
-        got = []
-        for a0, a1 in ((0, 8 * B), (8 * B, 13 * B), (13 * B, n)):
-            m = a1 - a0
-            d_in = api.DeviceArray.from_bytes(b[w * a0:w * a1]) if fmt == "u8" else api.DeviceArray.from_numpy(xf[w * a0:w * a1])
-            cap = int(m / rate) + 64
-            d_out = api.DeviceArray(w * cap)
-            k = r.process_stream(d_in, m, d_out, cap, rate)
-            got.append(d_out.to_numpy(w * k))
-        outs[fmt] = np.concatenate(got)
+        outs[fmt] = sc.run_rs(api, r, b if fmt == "u8" else xf, rate, cuts=[0, 8 * B, 13 * B, n], in_u8=fmt == "u8")[0][0]
     assert np.array_equal(outs["u8"], outs["f32"])
     for part in range(w):
         ref, _ = orc.Resample(taps, U, B).stream(np.ascontiguousarray(xf[part::w]), rate)
@@ -171,14 +158,8 @@ def test_stream_that_ends_on_a_block_seam(api, L, k, cplx):
     w = 2 if cplx else 1
     x = (synth.synth_cf32 if cplx else synth.synth_f32)(n, ch=900 + k)
     exact, fast = _pair(api, L, taps, U, B, cplx=cplx)
-    d_in = api.DeviceArray.from_numpy(x)
-    cap = int(n / rate) + 16 + 2 * (n // B + 1)
-    poison = np.full(w * cap, 7.0e7, dtype=np.float32)
-    de, df = api.DeviceArray.from_numpy(poison), api.DeviceArray.from_numpy(poison)
-    ke = exact.process_stream(d_in, n, de, cap, rate)
-    kf = fast.process_stream(d_in, n, df, cap, rate)
-    assert ke == kf and ke > 0
-    ye, yf = de.to_numpy()[: w * ke], df.to_numpy()[: w * kf]
-    assert np.abs(yf).max() < 1.0e6, "an output of the call was never stored"
+    (ye,), kes = sc.run_rs(api, exact, x, rate)
+    (yf,), kfs = sc.run_rs(api, fast, x, rate)
+    assert kes == kfs and kes[0] > 0
     assert synth.rel_rms(yf, ye) <= TOL
     assert np.abs(yf[-w:] - ye[-w:]).max() <= 2e-5 * max(1.0, float(np.abs(ye).max()))

@@ -4,6 +4,7 @@ Reference state being cut: libdsp/blkconv.cxx:105-109 (m_overlap), resample.cxx:
 import numpy as np
 import pytest
 
+import stream_checks as sc
 from simplefe_amd import shard, synth
 
 pytestmark = pytest.mark.gpu
@@ -21,6 +22,13 @@ def L():
     return lib
 
 
+@pytest.fixture(autouse=True)
+def _guards():
+    """every buffer of a test (stream_checks.Guarded): guards still poison, inputs still what was uploaded"""
+    yield
+    sc.check_guarded()
+
+
 def _fir_spans(api, L, taps, x, spans, cplx, halo_len):
     w = 2 if cplx else 1
     outs = []
@@ -30,12 +38,9 @@ def _fir_spans(api, L, taps, x, spans, cplx, halo_len):
         f = api.Fir(taps, data_complex=cplx, algo=L.FIR_ALGO_FFT)       # one handle per span == per GPU
         lo = max(0, first - halo_len)
         if first > lo:
-            d_h = api.DeviceArray.from_numpy(x[lo * w: first * w])
+            d_h = sc.from_numpy(api, x[lo * w: first * w])
             f.load_history(d_h, first - lo)
-        d_in = api.DeviceArray.from_numpy(x[first * w:(first + count) * w])
-        d_out = api.DeviceArray(count * w)
-        f.process_stream(d_in, d_out, count)
-        outs.append(d_out.to_numpy())
+        outs.append(sc.run_fir(api, f, x[first * w:(first + count) * w])[0])
     return np.concatenate(outs)
 
 
@@ -49,7 +54,7 @@ def test_fir_stream_split_on_transform_boundaries_is_bit_identical(api, L, G):
     taps = synth.taps_cfg2()
     n = 3840 * 37 + 1234
     x = synth.synth_cf32(n)
-    whole = api.Fir(taps, data_complex=True, algo=L.FIR_ALGO_FFT).filter(x)[0]
+    whole = sc.fir_filter(api, api.Fir(taps, data_complex=True, algo=L.FIR_ALGO_FFT), x)[0]
     spans = [shard.span_block(n, G, r, quantum=3840) for r in range(G)]
     assert np.array_equal(_fir_spans(api, L, taps, x, spans, True, 256), whole)
     assert synth.rel_rms(_fir_spans(api, L, taps, x, spans, True, 255), whole) <= 1e-6
@@ -62,7 +67,7 @@ def test_fir_stream_split_anywhere_short_halo_and_real_data(api, L, orc):
     n = 100003
     for cplx in (True, False):
         x = synth.synth_cf32(n) if cplx else synth.synth_f32(n)
-        whole = api.Fir(taps, data_complex=cplx, algo=L.FIR_ALGO_FFT).filter(x)[0]
+        whole = sc.fir_filter(api, api.Fir(taps, data_complex=cplx, algo=L.FIR_ALGO_FFT), x)[0]
         spans = [(0, 33333), (33333, 1), (33334, 40001), (73335, n - 73335)]
         for halo in (110, 5000):
             got = _fir_spans(api, L, taps, x, spans, cplx, halo)
@@ -88,7 +93,7 @@ def test_resampler_stream_split_with_seek(api, L, orc, which, U, S, n_taps):
     for exact in (True, False):
         r0 = api.Rs(taps, U, 4096, mode=mode, data_complex=True)
         r0.set_exact(exact)
-        whole = r0.resample_array(x[None, :], rate)[0]
+        whole = sc.resample_array(api, r0, x[None, :], rate)[0]
         outs, pend = [], 0
         for a, b in zip(cuts[:-1], cuts[1:]):
             r = api.Rs(taps, U, 4096, mode=mode, data_complex=True)      # one handle per span == per GPU
@@ -97,8 +102,8 @@ def test_resampler_stream_split_with_seek(api, L, orc, which, U, S, n_taps):
             pend += r.get_state().leftover
             lo = max(0, a - plen)
             if a > lo:
-                r.load_history(api.DeviceArray.from_numpy(x[2 * lo: 2 * a]), a - lo)
-            outs.append(r.resample_array(x[None, 2 * a: 2 * b], rate)[0])
+                r.load_history(sc.from_numpy(api, x[2 * lo: 2 * a]), a - lo)
+            outs.append(sc.resample_array(api, r, x[None, 2 * a: 2 * b], rate)[0])
         got = np.concatenate(outs)
         assert got.shape == whole.shape
         if exact:
@@ -106,7 +111,8 @@ def test_resampler_stream_split_with_seek(api, L, orc, which, U, S, n_taps):
             for part in (0, 1):
                 ref, _ = getattr(orc, "Resample" if which == "resample" else "Decimate")(taps, U, 4096).stream(
                     np.ascontiguousarray(x[part::2]), rate)
-                assert np.array_equal(got[part::2], ref[: len(got) // 2])
+                sc.check_total(len(got) // 2, len(ref), n, U, rate)
+                assert np.array_equal(got[part::2], ref)
         else:
             assert synth.rel_rms(got, whole) <= 1e-6
     assert pend >= 1 or S == 8        # at least one cut exercised the pending-leftover branch
@@ -120,16 +126,16 @@ def test_general_rate_split_carries_the_state(api, L, orc):
     x = synth.synth_f32(n, ch=9)
     r0 = api.Rs(taps, U, 128, mode=L.RS_RESAMPLE)
     r0.set_exact(True)
-    whole = r0.resample_array(x[None, :], rate)[0]
+    whole = sc.resample_array(api, r0, x[None, :], rate)[0]
     with pytest.raises(api.SfeError):
         api.Rs(taps, U, 128, mode=L.RS_RESAMPLE).seek(1000, rate)
     cut = 128 * 100                        # the reference's chunking (blksize) must line up for the replay
     ra = api.Rs(taps, U, 128, mode=L.RS_RESAMPLE)
     ra.set_exact(True)
-    ya = ra.resample_array(x[None, :cut], rate)[0]
+    ya = sc.resample_array(api, ra, x[None, :cut], rate)[0]
     rb = api.Rs(taps, U, 128, mode=L.RS_RESAMPLE)
     rb.set_exact(True)
     rb.set_state(ra.get_state())
-    rb.load_history(api.DeviceArray.from_numpy(x[cut - 64: cut]), 64)
-    yb = rb.resample_array(x[None, cut:], rate)[0]
+    rb.load_history(sc.from_numpy(api, x[cut - 64: cut]), 64)
+    yb = sc.resample_array(api, rb, x[None, cut:], rate)[0]
     assert np.array_equal(np.concatenate([ya, yb]), whole)
