@@ -1302,6 +1302,86 @@ int sfe_dsp_vit_process_stream(sfe_vit_t h, const void *d_in, size_t in_stride,
                                sfe_stream_t stream);
 int sfe_dsp_vit_destroy(sfe_vit_t h);
 
+/* ------------------------------------------------- burst modulator, bytes to waveform
+ * The transmit mirror of the burst demodulator and the Viterbi decoder: per burst,
+ * ceil(n_info / 8) packed payload bytes on the device become one pulse-shaped frame of complex
+ * baseband samples at a stated place of an output stream, cf32 or the transmit wire format.
+ * Bursts are independent; nothing is carried.  No NCO: frequency placement is sfe_dsp_combine_*'s.
+ * Shape, fixed at create:
+ * Code: K, n_gen, gen, keep, P, terminated, n_info exactly as sfe_dsp_vit_* defines and validates
+ * them (the same checker).  n_gen = 0 means UNCODED: the coded bits are the payload bits; K, gen,
+ * keep, P and terminated are ignored.  n_info in [1, 8192].  n_soft: the number of kept coded
+ * positions (n_info when uncoded).
+ * Mapping: order 2 or 4, the maps SFE_VIT_IN_BPSK / SFE_VIT_IN_QPSK undo.  BPSK: data symbol i =
+ * (amp (1 - 2 c_i), +0).  Gray QPSK: data symbol i = (a4 (1 - 2 c_2i), a4 (1 - 2 c_2i+1)) with
+ * a4 = float32(amp / sqrt 2), formed in float64 and rounded once; an odd n_soft is padded with a 0
+ * bit.  n_data = n_soft or ceil(n_soft / 2).  amp is finite and > 0.
+ * Preamble: p[0 .. Lp) cf32, 0 <= Lp <= 4096, every value finite; the transmitted preamble symbol
+ * is amp p[k], one float32 product per component.  N = Lp + n_data symbols s[0 .. N), the preamble
+ * first.
+ * Pulse: h[0 .. n_taps) real float32, finite; sps in [1, 64]; 1 <= n_taps <= 64 sps;
+ * Q = ceil(n_taps / sps) <= 64 taps per arm; h[i] = 0 for i >= n_taps.
+ * Frame: F = (N + Q - 1) sps samples.
+ * Output format: SFE_FMT_F32 or SFE_FMT_TX10, given at create; there is no setter.
+ * Bits: payload bit t of burst b is bit 7 - (t mod 8) of byte floor(t / 8) at d_bytes + b*in_stride
+ * (MSB-first, the layout sfe_dsp_vit_* writes); pad bits are ignored.  u_t = 0 for t < 0 and for
+ * t >= n_info (the termination tail).  Coded bit (t, j) = parity(reg_t & g_j), bit i of reg_t being
+ * u_(t-i), i < K, for t < T = n_info + (terminated ? K - 1 : 0).  The kept positions, numbered in
+ * the order of (t, j), are coded bits 0 .. n_soft - 1: what sfe_dsp_vit_encode gives.
+ * Waveform: frame sample i = k sps + r, 0 <= r < sps, 0 <= k < N + Q - 1:
+ *   y[i] = sum over q = 0 .. Q-1 of h[q sps + r] s[k - q],
+ * the terms with k - q outside [0, N) or q sps + r >= n_taps skipped; per component the sum is an
+ * fmaf chain from +0 in increasing q.  A symmetric pulse of odd length therefore puts symbol k's
+ * peak at frame sample k sps + (n_taps - 1) / 2.
+ * Placement: a call defines EVERY sample of the output stream [0, n_out).  Burst b's frame occupies
+ * [o_b, o_b + F), o_b = start_base + b*start_step; every sample in no frame is +0.  SFE_EINVAL,
+ * nothing launched: start_base < 0; start_step < F with more than one burst (start_step is ignored
+ * with one); o_(n_bursts-1) + F > n_out; n_out or n_bursts >= 2^31; an odd n_out under TX10.
+ * n_bursts = 0 writes n_out zeros.
+ * TX10: the bytes are exactly sfe_dsp_tx_f32_to_10bit's of the F32 output -- two complex samples
+ * in 5 bytes, the groups aligned to the stream, not to frames: a frame may start in the middle of
+ * a group.  (n_out / 2) * 5 bytes are written.
+ * Promised about bits: the same call gives the same bits on every run; burst b's frame depends on
+ * its bytes and the handle only -- never on b, n_bursts, addresses, strides or offsets; the
+ * device's F32 words and TX10 bytes EQUAL sfe_dsp_mod_plan's, for every input whose partial sums
+ * are zero or normal numbers (nothing is promised otherwise); nothing outside the n_out samples is
+ * written.
+ * A bad argument is SFE_EINVAL on any machine, with a message that starts with "mod: ". */
+typedef void *sfe_mod_t;  /* opaque: one modulator; it owns its taps and its scaled preamble on the device and nothing in it changes after create */
+/* Host-only: the samples of the stream one workgroup writes (a frame is cut into such tiles
+ * wherever they fall, the Q - 1 symbols before a tile derived again) and the LDS it uses. */
+int sfe_dsp_mod_footprint(int *tile_samples, size_t *lds_bytes);
+/* Host-only (no GPU): validates what create validates and reports N, F and n_soft (each pointer
+ * may be NULL); then the placement as process_stream does; then, with out != NULL, writes the
+ * stream by the law above, exactly as stated -- n_out cf32 samples, or (n_out / 2) * 5 bytes under
+ * SFE_FMT_TX10 -- from bytes (host memory laid out as d_bytes; required with n_bursts > 0): the
+ * reference of the device's bits.  in_stride < ceil(n_info / 8) is SFE_ERANGE. */
+int sfe_dsp_mod_plan(int K, int n_gen, const uint32_t *gen, const uint8_t *keep, int P,
+                     int terminated, int n_info, int order, const float *preamble, int n_pre,
+                     int sps, const float *taps, int n_taps, float amp, int out_fmt,
+                     const uint8_t *bytes, size_t in_stride, size_t n_bursts, int64_t start_base,
+                     int64_t start_step, size_t n_out, void *out, int *n_sym, int *frame_len,
+                     size_t *n_soft);
+/* Arguments are checked before the device is touched: SFE_EINVAL for a bad one on any machine,
+ * SFE_ENODEV without a GPU.  gen, keep, preamble and taps are copied. */
+int sfe_dsp_mod_create(int K, int n_gen, const uint32_t *gen, const uint8_t *keep, int P,
+                       int terminated, int n_info, int order, const float *preamble, int n_pre,
+                       int sps, const float *taps, int n_taps, float amp, int out_fmt, int device,
+                       sfe_mod_t *out);
+/* One stream of n_out samples holding n_bursts frames.  *n_written = n_out.  The placement
+ * refusals above; in_stride < ceil(n_info / 8) is SFE_ERANGE; a null d_out, a null d_bytes with
+ * bursts, a cf32 d_out that is not 8-byte aligned (TX10 output and the payload bytes need no
+ * alignment), an in_stride that takes the payloads' byte range to 2^62 and an output byte range
+ * that overlaps the payloads' are SFE_EINVAL; nothing is launched on a refusal.  n_out = 0 is a
+ * no-op.  Asynchronous on `stream`; one kernel launch and nothing else: allocates nothing, does
+ * not synchronise the host, carries no state (there is no reset).  A handle has no setter, so a
+ * call on a stream under graph capture IS supported.  Behind a decoder: its d_bits and out_stride
+ * are the whole glue (a regenerative relay). */
+int sfe_dsp_mod_process_stream(sfe_mod_t h, const void *d_bytes, size_t in_stride, size_t n_bursts,
+                               int64_t start_base, int64_t start_step, void *d_out, size_t n_out,
+                               size_t *n_written, sfe_stream_t stream);
+int sfe_dsp_mod_destroy(sfe_mod_t h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,7 @@ Two layers, both thin:
     transpose, the synthesis filter bank (sfe_dsp_combine_*); `Psd`, the streaming Welch spectrum estimator (sfe_dsp_psd_*);
     `Corr`, the streaming preamble correlator bank (sfe_dsp_corr_*); `Iir`, the streaming biquad-cascade IIR filter
     (sfe_dsp_iir_*); `Beam`, the multi-stream beamformer / stream-mixing bank (sfe_dsp_beam_*); `Cov`, the streaming
-    spatial covariance estimator (sfe_dsp_cov_*).
+    spatial covariance estimator (sfe_dsp_cov_*); `Mod`, the burst modulator (sfe_dsp_mod_*).
 
 Everything computes on the GPU through the C ABI; numpy is only the host container.
 """
@@ -1320,6 +1320,92 @@ class Vit(_Block):
             for d in held:
                 d.free()
         return np.ascontiguousarray(by), np.ascontiguousarray(rec), np.ascontiguousarray(st)
+
+
+def _mod_shape(K, gen, n_info, keep, terminated, order, preamble, sps, taps, amp, out_fmt):
+    """The shape arguments sfe_dsp_mod_plan and sfe_dsp_mod_create share, and what keeps their arrays alive.  gen None or
+    empty: uncoded."""
+    if gen is None or len(gen) == 0:
+        n, gp, kp, P, alive = 0, None, None, 1, ()
+    else:
+        n, gp, kp, P, alive = _vit_code(gen, keep)
+    p, pp = _burst_preamble(preamble if preamble is not None else [])
+    t = np.ascontiguousarray(np.asarray(taps, dtype=np.float32).ravel())
+    head = (int(K), n, gp, kp, P, int(bool(terminated)), int(n_info), int(order), pp if p.size else None, p.size, int(sps),
+            t.ctypes.data_as(C.POINTER(C.c_float)), t.size, float(amp), int(out_fmt))
+    return head, (alive, p, t)
+
+
+def mod_footprint():
+    """sfe_dsp_mod_footprint (host only): (samples of the stream one workgroup writes, the LDS bytes it uses)."""
+    ts, by = C.c_int(0), C.c_size_t(0)
+    check(_l.load().sfe_dsp_mod_footprint(C.byref(ts), C.byref(by)))
+    return ts.value, by.value
+
+
+def mod_plan(K, gen, n_info, taps, sps, keep=None, terminated=True, order=2, preamble=None, amp=1.0, out_fmt=_l.FMT_F32, data=None,
+             n_out=0, start_base=0, start_step=0, n_bursts=None):
+    """sfe_dsp_mod_plan (host only, no GPU): validates and, without data, returns (N symbols per burst, F samples per frame,
+    n_soft) -- after checking the placement too where n_out or n_bursts is given.  With data -- (n_bursts, >= ceil(n_info / 8))
+    uint8 payload bytes, MSB-first -- it writes the stream of n_out samples by the law: returns complex64 (n_out,), or the
+    (n_out / 2) * 5 uint8 bytes of the transmit wire format with FMT_TX10.  These are the device's bits.  gen None: uncoded.
+    Raises SfeError on arguments the block refuses."""
+    head, _alive = _mod_shape(K, gen, n_info, keep, terminated, order, preamble, sps, taps, amp, out_fmt)
+    L, N, F, ns = _l.load(), C.c_int(0), C.c_int(0), C.c_size_t(0)
+    tail = (C.byref(N), C.byref(F), C.byref(ns))
+    if data is None:
+        check(L.sfe_dsp_mod_plan(*head, None, 0, int(n_bursts or 0), int(start_base), int(start_step), int(n_out), None, *tail))
+        return N.value, F.value, ns.value
+    d = np.asarray(data, dtype=np.uint8)
+    d = np.ascontiguousarray(d.reshape(1, -1) if d.ndim == 1 else d)
+    nb = d.shape[0] if n_bursts is None else int(n_bursts)
+    n_out = max(int(n_out), 0)
+    out = np.empty(n_out // 2 * 5, np.uint8) if out_fmt == _l.FMT_TX10 else np.empty(n_out, np.complex64)
+    check(L.sfe_dsp_mod_plan(*head, d.ctypes.data_as(C.POINTER(C.c_uint8)), d.shape[1] if d.size else 0, nb, int(start_base), int(start_step),
+                             n_out, out.ctypes.data if out.size else None, *tail))
+    return out
+
+
+class Mod(_Block):
+    """Burst modulator (sfe_dsp_mod_*): per burst, ceil(n_info / 8) packed payload bytes on the device -- what a Vit wrote,
+    say -- are encoded, mapped to BPSK or Gray QPSK behind a preamble, pulse-shaped and written as one frame of an output
+    stream, cf32 or (out_fmt FMT_TX10) the transmit wire format; every other sample of the stream is written as zero.
+    The device's bits are mod_plan's."""
+    _prefix = "mod"
+
+    def __init__(self, K, gen, n_info, taps, sps, keep=None, terminated=True, order=2, preamble=None, amp=1.0, out_fmt=_l.FMT_F32, device=0):
+        head, _alive = _mod_shape(K, gen, n_info, keep, terminated, order, preamble, sps, taps, amp, out_fmt)
+        self.n_info, self.sps, self.order, self.out_fmt = int(n_info), int(sps), int(order), int(out_fmt)
+        self.n_bytes = (max(self.n_info, 0) + 7) // 8
+        self._create(*head, device)
+        self.n_sym, self.frame_len, self.n_soft = mod_plan(K, gen, n_info, taps, sps, keep, terminated, order, preamble, amp, out_fmt)
+
+    def process_stream(self, d_bytes, n_bursts, d_out, n_out, start_base=0, start_step=0, in_stride=None, stream=None):
+        """d_*: DeviceArray or raw device pointers.  Burst b reads n_bytes bytes at d_bytes + b*in_stride (bytes; default
+        n_bytes) and its frame_len samples start at sample start_base + b*start_step of the n_out samples at d_out (cf32, or
+        5-byte groups of two samples with FMT_TX10); the call writes all n_out samples.  Returns n_out."""
+        k = C.c_size_t(0)
+        check(self._fn("process_stream")(self._h, self._ptr(d_bytes), self.n_bytes if in_stride is None else int(in_stride), int(n_bursts),
+                                         int(start_base), int(start_step), self._ptr(d_out), int(n_out), C.byref(k), stream))
+        return k.value
+
+    def reset(self):
+        raise AttributeError("Mod has no reset: it carries no state")
+
+    def modulate(self, data, n_out, start_base=0, start_step=0):
+        """Host convenience, computed on the GPU: data is (n_bursts, n_bytes) uint8; returns what mod_plan returns."""
+        d = np.asarray(data, dtype=np.uint8)
+        d = np.ascontiguousarray(d.reshape(1, -1) if d.ndim == 1 else d)
+        tx10 = self.out_fmt == _l.FMT_TX10
+        nbytes = int(n_out) // 2 * 5 if tx10 else 8 * int(n_out)
+        held = [DeviceArray.from_bytes(d), DeviceArray(max(1, (nbytes + 3) // 4))]
+        try:
+            self.process_stream(held[0], d.shape[0], held[1], n_out, start_base, start_step, in_stride=d.shape[1])
+            raw = held[1].to_numpy().view(np.uint8)[:nbytes]
+        finally:
+            for x in held:
+                x.free()
+        return np.ascontiguousarray(raw) if tx10 else np.ascontiguousarray(raw).view(np.complex64)
 
 
 def rs_plan(state, upsample, n_in, out_len, rate):

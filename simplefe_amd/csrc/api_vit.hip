@@ -8,68 +8,36 @@
 #include "host.h"
 #include "block.h"
 #include "vit.h"
+#include "vit_code.h"
 
 namespace sfe {
-namespace {
 
-// a validated code, burst shape and input mode
-struct VitCode {
-    int K = 0, n = 0, P = 1, terminated = 1, n_info = 0, T = 0, n_soft = 0, per_period = 0, in_mode = 0, skip = 0;
-    unsigned gen[VIT_MAX_GEN] = {0, 0, 0, 0};
-    unsigned long long keep_lo = 0, keep_hi = 0;    // bit 4 (t mod P) + j: position (t, j) is transmitted
-
-    int S() const { return vit_states(K); }
-    bool kept(int tp, int j) const
-    {
-        const int bit = 4 * tp + j;
-        return ((bit < 64 ? keep_lo : keep_hi) >> (bit & 63)) & 1ull;
-    }
-    unsigned label(unsigned reg) const          // bit j: coded bit c_j of the shift register reg
-    {
-        unsigned l = 0;
-        for (int j = 0; j < n; j++) l |= (unsigned)(__builtin_popcount(reg & gen[j]) & 1) << j;
-        return l;
-    }
-    // floats per burst row element, and where soft value i lies: the float at in_off() + i in_mul()
-    int elem_floats() const { return in_mode == SFE_VIT_IN_SOFT ? 1 : 2; }
-    int in_off() const { return in_mode == SFE_VIT_IN_SOFT ? 0 : 2 * skip; }
-    int in_mul() const { return in_mode == SFE_VIT_IN_BPSK ? 2 : 1; }
-    // elements of the mode's type a burst's row must hold
-    size_t row_elems() const
-    {
-        if (in_mode == SFE_VIT_IN_SOFT) return (size_t)n_soft;
-        return (size_t)skip + (in_mode == SFE_VIT_IN_BPSK ? (size_t)n_soft : ((size_t)n_soft + 1) / 2);
-    }
-};
-
-constexpr int VIT_MAX_SKIP = 1 << 24;
-
-// the code alone: what encode needs
-int vit_check_code(int K, int n_gen, const uint32_t *gen, const uint8_t *keep, int P, int terminated, size_t n_info, VitCode *c)
+// the code alone: what encode needs, and what the modulator (api_mod.hip) shares; `who` is the message prefix
+int vit_check_code(const char *who, int K, int n_gen, const uint32_t *gen, const uint8_t *keep, int P, int terminated, size_t n_info, VitCode *c)
 {
     if (K < VIT_MIN_K || K > VIT_MAX_K) {
-        set_error("vit: K = %d must be in [%d, %d]", K, VIT_MIN_K, VIT_MAX_K);
+        set_error("%s: K = %d must be in [%d, %d]", who, K, VIT_MIN_K, VIT_MAX_K);
         return SFE_EINVAL;
     }
     if (n_gen < VIT_MIN_GEN || n_gen > VIT_MAX_GEN) {
-        set_error("vit: n_gen = %d must be in [%d, %d]", n_gen, VIT_MIN_GEN, VIT_MAX_GEN);
+        set_error("%s: n_gen = %d must be in [%d, %d]", who, n_gen, VIT_MIN_GEN, VIT_MAX_GEN);
         return SFE_EINVAL;
     }
     if (!gen) {
-        set_error("vit: null generators");
+        set_error("%s: null generators", who);
         return SFE_EINVAL;
     }
     for (int j = 0; j < n_gen; j++)
         if (gen[j] == 0 || gen[j] >= (1u << K)) {
-            set_error("vit: generator %d = 0%o must be in (0, 2^K = %u)", j, gen[j], 1u << K);
+            set_error("%s: generator %d = 0%o must be in (0, 2^K = %u)", who, j, gen[j], 1u << K);
             return SFE_EINVAL;
         }
     if (terminated != 0 && terminated != 1) {
-        set_error("vit: terminated = %d must be 0 (truncated) or 1 (K - 1 zero bits follow the payload)", terminated);
+        set_error("%s: terminated = %d must be 0 (truncated) or 1 (K - 1 zero bits follow the payload)", who, terminated);
         return SFE_EINVAL;
     }
     if (n_info < 1 || n_info > (size_t)VIT_MAX_INFO) {
-        set_error("vit: n_info = %zu must be in [1, %d]", n_info, VIT_MAX_INFO);
+        set_error("%s: n_info = %zu must be in [1, %d]", who, n_info, VIT_MAX_INFO);
         return SFE_EINVAL;
     }
     c->K = K, c->n = n_gen, c->terminated = terminated, c->n_info = (int)n_info;
@@ -80,7 +48,7 @@ int vit_check_code(int K, int n_gen, const uint32_t *gen, const uint8_t *keep, i
         c->keep_lo = (1ull << n_gen) - 1ull;
     } else {
         if (P < 1 || P > VIT_MAX_PERIOD) {
-            set_error("vit: puncturing period P = %d must be in [1, %d]", P, VIT_MAX_PERIOD);
+            set_error("%s: puncturing period P = %d must be in [1, %d]", who, P, VIT_MAX_PERIOD);
             return SFE_EINVAL;
         }
         c->P = P;
@@ -88,7 +56,7 @@ int vit_check_code(int K, int n_gen, const uint32_t *gen, const uint8_t *keep, i
             for (int j = 0; j < n_gen; j++) {
                 const uint8_t k = keep[tp * n_gen + j];
                 if (k > 1) {
-                    set_error("vit: keep[%d][%d] = %d must be 0 or 1", tp, j, (int)k);
+                    set_error("%s: keep[%d][%d] = %d must be 0 or 1", who, tp, j, (int)k);
                     return SFE_EINVAL;
                 }
                 if (k) (4 * tp + j < 64 ? c->keep_lo : c->keep_hi) |= 1ull << ((4 * tp + j) & 63);
@@ -96,24 +64,28 @@ int vit_check_code(int K, int n_gen, const uint32_t *gen, const uint8_t *keep, i
     }
     c->per_period = __builtin_popcountll(c->keep_lo) + __builtin_popcountll(c->keep_hi);
     if (c->per_period == 0) {
-        set_error("vit: the puncturing pattern keeps no position");
+        set_error("%s: the puncturing pattern keeps no position", who);
         return SFE_EINVAL;
     }
     long long ns = (long long)(c->T / c->P) * c->per_period;
     for (int tp = 0; tp < c->T % c->P; tp++)
         for (int j = 0; j < n_gen; j++) ns += c->kept(tp, j);
     if (ns == 0) {
-        set_error("vit: the puncturing pattern keeps none of the burst's T = %d steps' positions", c->T);
+        set_error("%s: the puncturing pattern keeps none of the burst's T = %d steps' positions", who, c->T);
         return SFE_EINVAL;
     }
     c->n_soft = (int)ns;
     return SFE_OK;
 }
 
+namespace {
+
+constexpr int VIT_MAX_SKIP = 1 << 24;
+
 // what plan and create validate
 int vit_check(int K, int n_gen, const uint32_t *gen, const uint8_t *keep, int P, int terminated, int n_info, int in_mode, int skip, VitCode *c)
 {
-    const int rc = vit_check_code(K, n_gen, gen, keep, P, terminated, n_info < 0 ? 0 : (size_t)n_info, c);
+    const int rc = vit_check_code("vit", K, n_gen, gen, keep, P, terminated, n_info < 0 ? 0 : (size_t)n_info, c);
     if (rc != SFE_OK) return rc;
     if (in_mode != SFE_VIT_IN_SOFT && in_mode != SFE_VIT_IN_BPSK && in_mode != SFE_VIT_IN_QPSK) {
         set_error("vit: in_mode = %d must be SFE_VIT_IN_SOFT, SFE_VIT_IN_BPSK or SFE_VIT_IN_QPSK", in_mode);
@@ -240,7 +212,7 @@ int sfe_dsp_vit_encode(int K, int n_gen, const uint32_t *gen, const uint8_t *kee
 {
     if (n_coded) *n_coded = 0;
     VitCode c;
-    const int rc = vit_check_code(K, n_gen, gen, keep, P, terminated, n_info, &c);
+    const int rc = vit_check_code("vit", K, n_gen, gen, keep, P, terminated, n_info, &c);
     if (rc != SFE_OK) return rc;
     if (!n_coded) {
         set_error("vit: null n_coded");
@@ -272,7 +244,7 @@ int sfe_dsp_vit_footprint(int K, int n_gen, int terminated, int n_info, size_t *
 {
     const uint32_t one[VIT_MAX_GEN] = {1, 1, 1, 1};
     VitCode c;
-    const int rc = vit_check_code(K, n_gen, one, nullptr, 1, terminated, n_info < 0 ? 0 : (size_t)n_info, &c);
+    const int rc = vit_check_code("vit", K, n_gen, one, nullptr, 1, terminated, n_info < 0 ? 0 : (size_t)n_info, &c);
     if (rc != SFE_OK) return rc;
     if (lds_bytes) *lds_bytes = vit_base_bytes(K, c.T, n_info);
     if (staged) *staged = vit_staged(K, n_gen, c.T, n_info) ? 1 : 0;

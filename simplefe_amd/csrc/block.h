@@ -1,5 +1,5 @@
 // block.h -- what the handles of the streaming blocks share (api_chan.hip, api_combine.hip, api_ddc.hip, api_psd.hip,
-// api_corr.hip, api_iir.hip, api_beam.hip, api_cov.hip, api_mvdr.hip, api_eig.hip, api_burst.hip, api_vit.hip): owners of their device memory, the device scope of a create, the handle cast, the table
+// api_corr.hip, api_iir.hip, api_beam.hip, api_cov.hip, api_mvdr.hip, api_eig.hip, api_burst.hip, api_vit.hip, api_mod.hip): owners of their device memory, the device scope of a create, the handle cast, the table
 // of the unit circle, and the checks every process_stream opens with.  HOST CODE ONLY, like host.h; include it after
 // host.h.  A block's struct names its magic as `static constexpr uint32_t MAGIC` and carries `magic` and `device`.
 #pragma once

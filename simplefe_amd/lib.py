@@ -183,6 +183,13 @@ SIGNATURES = {
     "sfe_dsp_vit_create": (i32, [i32, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), i32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
     "sfe_dsp_vit_process_stream": (i32, [vp, vp, sz, vp, sz, vp, sz, vp, vp, C.POINTER(sz), vp]),
     "sfe_dsp_vit_destroy": (i32, [vp]),
+    "sfe_dsp_mod_footprint": (i32, [C.POINTER(i32), C.POINTER(sz)]),
+    "sfe_dsp_mod_plan": (i32, [i32, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), i32, i32, i32, i32, fp, i32, i32, fp, i32, f32, i32,
+                               C.POINTER(C.c_uint8), sz, sz, C.c_int64, C.c_int64, sz, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(sz)]),
+    "sfe_dsp_mod_create": (i32, [i32, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), i32, i32, i32, i32, fp, i32, i32, fp, i32, f32, i32, i32,
+                                 C.POINTER(vp)]),
+    "sfe_dsp_mod_process_stream": (i32, [vp, vp, sz, sz, C.c_int64, C.c_int64, vp, sz, C.POINTER(sz), vp]),
+    "sfe_dsp_mod_destroy": (i32, [vp]),
 }
 
 # the diagnostic library only (simplefe_amd/csrc/diag/sfe_dsp_diag.h; scripts/ load it by pointing LIB_PATH at it): bound when present

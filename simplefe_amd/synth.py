@@ -801,3 +801,69 @@ def vit_symbols(coded, order=2):
     if c.size & 1:
         c = np.concatenate([c, [0.0]])
     return ((1.0 - 2.0 * c[0::2]) + 1j * (1.0 - 2.0 * c[1::2])) / np.sqrt(2.0)
+
+
+# ---- the burst modulator (sfe_dsp_mod_*): the law restated in numpy, and the transmit wire format on the host
+def mod_symbols(coded, order, amp, preamble=None):
+    """The N symbols of one burst as complex64, float32 components exactly as the law forms them: amp * p[k] (one float32
+    product per component) for the preamble, then the coded bits as BPSK (amp (1 - 2c), +0) or Gray QPSK (float32(amp /
+    sqrt 2) per component, an odd count padded with a 0 bit)."""
+    amp = np.float32(amp)
+    c = np.asarray(coded, dtype=np.uint8).ravel()
+    if order == 2:
+        re, im = np.where(c == 1, -amp, amp).astype(np.float32), np.zeros(c.size, np.float32)
+    else:
+        if c.size & 1:
+            c = np.concatenate([c, np.zeros(1, np.uint8)])
+        a4 = np.float32(np.float64(amp) / np.sqrt(np.float64(2.0)))
+        re, im = np.where(c[0::2] == 1, -a4, a4).astype(np.float32), np.where(c[1::2] == 1, -a4, a4).astype(np.float32)
+    s = np.empty(re.size, np.complex64)
+    s.real, s.imag = re, im
+    if preamble is None or len(preamble) == 0:
+        return s
+    p = np.asarray(preamble, dtype=np.complex64).ravel()
+    ps = np.empty(p.size, np.complex64)
+    ps.real, ps.imag = amp * p.real, amp * p.imag
+    return np.concatenate([ps, s])
+
+
+def mod_reference(symbols, taps, sps, absolute=False):
+    """The modulator's waveform law in float64: frame sample k sps + r = sum over q of h[q sps + r] s[k - q], h zero from
+    n_taps on, s zero outside [0, N) -- the (N + Q - 1) sps samples of one frame as complex128.  absolute: the same sum
+    on |h| and on |Re s|, |Im s| (the A of the direct-sum error bound)."""
+    s = np.asarray(symbols).astype(np.complex128).ravel()
+    h = np.asarray(taps, dtype=np.float32).astype(np.float64).ravel()
+    sps = int(sps)
+    Q = -(-h.size // sps)
+    hp = np.concatenate([h, np.zeros(Q * sps - h.size)])
+    if absolute:
+        s, hp = np.abs(s.real) + 1j * np.abs(s.imag), np.abs(hp)
+    y = np.zeros((s.size + Q - 1, sps), np.complex128)
+    for q in range(Q):                                  # arm r of row k gets h[q sps + r] s[k - q]
+        y[q:q + s.size, :] += s[:, None] * hp[None, q * sps:(q + 1) * sps]
+    return y.ravel()
+
+
+def tx10_pack(x):
+    """The transmit converter's law (sfe_dsp_tx_f32_to_10bit) on the host: float32 values, four to a 5-byte group, each
+    ((short)(x * 511) + 512) & 0x3FF -- the high two bits of the four in byte 0, the low bytes behind it."""
+    x = np.ascontiguousarray(x).view(np.float32).ravel()
+    u = ((x * np.float32(511)).astype(np.int32).astype(np.int16).astype(np.int32) + 512) & 0x3FF
+    u = u[:u.size // 4 * 4].reshape(-1, 4)
+    out = np.empty((u.shape[0], 5), np.uint8)
+    out[:, 0] = (u[:, 0] >> 8) | ((u[:, 1] >> 8) << 2) | ((u[:, 2] >> 8) << 4) | ((u[:, 3] >> 8) << 6)
+    out[:, 1:] = u & 0xFF
+    return out.ravel()
+
+
+def tx10_unpack(b):
+    """The values a receiver of the transmit wire format sees, float32: (u - 512) / 511 of each 10-bit word."""
+    b = np.asarray(b, dtype=np.uint8).reshape(-1, 5).astype(np.int32)
+    hi = np.stack([(b[:, 0] >> (2 * i)) & 3 for i in range(4)], axis=1)
+    return ((((hi << 8) | b[:, 1:]) - 512).astype(np.float32) / np.float32(511)).ravel()
+
+
+def f32_to_u8(x):
+    """float32 values requantised to the receive wire format: the byte nearest to 127 x + 128, clipped to [0, 255]."""
+    x = np.ascontiguousarray(x).view(np.float32).ravel().astype(np.float64)
+    return np.clip(np.rint(x * 127.0 + 128.0), 0, 255).astype(np.uint8)
