@@ -6,42 +6,10 @@ namespace sfe {
 
 // ------------------------------------------------------------------------------ FIR
 
-Fir *as_fir(void *h)
-{
-    Fir *f = static_cast<Fir *>(h);
-    if (f && f->magic != 0x46495231u) {
-        set_error("not a live FIR handle");
-        return nullptr;
-    }
-    return f;
-}
+Fir *as_fir(void *h) { return as_handle<Fir>(h, "FIR"); }
 
-void fir_free(Fir *f)
-{
-    if (!f) return;
-    f->magic = 0;
-    DeviceGuard g(f->device);
-    if (f->d_hs) (void)hipFree(f->d_hs);
-    if (f->d_tw1) (void)hipFree(f->d_tw1);
-    if (f->d_tw2) (void)hipFree(f->d_tw2);
-    if (f->d_ticket) (void)hipFree(f->d_ticket);
-    if (f->d_taps) (void)hipFree(f->d_taps);
-    f->plans.clear();
-    for (int i = 0; i < 2; i++)
-        if (f->d_hist[i]) (void)hipFree(f->d_hist[i]);
-    if (f->h_buf) (void)hipHostFree(f->h_buf);
-    if (f->d_blk_in) (void)hipFree(f->d_blk_in);
-    if (f->d_blk_out) (void)hipFree(f->d_blk_out);
-    if (f->h_blk_out) (void)hipHostFree(f->h_blk_out);
-    if (f->h_stage_out) (void)hipHostFree(f->h_stage_out);
-    if (f->h_stage) (void)hipHostFree(f->h_stage);
-    if (f->d_st_in) (void)hipFree(f->d_st_in);
-    if (f->d_st_out) (void)hipFree(f->d_st_out);
-    if (f->stream) (void)hipStreamDestroy(f->stream);
-    delete f;
-}
-
-static int fir_build_tables(Fir *f, const float *taps)
+// the tables of the 4096-point kernel for `parts` partitions at overlap `ovl`; the rest of the shape is the handle's
+static int fir_build_tables(const Fir *f, const float *taps, int parts, int ovl, FirTables &t)
 {
     const int N = FFT_N;
     // spectrum of each zero-padded tap partition in double precision, scaled by 1/N (blkconv.cxx:50
@@ -81,13 +49,13 @@ static int fir_build_tables(Fir *f, const float *taps)
     };
     // one set of spectra per tap vector: one for all channels, or (per_channel) channel by channel, [set][partition][k0][t]
     const int n_sets = f->per_channel ? f->n_channels : 1;
-    std::vector<v2f> hs((size_t)n_sets * f->parts * 16 * 256), tw1(7 * 256), tw2(7 * 16);
+    std::vector<v2f> hs((size_t)n_sets * parts * 16 * 256), tw1(7 * 256), tw2(7 * 16);
     std::vector<double> hr(N), hi(N);
     for (int set = 0; set < n_sets; set++) {
     const float *tp = taps + (size_t)set * f->n_taps * (f->taps_complex ? 2 : 1);
-    for (int p = 0; p < f->parts; p++) {
-        const int first = f->parts == 1 ? 0 : p * f->ovl;
-        const int count = f->parts == 1 ? f->n_taps : (f->n_taps - first < f->ovl ? f->n_taps - first : f->ovl);
+    for (int p = 0; p < parts; p++) {
+        const int first = parts == 1 ? 0 : p * ovl;
+        const int count = parts == 1 ? f->n_taps : (f->n_taps - first < ovl ? f->n_taps - first : ovl);
         for (int n = 0; n < N; n++) {
             hr[n] = n < count ? (f->taps_complex ? tp[2 * (first + n)] : tp[first + n]) / (double)N : 0.0;
             hi[n] = n < count && f->taps_complex ? tp[2 * (first + n) + 1] / (double)N : 0.0;
@@ -96,7 +64,7 @@ static int fir_build_tables(Fir *f, const float *taps)
         for (int t = 0; t < 256; t++)
             for (int k0 = 0; k0 < 16; k0++) {
                 const int bin = (t >> 4) + 16 * (t & 15) + 256 * k0;
-                hs[(((size_t)set * f->parts + p) * 16 + k0) * 256 + t] = (v2f){(float)hr[bin], (float)hi[bin]};
+                hs[(((size_t)set * parts + p) * 16 + k0) * 256 + t] = (v2f){(float)hr[bin], (float)hi[bin]};
             }
     }
     }
@@ -114,15 +82,9 @@ static int fir_build_tables(Fir *f, const float *taps)
             tw2[k * 16 + n0] = (v2f){(float)cos(a), (float)sin(a)};
             tw2[(k + 3) * 16 + n0] = (v2f){(float)cos(4.0 * a), (float)sin(4.0 * a)};
         }
-    SFE_HIP(hipMalloc(&f->d_hs, hs.size() * sizeof(v2f)));
-    SFE_HIP(hipMalloc(&f->d_tw1, tw1.size() * sizeof(v2f)));
-    SFE_HIP(hipMalloc(&f->d_tw2, tw2.size() * sizeof(v2f)));
-    SFE_HIP(hipMemcpy(f->d_hs, hs.data(), hs.size() * sizeof(v2f), hipMemcpyHostToDevice));
-    SFE_HIP(hipMemcpy(f->d_tw1, tw1.data(), tw1.size() * sizeof(v2f), hipMemcpyHostToDevice));
-    SFE_HIP(hipMemcpy(f->d_tw2, tw2.data(), tw2.size() * sizeof(v2f), hipMemcpyHostToDevice));
-    SFE_HIP(hipMalloc(&f->d_ticket, FIR_TICKET_GROUPS_MAX * 128));
-    SFE_HIP(hipMemset(f->d_ticket, 0, FIR_TICKET_GROUPS_MAX * 128));
-    return SFE_OK;
+    int rc;
+    if ((rc = t.hs.upload(hs)) != SFE_OK || (rc = t.tw1.upload(tw1)) != SFE_OK || (rc = t.tw2.upload(tw2)) != SFE_OK) return rc;
+    return t.ticket.alloc_zero(FIR_TICKET_GROUPS_MAX * 128 / sizeof(unsigned));
 }
 
 // How a tap count is cut for the 4096-point kernel.  One launch with overlap hl costs ~1/(4096-hl) per
@@ -225,14 +187,12 @@ static int fir_calibrate(Fir *f, FirFftArgs &a, hipStream_t s, int *chosen)
 {
     *chosen = FIR_VAR_REG;
     if (!fir_has_variants(f, a)) return SFE_OK;             // one variant: nothing to choose
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
-        if (e0) (void)hipEventDestroy(e0);
-        return hip_fail(hipGetLastError(), "fir_calibrate: hipEventCreate");
-    }
+    Event e0, e1;
+    int rc = e0.create(hipEventDefault);
+    if (rc == SFE_OK) rc = e1.create(hipEventDefault);
+    if (rc != SFE_OK) return rc;
     const int nvar = f->per_channel ? 2 : FIR_VAR_COUNT;      // per-channel taps: no wave-private instantiation
     float t[FIR_VAR_COUNT][FIR_CAL_ROUNDS];
-    int rc = SFE_OK;
     // interleaved rounds; a measurement made on a chip that has just come out of idle ranks the variants by
     // how they run at a clock the stream will never see again, so rounds go on until FIR_CAL_WARM_MS of
     // launches have run (and at least FIR_CAL_ROUNDS rounds) and only the last FIR_CAL_ROUNDS count
@@ -253,8 +213,6 @@ static int fir_calibrate(Fir *f, FirFftArgs &a, hipStream_t s, int *chosen)
                 spent += ms;
             }
         }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     if (rc != SFE_OK) return rc;
     // Register loads are the reference point: with the straight-line store block they are the fastest or within
     // 0.5 % of it on every box of profiles/r03/fir_variants_box*.txt, where the three medians of one measurement lie
@@ -287,9 +245,9 @@ static void fir_fill_args(const Fir *f, FirFftArgs &a, const void *d_in, void *d
 {
     a.in = d_in;
     a.out = d_out;
-    a.hist = f->d_hist[f->cur];
-    a.tw1 = f->d_tw1;
-    a.tw2 = f->d_tw2;
+    a.hist = f->hist.cur();
+    a.tw1 = f->tab.tw1;
+    a.tw2 = f->tab.tw2;
     a.n = (long long)n;
     a.in_stride = (long long)in_stride;
     a.out_stride = (long long)out_stride;
@@ -297,37 +255,35 @@ static void fir_fill_args(const Fir *f, FirFftArgs &a, const void *d_in, void *d
     a.advance = FFT_N - f->ovl;
     a.hist_len = f->hl;
     a.nblk = ((long long)n + a.advance - 1) / a.advance;
-    a.ticket = f->d_ticket;
+    a.ticket = f->tab.ticket;
     a.total = 0;
     a.tgroups = 0;
     a.hs_stride = f->per_channel ? (long long)f->parts * 16 * 256 : 0;
     a.variant = FIR_VAR_AUTO;
-    a.hs = f->d_hs;
+    a.hs = f->tab.hs;
     a.shift = 0;
     a.hist_out = nullptr;
 }
 
 // Behind a call's launches: the state the NEXT call starts from.  `fused`: the main launch already wrote
-// it into d_hist[cur ^ 1].  A handle one of whose calls sits in a hipGraph keeps its state in d_hist[cur]
+// it into hist.next().  A handle one of whose calls sits in a hipGraph keeps its state in hist.cur()
 // for good -- the graph names that buffer -- so an eager call on such a handle copies the new state back
-// instead of flipping (a replay after an eager call used to read the stale buffer).
+// instead of flipping (CarriedPair::carry; ADVICE r3: a replay after an eager call used to read the stale buffer).
 static int fir_carry_state(Fir *f, const void *d_in, size_t n, size_t in_stride, bool fused, bool capturing, hipStream_t s)
 {
     const int width = f->data_complex ? 2 : 1;
     if (capturing) {
         // in place, behind everything that read the old history: with n >= hl the kernel reads `in` only
         f->captured = true;
-        return launch_history_update(d_in, (long long)n, (long long)in_stride, f->d_hist[f->cur], f->d_hist[f->cur], f->hl,
+        return launch_history_update(d_in, (long long)n, (long long)in_stride, f->hist.cur(), f->hist.cur(), f->hl,
                                      width, f->n_channels, s, f->in_u8);
     }
     if (!fused) {
-        int rc = launch_history_update(d_in, (long long)n, (long long)in_stride, f->d_hist[f->cur], f->d_hist[f->cur ^ 1],
+        int rc = launch_history_update(d_in, (long long)n, (long long)in_stride, f->hist.cur(), f->hist.next(),
                                        f->hl, width, f->n_channels, s, f->in_u8);
         if (rc != SFE_OK) return rc;
     }
-    if (f->captured) SFE_HIP(hipMemcpyAsync(f->d_hist[f->cur], f->d_hist[f->cur ^ 1], f->hist_bytes(), hipMemcpyDeviceToDevice, s));
-    else f->cur ^= 1;
-    return SFE_OK;
+    return f->hist.carry(f->captured, s);
 }
 
 int fir_run(Fir *f, const void *d_in, void *d_out, size_t n, size_t in_stride,
@@ -359,9 +315,9 @@ int fir_run(Fir *f, const void *d_in, void *d_out, size_t n, size_t in_stride,
         // one launch per tap partition: partition p filters the stream delayed by p*ovl samples and
         // (p > 0) adds to what the earlier ones wrote
         for (int p = 0; p < f->parts && rc == SFE_OK; p++) {
-            a.hs = f->d_hs + (size_t)p * 16 * 256;
+            a.hs = f->tab.hs.p + (size_t)p * 16 * 256;
             a.shift = p * f->ovl;
-            a.hist_out = (p == 0 && hist_fused) ? f->d_hist[f->cur ^ 1] : nullptr;
+            a.hist_out = (p == 0 && hist_fused) ? f->hist.next() : nullptr;
             rc = launch_fir_fft(a, f->data_complex, f->out_complex, f->in_u8, f->out_tx10, f->n_channels, s, p > 0);
         }
     } else {
@@ -375,7 +331,7 @@ int fir_run(Fir *f, const void *d_in, void *d_out, size_t n, size_t in_stride,
             PolyTiledArgs ta;
             ta.in = d_in;
             ta.out = d_out;
-            ta.hist = f->d_hist[f->cur];
+            ta.hist = f->hist.cur();
             ta.G = pl->d_G;
             ta.Gt = pl->d_Gt;
             ta.n_in = (long long)n;
@@ -391,7 +347,7 @@ int fir_run(Fir *f, const void *d_in, void *d_out, size_t n, size_t in_stride,
             memset(&a, 0, sizeof(a));
             a.in = d_in;
             a.out = d_out;
-            a.hist = f->d_hist[f->cur];
+            a.hist = f->hist.cur();
             a.taps = f->d_taps;
             a.n_in = (long long)n;
             a.in_stride = (long long)in_stride;
@@ -422,12 +378,9 @@ int fir_create_impl(const float *taps, int n_taps, int taps_complex, int data_co
         set_error("fir_create: fft_len %d leaves no block for %d taps (blkconv.cxx:47)", block_hint, n_taps);
         return SFE_EINVAL;
     }
-    int prev_dev = -1;
-    (void)hipGetDevice(&prev_dev);
-    int rc = use_device(device);
-    if (rc != SFE_OK) return rc;
-    struct Restore { int d; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore__{prev_dev};
-    Fir *f = new (std::nothrow) Fir;
+    CreateScope scope(device);
+    if (scope.rc != SFE_OK) return scope.rc;
+    std::unique_ptr<Fir> f(new (std::nothrow) Fir);
     if (!f) return SFE_ENOMEM;
     f->n_taps = n_taps;
     f->taps_complex = taps_complex ? 1 : 0;
@@ -440,45 +393,35 @@ int fir_create_impl(const float *taps, int n_taps, int taps_complex, int data_co
     f->blk = block_hint ? block_hint + 1 - n_taps : 0;
     f->fft_ok = fir_choose_partition(n_taps, &f->ovl, &f->parts);
     if (f->per_channel && !f->fft_ok) {
-        delete f;
         set_error("fir_create_per_channel: %d taps exceed %d partitions of the 4096-point kernel", n_taps, FIR_MAX_PARTS);
         return SFE_ERANGE;
     }
     if (f->fft_ok) f->hl = f->parts * f->ovl;                       // history the slowest partition reaches back to
     else f->hl = ((n_taps - 1 + 255) / 256) * 256;                  // beyond FIR_MAX_PARTS partitions: direct kernel only
-    auto fail = [&](int code) { fir_free(f); return code; };
-#define TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail(hip_fail(e__, #call)); } while (0)
-    TRY(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
+    int rc = f->stream.create();
+    if (rc != SFE_OK) return rc;
     f->h_taps_all.assign(taps, taps + (size_t)n_taps * (taps_complex ? 2 : 1) * (per_channel ? n_channels : 1));
-    if (f->fft_ok) {
-        rc = fir_build_tables(f, taps);
-        if (rc != SFE_OK) return fail(rc);
-    }
+    if (f->fft_ok && (rc = fir_build_tables(f.get(), taps, f->parts, f->ovl, f->tab)) != SFE_OK) return rc;
     if (!f->taps_complex && !f->per_channel) {
         f->h_taps.assign(taps, taps + n_taps);
-        TRY(hipMalloc(&f->d_taps, (size_t)n_taps * sizeof(float)));
-        TRY(hipMemcpy(f->d_taps, taps, (size_t)n_taps * sizeof(float), hipMemcpyHostToDevice));
+        if ((rc = f->d_taps.upload(f->h_taps)) != SFE_OK) return rc;
     }
-    for (int i = 0; i < 2; i++) {
-        TRY(hipMalloc(&f->d_hist[i], f->hist_bytes()));
-        TRY(hipMemset(f->d_hist[i], 0, f->hist_bytes()));
-    }
+    if ((rc = f->hist.alloc_zero(f->hist_bytes())) != SFE_OK) return rc;
     if (f->blk > 0) {
         if (n_channels != 1) {
             set_error("fir_create: the host block path (block_hint) is single-channel");
-            return fail(SFE_EINVAL);
+            return SFE_EINVAL;
         }
         const size_t in_e = f->data_complex ? 2 : 1, out_e = f->out_complex ? 2 : 1;
-        const size_t hb = ((size_t)block_hint + 2) * (out_e > in_e ? out_e : in_e) * sizeof(float);
-        TRY(hipHostMalloc((void **)&f->h_buf, hb));
-        memset(f->h_buf, 0, hb);
-        TRY(hipMalloc(&f->d_blk_in, (size_t)f->blk * in_e * sizeof(float)));
-        TRY(hipMalloc(&f->d_blk_out, (size_t)f->blk * out_e * sizeof(float)));
-        TRY(hipHostMalloc(&f->h_blk_out, hb));
+        const size_t hf = ((size_t)block_hint + 2) * (out_e > in_e ? out_e : in_e);       // floats of a pinned block
+        if ((rc = f->h_buf.alloc(hf)) != SFE_OK) return rc;
+        memset(f->h_buf, 0, hf * sizeof(float));
+        if ((rc = f->d_blk_in.alloc((size_t)f->blk * in_e * sizeof(float))) != SFE_OK ||
+            (rc = f->d_blk_out.alloc((size_t)f->blk * out_e * sizeof(float))) != SFE_OK || (rc = f->h_blk_out.alloc(hf * sizeof(float))) != SFE_OK)
+            return rc;
     }
-    TRY(hipDeviceSynchronize());
-#undef TRY
-    *out = f;
+    SFE_HIP(hipDeviceSynchronize());
+    *out = f.release();
     return SFE_OK;
 }
 
@@ -603,46 +546,36 @@ int sfe_dsp_fir_process_host(sfe_fir_t h, const void *in, void *out, size_t n)
     SFE_ON_DEVICE(f->device);
     const size_t in_e = f->data_complex ? 8 : 4, out_e = f->out_complex ? 8 : 4;
     const size_t CH = (size_t)1 << 20;            // samples per staged chunk
-    if (!f->h_stage || !f->d_st_in || !f->d_st_out) {
-        // allocate into locals and commit only when all three exist: a failed later allocation must
+    if (!f->stage.h) {
+        // build the set beside the handle and move it in only when all of it exists: a failed later allocation must
         // not leave a half-built staging set behind for the next call to trip over
-        void *hs = nullptr, *di = nullptr, *dn = nullptr, *ho = nullptr;
+        FirStage st;
         const size_t zc = f->zc_max < CH ? f->zc_max : CH;
-        hipError_t e = hipHostMalloc(&hs, CH * (in_e > out_e ? in_e : out_e));
-        if (e == hipSuccess) e = hipMalloc(&di, CH * in_e);
-        if (e == hipSuccess) e = hipMalloc(&dn, CH * out_e);
-        if (e == hipSuccess && zc) e = hipHostMalloc(&ho, zc * out_e);
-        if (e != hipSuccess) {
-            if (hs) (void)hipHostFree(hs);
-            if (di) (void)hipFree(di);
-            if (dn) (void)hipFree(dn);
-            if (ho) (void)hipHostFree(ho);
-            return hip_fail(e, "fir_process_host staging");
-        }
-        f->h_stage = hs;
-        f->d_st_in = di;
-        f->d_st_out = dn;
-        f->h_stage_out = ho;
-        f->stage_samples = CH;
+        int rc = st.h.alloc(CH * (in_e > out_e ? in_e : out_e));
+        if (rc == SFE_OK) rc = st.d_in.alloc(CH * in_e);
+        if (rc == SFE_OK) rc = st.d_out.alloc(CH * out_e);
+        if (rc == SFE_OK && zc) rc = st.h_out.alloc(zc * out_e);
+        if (rc != SFE_OK) return rc;
+        f->stage = std::move(st);
     }
     const char *ip = static_cast<const char *>(in);
     char *op = static_cast<char *>(out);
     for (size_t off = 0; off < n; off += CH) {
         const size_t m = n - off < CH ? n - off : CH;
-        memcpy(f->h_stage, ip + off * in_e, m * in_e);
-        if (f->parts == 1 && f->h_stage_out && m <= f->zc_max) {          // small call: no DMA copies
-            int rc = fir_run(f, f->h_stage, f->h_stage_out, m, m, m, f->stream);
+        memcpy(f->stage.h, ip + off * in_e, m * in_e);
+        if (f->parts == 1 && f->stage.h_out && m <= f->zc_max) {          // small call: no DMA copies
+            int rc = fir_run(f, f->stage.h, f->stage.h_out, m, m, m, f->stream);
             if (rc != SFE_OK) return rc;
             SFE_HIP(hipStreamSynchronize(f->stream));
-            memcpy(op + off * out_e, f->h_stage_out, m * out_e);
+            memcpy(op + off * out_e, f->stage.h_out, m * out_e);
             continue;
         }
-        SFE_HIP(hipMemcpyAsync(f->d_st_in, f->h_stage, m * in_e, hipMemcpyHostToDevice, f->stream));
-        int rc = fir_run(f, f->d_st_in, f->d_st_out, m, m, m, f->stream);
+        SFE_HIP(hipMemcpyAsync(f->stage.d_in, f->stage.h, m * in_e, hipMemcpyHostToDevice, f->stream));
+        int rc = fir_run(f, f->stage.d_in, f->stage.d_out, m, m, m, f->stream);
         if (rc != SFE_OK) return rc;
-        SFE_HIP(hipMemcpyAsync(f->h_stage, f->d_st_out, m * out_e, hipMemcpyDeviceToHost, f->stream));
+        SFE_HIP(hipMemcpyAsync(f->stage.h, f->stage.d_out, m * out_e, hipMemcpyDeviceToHost, f->stream));
         SFE_HIP(hipStreamSynchronize(f->stream));
-        memcpy(op + off * out_e, f->h_stage, m * out_e);
+        memcpy(op + off * out_e, f->stage.h, m * out_e);
     }
     return SFE_OK;
 }
@@ -669,15 +602,11 @@ int sfe_dsp_fir_load_history(sfe_fir_t h, const void *d_prev, size_t n_prev, siz
     }
     SFE_ON_DEVICE(f->device);
     hipStream_t s = (hipStream_t)stream;
-    SFE_HIP(hipMemsetAsync(f->d_hist[f->cur], 0, f->hist_bytes(), s));        // shorter halos: zeros in front
-    if (n_prev) {
-        int rc = launch_history_update(d_prev, (long long)n_prev, (long long)stride, f->d_hist[f->cur], f->d_hist[f->cur ^ 1],
-                                       f->hl, f->data_complex ? 2 : 1, f->n_channels, s, 0);
-        if (rc != SFE_OK) return rc;
-        if (f->captured) SFE_HIP(hipMemcpyAsync(f->d_hist[f->cur], f->d_hist[f->cur ^ 1], f->hist_bytes(), hipMemcpyDeviceToDevice, s));
-        else f->cur ^= 1;
-    }
-    return SFE_OK;
+    SFE_HIP(hipMemsetAsync(f->hist.cur(), 0, f->hist_bytes(), s));        // shorter halos: zeros in front
+    if (!n_prev) return SFE_OK;
+    int rc = launch_history_update(d_prev, (long long)n_prev, (long long)stride, f->hist.cur(), f->hist.next(), f->hl,
+                                   f->data_complex ? 2 : 1, f->n_channels, s, 0);
+    return rc != SFE_OK ? rc : f->hist.carry(f->captured, s);
 }
 
 int sfe_dsp_fir_set_input_format(sfe_fir_t h, int fmt)
@@ -713,48 +642,17 @@ static int fir_replan_single(Fir *f)
         return SFE_ESTATE;
     }
     SFE_HIP(hipDeviceSynchronize());
-    // build the new plan beside the old one and swap only when all of it exists: a failure leaves the handle as it was
-    struct Saved {
-        v2f *hs, *tw1, *tw2;
-        unsigned *ticket;
-        void *hist[2];
-        int parts, ovl, hl, cur;
-        bool fft_ok;
-    } old = {f->d_hs, f->d_tw1, f->d_tw2, f->d_ticket, {f->d_hist[0], f->d_hist[1]}, f->parts, f->ovl, f->hl, f->cur, f->fft_ok};
-    f->d_hs = f->d_tw1 = f->d_tw2 = nullptr;
-    f->d_ticket = nullptr;
-    f->d_hist[0] = f->d_hist[1] = nullptr;
+    // build the new plan beside the old one and move it in only when all of it exists: a failure leaves the handle as it was
+    FirTables tab;
+    CarriedPair hist;
+    int rc = fir_build_tables(f, f->h_taps_all.data(), 1, hl1, tab);
+    if (rc == SFE_OK) rc = hist.alloc_zero((size_t)f->n_channels * hl1 * (f->data_complex ? 8 : 4));
+    if (rc != SFE_OK) return rc;
+    f->tab = std::move(tab);        // (the old tables and history go with the locals)
+    f->hist = std::move(hist);
     f->parts = 1;
-    f->ovl = hl1;
-    f->hl = hl1;
-    f->cur = 0;
-    int rc = fir_build_tables(f, f->h_taps_all.data());
-    for (int i = 0; i < 2 && rc == SFE_OK; i++) {
-        hipError_t e = hipMalloc(&f->d_hist[i], f->hist_bytes());
-        if (e == hipSuccess) e = hipMemset(f->d_hist[i], 0, f->hist_bytes());
-        if (e != hipSuccess) rc = hip_fail(e, "fir_replan_single: history");
-    }
-    if (rc == SFE_OK) {
-        void *drop[6] = {old.hs, old.tw1, old.tw2, old.ticket, old.hist[0], old.hist[1]};
-        for (void *q : drop)
-            if (q) (void)hipFree(q);
-        return SFE_OK;
-    }
-    void *drop[6] = {f->d_hs, f->d_tw1, f->d_tw2, f->d_ticket, f->d_hist[0], f->d_hist[1]};
-    for (void *q : drop)
-        if (q) (void)hipFree(q);
-    f->d_hs = old.hs;
-    f->d_tw1 = old.tw1;
-    f->d_tw2 = old.tw2;
-    f->d_ticket = old.ticket;
-    f->d_hist[0] = old.hist[0];
-    f->d_hist[1] = old.hist[1];
-    f->parts = old.parts;
-    f->ovl = old.ovl;
-    f->hl = old.hl;
-    f->cur = old.cur;
-    f->fft_ok = old.fft_ok;
-    return rc;
+    f->ovl = f->hl = hl1;
+    return SFE_OK;
 }
 
 int sfe_dsp_fir_set_output_format(sfe_fir_t h, int fmt)
@@ -850,7 +748,7 @@ int sfe_dsp_fir_set_zero_copy_max(sfe_fir_t h, size_t max_samples)
 {
     Fir *f = as_fir(h);
     if (!f) return SFE_EINVAL;
-    if (f->h_stage) {
+    if (f->stage.h) {
         // the pinned output staging of sfe_dsp_fir_process_host was sized from the old limit
         set_error("fir_set_zero_copy_max: set it before the first sfe_dsp_fir_process_host call");
         return SFE_ESTATE;
@@ -865,9 +763,10 @@ int sfe_dsp_fir_reset(sfe_fir_t h)
     if (!f) return SFE_EINVAL;
     SFE_ON_DEVICE(f->device);
     SFE_HIP(hipDeviceSynchronize());
-    for (int i = 0; i < 2; i++) SFE_HIP(hipMemset(f->d_hist[i], 0, f->hist_bytes()));
-    if (f->d_ticket) SFE_HIP(hipMemset(f->d_ticket, 0, FIR_TICKET_GROUPS_MAX * 128));
-    f->started = false;         // `captured` stays: a graph made before the reset still names d_hist[cur]
+    const int rc = f->hist.zero();
+    if (rc != SFE_OK) return rc;
+    if (f->tab.ticket) SFE_HIP(hipMemset(f->tab.ticket, 0, FIR_TICKET_GROUPS_MAX * 128));
+    f->started = false;         // `captured` stays: a graph made before the reset still names hist.cur()
     return SFE_OK;
 }
 
@@ -879,10 +778,7 @@ int sfe_dsp_fir_destroy(sfe_fir_t h)
         set_error("fir_destroy: a pipe still borrows this handle (sfe_dsp_pipe_destroy first)");
         return SFE_ESTATE;
     }
-    DeviceGuard g(f->device);
-    (void)hipDeviceSynchronize();
-    fir_free(f);
-    return SFE_OK;
+    return destroy_handle(f);
 }
 
 }  // extern "C"

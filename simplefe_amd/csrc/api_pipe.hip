@@ -43,7 +43,8 @@ static void copy_stream(void *dst, const void *src, size_t n)
 
 constexpr int PIPE_SLOTS = 4;
 struct FirPipe {
-    uint32_t magic = 0x50495031u;   // 'PIP1'
+    static constexpr uint32_t MAGIC = 0x50495031u;   // 'PIP1'
+    uint32_t magic = MAGIC;
     Fir *f = nullptr;               // the filter behind the pipe ...
     void *rs = nullptr;             // ... or the resampler / decimator (sfe_rs_t), at `rate`
     float rate = 1.0f;
@@ -53,15 +54,15 @@ struct FirPipe {
                                     // non-integer step: blksize, so the cut falls where a reference call ends; else 1)
     size_t tx_gs = 0;               // 10-bit packed output: samples per 5-byte group (2 complex / 4 real); an output ITEM is one group.
                                     // Cuts then fall on whole groups ONLY (less than a group is never sent: the converter emits whole groups)
+    Stream s_in, s_k, s_out;        // (before the slots: destroyed after them)
     struct Slot {
-        char *h_in = nullptr, *h_out = nullptr;
-        void *d_in = nullptr, *d_out = nullptr;
+        PinnedBuf<char> h_in, h_out;
+        DevBuf<char> d_in, d_out;
         size_t n = 0;               // items submitted in this slot
         size_t n_out = 0;           // items it produces (== n behind a filter)
-        hipEvent_t ev_in = nullptr, ev_k = nullptr, ev_out = nullptr;
+        Event ev_in, ev_k, ev_out;
         bool busy = false;          // submitted and not yet fully pulled
     } slot[PIPE_SLOTS];
-    hipStream_t s_in = nullptr, s_k = nullptr, s_out = nullptr;
     int head = 0;                   // slot being filled
     size_t fill = 0;                // items in it
     int tail = 0;                   // oldest busy slot
@@ -69,35 +70,7 @@ struct FirPipe {
     bool tail_ready = false;        // its ev_out has been seen complete
 };
 
-static FirPipe *as_pipe(void *h)
-{
-    FirPipe *p = static_cast<FirPipe *>(h);
-    if (p && p->magic != 0x50495031u) {
-        set_error("not a live pipe handle");
-        return nullptr;
-    }
-    return p;
-}
-
-static void pipe_free(FirPipe *p)
-{
-    if (!p) return;
-    p->magic = 0;
-    DeviceGuard g(p->device);
-    for (auto &sl : p->slot) {
-        if (sl.h_in) (void)hipHostFree(sl.h_in);
-        if (sl.h_out) (void)hipHostFree(sl.h_out);
-        if (sl.d_in) (void)hipFree(sl.d_in);
-        if (sl.d_out) (void)hipFree(sl.d_out);
-        if (sl.ev_in) (void)hipEventDestroy(sl.ev_in);
-        if (sl.ev_k) (void)hipEventDestroy(sl.ev_k);
-        if (sl.ev_out) (void)hipEventDestroy(sl.ev_out);
-    }
-    if (p->s_in) (void)hipStreamDestroy(p->s_in);
-    if (p->s_k) (void)hipStreamDestroy(p->s_k);
-    if (p->s_out) (void)hipStreamDestroy(p->s_out);
-    delete p;
-}
+static FirPipe *as_pipe(void *h) { return as_handle<FirPipe>(h, "pipe"); }
 
 // submits the first `count` items of the batch being filled (all of it when count == fill); what is left
 // moves to the front of the next slot (free: a partial submit only happens when nothing is in flight)
@@ -127,7 +100,7 @@ static int pipe_submit(FirPipe *p, size_t count)
     SFE_HIP(hipEventRecord(sl.ev_out, p->s_out));
     sl.busy = true;
     p->head = (p->head + 1) % PIPE_SLOTS;
-    if (rem) memcpy(p->slot[p->head].h_in, sl.h_in + count * p->in_e, rem * p->in_e);
+    if (rem) memcpy(p->slot[p->head].h_in, sl.h_in.p + count * p->in_e, rem * p->in_e);
     p->fill = rem;
     return SFE_OK;
 }
@@ -135,24 +108,17 @@ static int pipe_submit(FirPipe *p, size_t count)
 
 extern "C" {
 
-static int pipe_alloc(FirPipe *p, sfe_pipe_t *out)
+// the pipe's streams, pinned and device batches and events; `p` is dropped with whatever it holds where one of them fails
+static int pipe_alloc(std::unique_ptr<FirPipe> p, sfe_pipe_t *out)
 {
-    auto fail = [&](hipError_t e, const char *what) { int rc = hip_fail(e, what); pipe_free(p); return rc; };
-#define TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail(e__, #call); } while (0)
-    TRY(hipStreamCreateWithFlags(&p->s_in, hipStreamNonBlocking));
-    TRY(hipStreamCreateWithFlags(&p->s_k, hipStreamNonBlocking));
-    TRY(hipStreamCreateWithFlags(&p->s_out, hipStreamNonBlocking));
-    for (auto &sl : p->slot) {
-        TRY(hipHostMalloc((void **)&sl.h_in, p->batch * p->in_e));
-        TRY(hipHostMalloc((void **)&sl.h_out, p->out_cap * p->out_e));
-        TRY(hipMalloc(&sl.d_in, p->batch * p->in_e));
-        TRY(hipMalloc(&sl.d_out, p->out_cap * p->out_e));
-        TRY(hipEventCreateWithFlags(&sl.ev_in, hipEventDisableTiming));
-        TRY(hipEventCreateWithFlags(&sl.ev_k, hipEventDisableTiming));
-        TRY(hipEventCreateWithFlags(&sl.ev_out, hipEventDisableTiming));
-    }
-#undef TRY
-    *out = p;
+    int rc;
+    if ((rc = p->s_in.create()) != SFE_OK || (rc = p->s_k.create()) != SFE_OK || (rc = p->s_out.create()) != SFE_OK) return rc;
+    for (auto &sl : p->slot)
+        if ((rc = sl.h_in.alloc(p->batch * p->in_e)) != SFE_OK || (rc = sl.h_out.alloc(p->out_cap * p->out_e)) != SFE_OK ||
+            (rc = sl.d_in.alloc(p->batch * p->in_e)) != SFE_OK || (rc = sl.d_out.alloc(p->out_cap * p->out_e)) != SFE_OK ||
+            (rc = sl.ev_in.create()) != SFE_OK || (rc = sl.ev_k.create()) != SFE_OK || (rc = sl.ev_out.create()) != SFE_OK)
+            return rc;
+    *out = p.release();
     return SFE_OK;
 }
 
@@ -172,7 +138,7 @@ int sfe_dsp_fir_pipe_create(sfe_fir_t fir, size_t batch_items, sfe_pipe_t *out)
         return SFE_EINVAL;
     }
     SFE_ON_DEVICE(f->device);
-    FirPipe *p = new (std::nothrow) FirPipe;
+    std::unique_ptr<FirPipe> p(new (std::nothrow) FirPipe);
     if (!p) return SFE_ENOMEM;
     p->f = f;
     p->device = f->device;
@@ -188,7 +154,7 @@ int sfe_dsp_fir_pipe_create(sfe_fir_t fir, size_t batch_items, sfe_pipe_t *out)
         p->out_e = 5;
         p->out_cap = p->batch / p->tx_gs;
     }
-    const int rc = pipe_alloc(p, out);
+    const int rc = pipe_alloc(std::move(p), out);
     if (rc == SFE_OK) f->piped++;          // the handle's formats are frozen while the pipe lives
     return rc;
 }
@@ -215,7 +181,7 @@ int sfe_dsp_rs_pipe_create(sfe_rs_t rs, size_t batch_items, float rate, sfe_pipe
         return SFE_EINVAL;
     }
     SFE_ON_DEVICE(r->device);
-    FirPipe *p = new (std::nothrow) FirPipe;
+    std::unique_ptr<FirPipe> p(new (std::nothrow) FirPipe);
     if (!p) return SFE_ENOMEM;
     p->rs = rs;
     p->rate = rate;
@@ -229,7 +195,7 @@ int sfe_dsp_rs_pipe_create(sfe_rs_t rs, size_t batch_items, float rate, sfe_pipe
         const float stepf = rate * (float)r->U;
         p->quantum = (stepf >= 1.0f && stepf == floorf(stepf)) ? 1 : (size_t)r->blksize;
     }
-    const int rc = pipe_alloc(p, out);
+    const int rc = pipe_alloc(std::move(p), out);
     if (rc == SFE_OK) r->piped++;
     return rc;
 }
@@ -246,7 +212,7 @@ int sfe_dsp_pipe_push(sfe_pipe_t h, const void *in, size_t n_items, size_t *n_ta
         if (sl.busy) break;                                   // every slot in flight: pull first (backpressure)
         size_t m = p->batch - p->fill;
         if (m > n_items) m = n_items;
-        copy_stream(sl.h_in + p->fill * p->in_e, src, m * p->in_e);
+        copy_stream(sl.h_in.p + p->fill * p->in_e, src, m * p->in_e);
         p->fill += m;
         src += m * p->in_e;
         n_items -= m;
@@ -297,7 +263,7 @@ static int pipe_front(FirPipe *p, int wait, const char **ptr, size_t *count)
             p->tail_ready = false;
             continue;
         }
-        *ptr = sl.h_out + p->out_off * p->out_e;
+        *ptr = sl.h_out.p + p->out_off * p->out_e;
         *count = sl.n_out - p->out_off;
         return SFE_OK;
     }
@@ -349,7 +315,7 @@ int sfe_dsp_pipe_acquire(sfe_pipe_t h, void **buf, size_t *room_items)
     *room_items = 0;
     FirPipe::Slot &sl = p->slot[p->head];
     if (sl.busy) return SFE_OK;          // every batch in flight: take finished items out first
-    *buf = sl.h_in + p->fill * p->in_e;
+    *buf = sl.h_in.p + p->fill * p->in_e;
     *room_items = p->batch - p->fill;
     return SFE_OK;
 }
@@ -407,17 +373,10 @@ int sfe_dsp_pipe_destroy(sfe_pipe_t h)
 {
     FirPipe *p = as_pipe(h);
     if (!p) return SFE_OK;
-    {
-        DeviceGuard g(p->device);
-        (void)hipStreamSynchronize(p->s_in);
-        (void)hipStreamSynchronize(p->s_k);
-        (void)hipStreamSynchronize(p->s_out);
-    }
     // the handle is alive: its destroy call refuses while a pipe borrows it
     if (p->f && p->f->piped > 0) p->f->piped--;
     if (p->rs && static_cast<Rs *>(p->rs)->piped > 0) static_cast<Rs *>(p->rs)->piped--;
-    pipe_free(p);
-    return SFE_OK;
+    return destroy_handle(p);      // (its device sync waits for the pipe's three streams)
 }
 
 }  // extern "C"

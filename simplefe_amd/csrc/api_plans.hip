@@ -63,9 +63,10 @@ const PolyTiledPlan *get_tiled_plan(PlanCache &cache, const std::vector<float> &
 {
     *rc = SFE_OK;
     auto key = std::make_pair(step, pos0);
-    auto it = cache.plans.find(key);
-    if (it != cache.plans.end()) return it->second.d_G ? &it->second : nullptr;
-    PolyTiledPlan pl;
+    auto it = cache.find(key);
+    if (it != cache.end()) return it->second.plan.d_G ? &it->second.plan : nullptr;
+    PlanEntry<PolyTiledPlan, 2> en;     // (dropped with its tables on every way out that does not insert it)
+    PolyTiledPlan &pl = en.plan;
     const FoldedRows f = fold_rows(taps_pm, U, plen, step, pos0, 2);   // whole pairs of SP-sample chunks
     pl.SP = f.SP;
     pl.UP = f.UP;
@@ -75,28 +76,22 @@ const PolyTiledPlan *get_tiled_plan(PlanCache &cache, const std::vector<float> &
     // launcher declines -- exact mode, unaligned channels -- the caller runs the generic kernel)
     const bool many = pl.UP > 8 && pl.UP <= 256 && pl.SP >= 1 && pl.SP <= 256 && pl.Lp > 0;      // (147/160, 160/147: 44.1 <-> 48 kHz)
     if (!poly_tiled_supported(pl.SP, pl.UP, pl.Lp) && !many) {
-        cache.plans[key] = pl;          // d_G == nullptr marks "unsupported"
+        cache.emplace(key, std::move(en));          // d_G == nullptr marks "unsupported"
         return nullptr;
     }
-    hipError_t e = hipMalloc(&pl.d_G, f.G.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(pl.d_G, f.G.data(), f.G.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess && pl.UP <= 256) {
+    *rc = en.d[0].upload(f.G);
+    if (*rc == SFE_OK && pl.UP <= 256) {
         // the same taps transposed, [local time][phase] padded to whole groups of 8 phases (the runtime-shape kernels read a row per tap)
         pl.gt_pitch = (pl.UP + 7) / 8 * 8;
         std::vector<float> gt((size_t)pl.Lp * pl.gt_pitch, 0.0f);
         for (int r = 0; r < pl.UP; r++)
             for (int q = 0; q < pl.Lp; q++) gt[(size_t)q * pl.gt_pitch + r] = f.G[(size_t)r * pl.Lp + q];
-        e = hipMalloc(&pl.d_Gt, gt.size() * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(pl.d_Gt, gt.data(), gt.size() * sizeof(float), hipMemcpyHostToDevice);
+        *rc = en.d[1].upload(gt);
     }
-    if (e != hipSuccess) {
-        if (pl.d_G) (void)hipFree(pl.d_G);
-        if (pl.d_Gt) (void)hipFree(pl.d_Gt);
-        *rc = hip_fail(e, "tiled plan upload");
-        return nullptr;
-    }
-    auto ins = cache.plans.emplace(key, pl);
-    return &ins.first->second;
+    if (*rc != SFE_OK) return nullptr;
+    pl.d_G = en.d[0];
+    pl.d_Gt = en.d[1];
+    return &cache.emplace(key, std::move(en)).first->second.plan;
 }
 
 // ---- transform-domain plans (common.h: PolyFftPlan) -----------------------------------
@@ -108,9 +103,10 @@ const PolyFftPlan *get_fft_plan(FftPlanCache &cache, const std::vector<float> &t
 {
     *rc = SFE_OK;
     auto key = std::make_pair(step, pos0);
-    auto it = cache.plans.find(key);
-    if (it != cache.plans.end()) return it->second.d_H ? &it->second : nullptr;
-    PolyFftPlan pl;
+    auto it = cache.find(key);
+    if (it != cache.end()) return it->second.plan.d_H ? &it->second.plan : nullptr;
+    PlanEntry<PolyFftPlan, 2> en;
+    PolyFftPlan &pl = en.plan;
     const FoldedRows f = fold_rows(taps_pm, U, plen, step, pos0, 1);
     pl.SP = f.SP;
     pl.UP = f.UP;
@@ -134,7 +130,7 @@ const PolyFftPlan *get_fft_plan(FftPlanCache &cache, const std::vector<float> &t
                              (poly_tiled_is_compiled(f.SP, f.UP, Lp2) ? 1.0 : 0.5);
     const bool forced = fft_mode > 0;
     if (!pl.R || pl.Li > 192 || fft_mode < 0 || (!forced && tiled_ok && direct_flops < threshold)) {
-        cache.plans[key] = pl;
+        cache.emplace(key, std::move(en));
         return nullptr;
     }
     const int M = 256, SP = f.SP, UP = f.UP;
@@ -171,18 +167,10 @@ const PolyFftPlan *get_fft_plan(FftPlanCache &cache, const std::vector<float> &t
             tw[((k + 2) * 16 + l) * 2 + 0] = (float)cos(a4);
             tw[((k + 2) * 16 + l) * 2 + 1] = (float)sin(a4);
         }
-    hipError_t e = hipMalloc(&pl.d_H, H.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&pl.d_tw, tw.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(pl.d_H, H.data(), H.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(pl.d_tw, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (pl.d_H) (void)hipFree(pl.d_H);
-        if (pl.d_tw) (void)hipFree(pl.d_tw);
-        *rc = hip_fail(e, "transform-domain plan upload");
-        return nullptr;
-    }
-    auto ins = cache.plans.emplace(key, pl);
-    return &ins.first->second;
+    if ((*rc = en.d[0].upload(H)) != SFE_OK || (*rc = en.d[1].upload(tw)) != SFE_OK) return nullptr;
+    pl.d_H = en.d[0];
+    pl.d_tw = en.d[1];
+    return &cache.emplace(key, std::move(en)).first->second.plan;
 }
 
 // ---- f32-MFMA plans (common.h: PolyMfmaPlan) ------------------------------------------
@@ -192,13 +180,14 @@ const PolyMfmaPlan *get_mfma_plan(MfmaCache &cache, const std::vector<float> &ta
 {
     *rc = SFE_OK;
     auto key = std::make_pair(step, pos0);
-    auto it = cache.plans.find(key);
-    if (it != cache.plans.end()) return it->second.d_A ? &it->second : nullptr;
-    PolyMfmaPlan pl;
+    auto it = cache.find(key);
+    if (it != cache.end()) return it->second.plan.d_A ? &it->second.plan : nullptr;
+    PlanEntry<PolyMfmaPlan, 1> en;
+    PolyMfmaPlan &pl = en.plan;
     const int g = std::gcd(step, U);
     const int SP = step / g, UP = U / g;
     if (UP > 16) {
-        cache.plans[key] = pl;
+        cache.emplace(key, std::move(en));
         return nullptr;
     }
     const int DM = 16 / UP;
@@ -227,7 +216,7 @@ const PolyMfmaPlan *get_mfma_plan(MfmaCache &cache, const std::vector<float> &ta
     pl.u_lo = (int)(u_hi - pl.Kp + 1);
     pl.density = (float)((double)pl.RG * plen_eff / (16.0 * pl.Kp));
     if (!poly_mfma_fits(pl.GS, pl.RG, pl.Kp)) {
-        cache.plans[key] = pl;          // d_A == nullptr marks "unsupported"
+        cache.emplace(key, std::move(en));          // d_A == nullptr marks "unsupported"
         return nullptr;
     }
     const int ksteps = pl.Kp / 4;
@@ -240,15 +229,9 @@ const PolyMfmaPlan *get_mfma_plan(MfmaCache &cache, const std::vector<float> &ta
             const long long jt = (long long)SP * d + o[r] - u_hi + kk;      // tap met at window pos u_hi - kk
             if (jt >= 0 && jt < plen_eff) Af[(size_t)ks * 64 + lane] = taps_pm[(size_t)ph[r] * plen + jt];
         }
-    hipError_t e = hipMalloc(&pl.d_A, Af.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(pl.d_A, Af.data(), Af.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (pl.d_A) (void)hipFree(pl.d_A);
-        *rc = hip_fail(e, "mfma plan upload");
-        return nullptr;
-    }
-    auto ins = cache.plans.emplace(key, pl);
-    return &ins.first->second;
+    if ((*rc = en.d[0].upload(Af)) != SFE_OK) return nullptr;
+    pl.d_A = en.d[0];
+    return &cache.emplace(key, std::move(en)).first->second.plan;
 }
 
 }  // namespace sfe

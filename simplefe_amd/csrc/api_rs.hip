@@ -7,61 +7,18 @@ namespace sfe {
 
 // ------------------------------------------------------------------ resample / decimate
 
-Rs *as_rs(void *h)
-{
-    Rs *r = static_cast<Rs *>(h);
-    if (r && r->magic != 0x52533031u) {
-        set_error("not a live resample/decimate handle");
-        return nullptr;
-    }
-    return r;
-}
-
-void rs_free(Rs *r)
-{
-    if (!r) return;
-    r->magic = 0;
-    DeviceGuard g(r->device);
-    if (r->d_taps) (void)hipFree(r->d_taps);
-    r->plans.clear();
-    r->mfma_plans.clear();
-    r->fft_plans.clear();
-    if (r->d_ticket) (void)hipFree(r->d_ticket);
-    if (r->gen_tables) fir_free(r->gen_tables);
-    for (int i = 0; i < 2; i++)
-        if (r->d_hist[i]) (void)hipFree(r->d_hist[i]);
-    if (r->d_in) (void)hipFree(r->d_in);
-    if (r->d_out) (void)hipFree(r->d_out);
-    if (r->d_pos) (void)hipFree(r->d_pos);
-    if (r->d_mu) (void)hipFree(r->d_mu);
-    if (r->h_stage) (void)hipHostFree(r->h_stage);
-    if (r->d_u8f) (void)hipFree(r->d_u8f);
-    if (r->h_pos) (void)hipHostFree(r->h_pos);
-    if (r->h_mu) (void)hipHostFree(r->h_mu);
-    if (r->d_segs) (void)hipFree(r->d_segs);
-    if (r->d_chunks) (void)hipFree(r->d_chunks);
-    if (r->h_segs) (void)hipHostFree(r->h_segs);
-    if (r->h_chunks) (void)hipHostFree(r->h_chunks);
-    if (r->ev_plan) (void)hipEventDestroy(r->ev_plan);
-    if (r->stream) (void)hipStreamDestroy(r->stream);
-    delete r;
-}
+Rs *as_rs(void *h) { return as_handle<Rs>(h, "resample/decimate"); }
 
 static int rs_ensure_sched(Rs *r, size_t n)
 {
     if (n <= r->sched_cap) return SFE_OK;
     size_t cap = r->sched_cap ? r->sched_cap : 1024;
     while (cap < n) cap *= 2;
-    if (r->d_pos) (void)hipFree(r->d_pos);
-    if (r->d_mu) (void)hipFree(r->d_mu);
-    if (r->h_pos) (void)hipHostFree(r->h_pos);
-    if (r->h_mu) (void)hipHostFree(r->h_mu);
-    r->d_pos = nullptr; r->d_mu = nullptr; r->h_pos = nullptr; r->h_mu = nullptr;
     r->sched_cap = 0;
-    SFE_HIP(hipMalloc(&r->d_pos, cap * sizeof(long long)));
-    SFE_HIP(hipMalloc(&r->d_mu, cap * sizeof(float)));
-    SFE_HIP(hipHostMalloc(&r->h_pos, cap * sizeof(long long)));
-    SFE_HIP(hipHostMalloc(&r->h_mu, cap * sizeof(float)));
+    int rc;
+    if ((rc = r->d_pos.grow(cap)) != SFE_OK || (rc = r->d_mu.grow(cap)) != SFE_OK || (rc = r->h_pos.grow(cap)) != SFE_OK ||
+        (rc = r->h_mu.grow(cap)) != SFE_OK)
+        return rc;
     r->sched_cap = cap;
     return SFE_OK;
 }
@@ -71,10 +28,9 @@ static int rs_ensure_out(Rs *r, size_t n)
     if (n <= r->out_cap) return SFE_OK;
     size_t cap = r->out_cap ? r->out_cap : 1024;
     while (cap < n) cap *= 2;
-    if (r->d_out) (void)hipFree(r->d_out);
-    r->d_out = nullptr;
     r->out_cap = 0;
-    SFE_HIP(hipMalloc(&r->d_out, cap * r->esz()));
+    const int rc = r->d_out.grow(cap * r->esz());
+    if (rc != SFE_OK) return rc;
     r->out_cap = cap;
     return SFE_OK;
 }
@@ -82,10 +38,9 @@ static int rs_ensure_out(Rs *r, size_t n)
 static int rs_ensure_stage(Rs *r, size_t bytes)
 {
     if (bytes <= r->h_stage_bytes) return SFE_OK;
-    if (r->h_stage) (void)hipHostFree(r->h_stage);
-    r->h_stage = nullptr;
     r->h_stage_bytes = 0;
-    SFE_HIP(hipHostMalloc(&r->h_stage, bytes));
+    const int rc = r->h_stage.grow(bytes);
+    if (rc != SFE_OK) return rc;
     r->h_stage_bytes = bytes;
     return SFE_OK;
 }
@@ -123,12 +78,9 @@ int sfe_dsp_rs_create(const float *taps, int n_taps, int upsample, int blksize, 
         set_error("rs_create: bad arguments");
         return SFE_EINVAL;
     }
-    int prev_dev = -1;
-    (void)hipGetDevice(&prev_dev);
-    int rc = use_device(device);
-    if (rc != SFE_OK) return rc;
-    struct Restore { int d; ~Restore() { if (d >= 0) (void)hipSetDevice(d); } } restore__{prev_dev};
-    Rs *r = new (std::nothrow) Rs;
+    CreateScope scope(device);
+    if (scope.rc != SFE_OK) return scope.rc;
+    std::unique_ptr<Rs> r(new (std::nothrow) Rs);
     if (!r) return SFE_ENOMEM;
     r->U = upsample;
     r->n_taps = n_taps;
@@ -142,29 +94,21 @@ int sfe_dsp_rs_create(const float *taps, int n_taps, int upsample, int blksize, 
     const int eff = (mode == SFE_RS_DECIMATE && (n_taps % 2 == 0)) ? n_taps + 1 : n_taps;
     r->plen = (eff + upsample - 1) / upsample;
     r->hl = ((r->plen + 1 + 63) / 64) * 64;
-    auto fail = [&](int code) { rs_free(r); return code; };
-#define TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return fail(hip_fail(e__, #call)); } while (0)
-    TRY(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
-    std::vector<float> pm((size_t)upsample * r->plen, 0.0f);
+    int rc = r->stream.create();
+    if (rc != SFE_OK) return rc;
+    std::vector<float> &pm = r->h_taps_pm;
+    pm.assign((size_t)upsample * r->plen, 0.0f);
     for (int j = 0; j < upsample; j++)
         for (int i = 0; i < r->plen; i++) {
             const int n = i * upsample + j;
             pm[(size_t)j * r->plen + i] = n < n_taps ? taps[n] : 0.0f;
         }
-    r->h_taps_pm = pm;
-    TRY(hipMalloc(&r->d_taps, pm.size() * sizeof(float)));
-    TRY(hipMemcpy(r->d_taps, pm.data(), pm.size() * sizeof(float), hipMemcpyHostToDevice));
-    const size_t hb = (size_t)n_channels * r->hl * r->esz();
-    for (int i = 0; i < 2; i++) {
-        TRY(hipMalloc(&r->d_hist[i], hb));
-        TRY(hipMemset(r->d_hist[i], 0, hb));
-    }
-    TRY(hipMalloc(&r->d_in, (size_t)blksize * r->esz()));
-    TRY(hipMalloc(&r->d_ticket, POLY_TICKET_GROUPS * 128));
-    TRY(hipMemset(r->d_ticket, 0, POLY_TICKET_GROUPS * 128));
-    TRY(hipDeviceSynchronize());
-#undef TRY
-    *out = r;
+    if ((rc = r->d_taps.upload(pm)) != SFE_OK || (rc = r->hist.alloc_zero((size_t)n_channels * r->hl * r->esz())) != SFE_OK ||
+        (rc = r->d_in.alloc((size_t)blksize * r->esz())) != SFE_OK ||
+        (rc = r->d_ticket.alloc_zero(POLY_TICKET_GROUPS * 128 / sizeof(unsigned))) != SFE_OK)
+        return rc;
+    SFE_HIP(hipDeviceSynchronize());
+    *out = r.release();
     return SFE_OK;
 }
 
@@ -221,7 +165,7 @@ int sfe_dsp_rs_process(sfe_rs_t h, const float *in, int n_in, float *out, int ou
             const size_t in_b = (size_t)n_in * r->esz(), out_off = (in_b + 255) & ~(size_t)255;
             int rc = rs_ensure_stage(r, out_off + ((size_t)out_len + 1) * r->esz());
             if (rc != SFE_OK) return rc;
-            char *h_out = static_cast<char *>(r->h_stage) + out_off;
+            char *h_out = r->h_stage.p + out_off;
             memcpy(r->h_stage, in, in_b);
             SFE_HIP(hipMemcpyAsync(r->d_in, r->h_stage, in_b, hipMemcpyHostToDevice, r->stream));
             const int keep = r->exact_stream;
@@ -249,8 +193,8 @@ int sfe_dsp_rs_process(sfe_rs_t h, const float *in, int n_in, float *out, int ou
 
     int k = 0;
     const int n = time_law(&r->ts, r->U, n_in, out_len, rate, [&](int p, float m) {
-        r->h_pos[k] = p;
-        r->h_mu[k] = m;
+        r->h_pos.p[k] = p;
+        r->h_mu.p[k] = m;
         k++;
     });
     if (n_in) {
@@ -264,7 +208,7 @@ int sfe_dsp_rs_process(sfe_rs_t h, const float *in, int n_in, float *out, int ou
         memset(&a, 0, sizeof(a));
         a.in = r->d_in;
         a.out = r->d_out;
-        a.hist = r->d_hist[r->cur];
+        a.hist = r->hist.cur();
         a.taps = r->d_taps;
         a.n_in = n_in;
         a.in_stride = n_in;
@@ -278,13 +222,9 @@ int sfe_dsp_rs_process(sfe_rs_t h, const float *in, int n_in, float *out, int ou
         rc = launch_poly_sched(a, r->data_complex, 1, 1, r->stream);
         if (rc != SFE_OK) return rc;
     }
-    rc = launch_history_update(r->d_in, n_in, n_in, r->d_hist[r->cur], r->d_hist[r->cur ^ 1], r->hl,
-                               r->data_complex ? 2 : 1, 1, r->stream);
+    rc = launch_history_update(r->d_in, n_in, n_in, r->hist.cur(), r->hist.next(), r->hl, r->data_complex ? 2 : 1, 1, r->stream);
+    if (rc == SFE_OK) rc = r->hist.carry(r->captured, r->stream);
     if (rc != SFE_OK) return rc;
-    if (r->captured)
-        SFE_HIP(hipMemcpyAsync(r->d_hist[r->cur], r->d_hist[r->cur ^ 1], (size_t)r->hl * r->esz(), hipMemcpyDeviceToDevice, r->stream));
-    else
-        r->cur ^= 1;
     if (n > 0) SFE_HIP(hipMemcpyAsync(r->h_stage, r->d_out, (size_t)n * r->esz(), hipMemcpyDeviceToHost, r->stream));
     SFE_HIP(hipStreamSynchronize(r->stream));
     if (n > 0) memcpy(out, r->h_stage, (size_t)n * r->esz());
@@ -316,17 +256,15 @@ int sfe_dsp_rs_process_stream(sfe_rs_t h, const void *d_in, size_t n_in, size_t 
                       floats * 4);
             return SFE_ESTATE;
         }
-        if (r->d_u8f) (void)hipFree(r->d_u8f);
-        r->d_u8f = nullptr;
         r->d_u8f_floats = 0;
-        SFE_HIP(hipMalloc(&r->d_u8f, floats * sizeof(float)));
+        if ((rc = r->d_u8f.grow(floats)) != SFE_OK) return rc;
         r->d_u8f_floats = floats;
     } else if (r->u8f_stream != s && r->u8f_stream) {
         SFE_HIP(hipStreamSynchronize(r->u8f_stream));         // the previous call on another stream may still read the scratch
     }
     r->u8f_stream = s;
     for (int c = 0; c < r->n_channels; c++) {
-        rc = launch_rx_u8_to_f32(static_cast<const uint8_t *>(d_in) + (size_t)c * in_stride * w, r->d_u8f + (size_t)c * n_in * w, n_in * w, s);
+        rc = launch_rx_u8_to_f32(static_cast<const uint8_t *>(d_in) + (size_t)c * in_stride * w, r->d_u8f.p + (size_t)c * n_in * w, n_in * w, s);
         if (rc != SFE_OK) return rc;
     }
     r->in_u8 = 0;
@@ -385,7 +323,7 @@ static int rs_process_stream_impl(sfe_rs_t h, const void *d_in, size_t n_in, siz
     memset(&a, 0, sizeof(a));
     a.in = d_in;
     a.out = d_out;
-    a.hist = r->d_hist[r->cur];
+    a.hist = r->hist.cur();
     a.taps = r->d_taps;
     a.n_in = (long long)n_in;
     a.in_stride = (long long)in_stride;
@@ -431,8 +369,8 @@ static int rs_process_stream_impl(sfe_rs_t h, const void *d_in, size_t n_in, siz
             memset(&fa, 0, sizeof(fa));
             fa.in = d_in;
             fa.out = d_out;
-            fa.hist = r->d_hist[r->cur];
-            fa.hist_out = can_fuse ? r->d_hist[r->cur ^ 1] : nullptr;
+            fa.hist = r->hist.cur();
+            fa.hist_out = can_fuse ? r->hist.next() : nullptr;
             hist_fused = can_fuse;
             fa.H = fp->d_H;
             fa.tw = fp->d_tw;
@@ -451,7 +389,7 @@ static int rs_process_stream_impl(sfe_rs_t h, const void *d_in, size_t n_in, siz
             memset(&ma, 0, sizeof(ma));
             ma.in = d_in;
             ma.out = d_out;
-            ma.hist = r->d_hist[r->cur];
+            ma.hist = r->hist.cur();
             ma.A = mp->d_A;
             ma.n_in = (long long)n_in;
             ma.in_stride = (long long)in_stride;
@@ -467,8 +405,8 @@ static int rs_process_stream_impl(sfe_rs_t h, const void *d_in, size_t n_in, siz
             PolyTiledArgs ta;
             ta.in = d_in;
             ta.out = d_out;
-            ta.hist = r->d_hist[r->cur];
-            ta.hist_out = can_fuse && !r->exact_stream ? r->d_hist[r->cur ^ 1] : nullptr;      // exact kernels: separate carry-over launch
+            ta.hist = r->hist.cur();
+            ta.hist_out = can_fuse && !r->exact_stream ? r->hist.next() : nullptr;      // exact kernels: separate carry-over launch
             hist_fused = ta.hist_out != nullptr;
             ta.G = pl->d_G;
             ta.Gt = pl->d_Gt;
@@ -617,7 +555,7 @@ static int rs_process_stream_impl(sfe_rs_t h, const void *d_in, size_t n_in, siz
         memset(&sa, 0, sizeof(sa));
         sa.in = d_in;
         sa.out = d_out;
-        sa.hist = r->d_hist[r->cur];
+        sa.hist = r->hist.cur();
         sa.taps = r->d_taps;
         sa.n_in = (long long)n_in;
         sa.in_stride = (long long)in_stride;
@@ -637,38 +575,30 @@ static int rs_process_stream_impl(sfe_rs_t h, const void *d_in, size_t n_in, siz
         if (r->ev_plan) {
             if (r->plan_stream != s) SFE_HIP(hipStreamSynchronize(r->plan_stream));
             else SFE_HIP(hipEventSynchronize(r->ev_plan));
-        } else {
-            SFE_HIP(hipEventCreateWithFlags(&r->ev_plan, hipEventDisableTiming));
+        } else if ((rc = r->ev_plan.create()) != SFE_OK) {
+            return rc;
         }
         if (n_segs > r->segs_cap) {
-            if (r->d_segs) (void)hipFree(r->d_segs);
-            if (r->h_segs) (void)hipHostFree(r->h_segs);
-            r->d_segs = r->h_segs = nullptr;
             r->segs_cap = 0;
             r->seg_uploaded = 0;
             const size_t cap2 = n_segs * 2 + 1024;
-            SFE_HIP(hipMalloc(&r->d_segs, cap2 * sizeof(TlSeg)));
-            SFE_HIP(hipHostMalloc(&r->h_segs, cap2 * sizeof(TlSeg)));
+            if ((rc = r->d_segs.grow(cap2)) != SFE_OK || (rc = r->h_segs.grow(cap2)) != SFE_OK) return rc;
             r->segs_cap = cap2;
         }
         if (chunks.size() > r->chunks_cap) {
-            if (r->d_chunks) (void)hipFree(r->d_chunks);
-            if (r->h_chunks) (void)hipHostFree(r->h_chunks);
-            r->d_chunks = r->h_chunks = nullptr;
             r->chunks_cap = 0;
             const size_t cap2 = chunks.size() * 2 + 64;
-            SFE_HIP(hipMalloc(&r->d_chunks, cap2 * sizeof(SegChunk)));
-            SFE_HIP(hipHostMalloc(&r->h_chunks, cap2 * sizeof(SegChunk)));
+            if ((rc = r->d_chunks.grow(cap2)) != SFE_OK || (rc = r->h_chunks.grow(cap2)) != SFE_OK) return rc;
             r->chunks_cap = cap2;
         }
         // upload what the device does not hold yet: the table's new tail, then this call's own runs behind it
         {
-            TlSeg *hs = static_cast<TlSeg *>(r->h_segs);
+            TlSeg *hs = r->h_segs;
             const size_t from = r->seg_uploaded < n_table ? r->seg_uploaded : n_table;
             if (n_table > from) memcpy(hs + from, r->seg_table.data() + from, (n_table - from) * sizeof(TlSeg));
             if (!extra.empty()) memcpy(hs + n_table, extra.data(), extra.size() * sizeof(TlSeg));
             if (n_segs > from)
-                SFE_HIP(hipMemcpyAsync(static_cast<TlSeg *>(r->d_segs) + from, hs + from, (n_segs - from) * sizeof(TlSeg),
+                SFE_HIP(hipMemcpyAsync(r->d_segs.p + from, hs + from, (n_segs - from) * sizeof(TlSeg),
                                        hipMemcpyHostToDevice, s));
             r->seg_uploaded = n_table;
         }
@@ -677,7 +607,7 @@ static int rs_process_stream_impl(sfe_rs_t h, const void *d_in, size_t n_in, siz
         SFE_HIP(hipEventRecord(r->ev_plan, s));
         r->plan_stream = s;
         sa.segs = r->d_segs;
-        sa.chunks = static_cast<const SegChunk *>(r->d_chunks);
+        sa.chunks = r->d_chunks;
         // Bulk calls (complex or real, float32 or u8) in fused arithmetic, at any rate: the transform-domain kernel (poly_gen.hip) --
         // all U phases of every input by one forward and U inverse 4096-point transforms, outputs picked and blended from
         // LDS by the same runs.  sfe_dsp_rs_set_algo(SFE_RS_ALGO_DIRECT) and the exact mode keep poly_seg_kernel.
@@ -697,11 +627,8 @@ static int rs_process_stream_impl(sfe_rs_t h, const void *d_in, size_t n_in, siz
                     for (int i = 0; i < r->plen; i++) rows[(size_t)j * (r->plen + 1) + i] = r->h_taps_pm[(size_t)j * r->plen + i];
                 sfe_fir_t gh = nullptr;
                 if (fir_create_impl(rows.data(), r->plen + 1, 0, 1, r->U, 0, r->device, 1, &gh) == SFE_OK) {
-                    r->gen_tables = static_cast<Fir *>(gh);
-                    if (r->gen_tables->parts != 1) {
-                        fir_free(r->gen_tables);
-                        r->gen_tables = nullptr;
-                    }
+                    r->gen_tables.reset(static_cast<Fir *>(gh));
+                    if (r->gen_tables->parts != 1) r->gen_tables.reset();
                 }
             }
             if (r->gen_tables) {
@@ -709,12 +636,12 @@ static int rs_process_stream_impl(sfe_rs_t h, const void *d_in, size_t n_in, siz
                 memset(&ga, 0, sizeof(ga));
                 ga.in = d_in;
                 ga.out = d_out;
-                ga.hist = r->d_hist[r->cur];
-                ga.hs = r->gen_tables->d_hs;
-                ga.tw1 = r->gen_tables->d_tw1;
-                ga.tw2 = r->gen_tables->d_tw2;
+                ga.hist = r->hist.cur();
+                ga.hs = r->gen_tables->tab.hs;
+                ga.tw1 = r->gen_tables->tab.tw1;
+                ga.tw2 = r->gen_tables->tab.tw2;
                 ga.segs = r->d_segs;
-                ga.chunks = static_cast<const SegChunk *>(r->d_chunks);
+                ga.chunks = r->d_chunks;
                 ga.n_in = (long long)n_in;
                 ga.in_stride = (long long)in_stride;
                 ga.out_stride = (long long)out_stride;
@@ -807,22 +734,17 @@ static int rs_process_stream_impl(sfe_rs_t h, const void *d_in, size_t n_in, siz
     }
     if (capturing) {        // in place behind the main launch: with n_in >= hl the kernel reads `in` only; the time state did not move
         r->captured = true;
-        return launch_history_update(d_in, (long long)n_in, (long long)in_stride, r->d_hist[r->cur],
-                                     r->d_hist[r->cur], r->hl, r->data_complex ? 2 : 1, r->n_channels, s, r->in_u8);
+        return launch_history_update(d_in, (long long)n_in, (long long)in_stride, r->hist.cur(),
+                                     r->hist.cur(), r->hl, r->data_complex ? 2 : 1, r->n_channels, s, r->in_u8);
     }
     if (!hist_fused) {
-        rc = launch_history_update(d_in, (long long)n_in, (long long)in_stride, r->d_hist[r->cur],
-                                   r->d_hist[r->cur ^ 1], r->hl, r->data_complex ? 2 : 1, r->n_channels, s, r->in_u8);
+        rc = launch_history_update(d_in, (long long)n_in, (long long)in_stride, r->hist.cur(),
+                                   r->hist.next(), r->hl, r->data_complex ? 2 : 1, r->n_channels, s, r->in_u8);
         if (rc != SFE_OK) return rc;
     }
-    // a handle one of whose calls sits in a hipGraph keeps its history in d_hist[cur], the buffer the graph
+    // a handle one of whose calls sits in a hipGraph keeps its history in hist.cur(), the buffer the graph
     // names: eager calls copy the new history back instead of flipping (fir_carry_state has the reasoning)
-    if (r->captured)
-        SFE_HIP(hipMemcpyAsync(r->d_hist[r->cur], r->d_hist[r->cur ^ 1], (size_t)r->n_channels * r->hl * r->esz(),
-                               hipMemcpyDeviceToDevice, s));
-    else
-        r->cur ^= 1;
-    return SFE_OK;
+    return r->hist.carry(r->captured, s);
 }
 
 
@@ -844,16 +766,11 @@ int sfe_dsp_rs_load_history(sfe_rs_t h, const void *d_prev, size_t n_prev, size_
     }
     SFE_ON_DEVICE(r->device);
     hipStream_t s = (hipStream_t)stream;
-    const size_t hb = (size_t)r->n_channels * r->hl * r->esz();
-    SFE_HIP(hipMemsetAsync(r->d_hist[r->cur], 0, hb, s));
-    if (n_prev) {
-        int rc = launch_history_update(d_prev, (long long)n_prev, (long long)stride, r->d_hist[r->cur], r->d_hist[r->cur ^ 1],
-                                       r->hl, r->data_complex ? 2 : 1, r->n_channels, s, 0);
-        if (rc != SFE_OK) return rc;
-        if (r->captured) SFE_HIP(hipMemcpyAsync(r->d_hist[r->cur], r->d_hist[r->cur ^ 1], hb, hipMemcpyDeviceToDevice, s));
-        else r->cur ^= 1;
-    }
-    return SFE_OK;
+    SFE_HIP(hipMemsetAsync(r->hist.cur(), 0, r->hist.bytes, s));
+    if (!n_prev) return SFE_OK;
+    int rc = launch_history_update(d_prev, (long long)n_prev, (long long)stride, r->hist.cur(), r->hist.next(), r->hl,
+                                   r->data_complex ? 2 : 1, r->n_channels, s, 0);
+    return rc != SFE_OK ? rc : r->hist.carry(r->captured, s);
 }
 
 int sfe_dsp_rs_get_state(sfe_rs_t h, sfe_rs_timestate *state)
@@ -952,8 +869,8 @@ int sfe_dsp_rs_reset(sfe_rs_t h)
     if (!r) return SFE_EINVAL;
     SFE_ON_DEVICE(r->device);
     SFE_HIP(hipDeviceSynchronize());
-    const size_t hb = (size_t)r->n_channels * r->hl * r->esz();
-    for (int i = 0; i < 2; i++) SFE_HIP(hipMemset(r->d_hist[i], 0, hb));
+    const int rc = r->hist.zero();
+    if (rc != SFE_OK) return rc;
     if (r->d_ticket) SFE_HIP(hipMemset(r->d_ticket, 0, POLY_TICKET_GROUPS * 128));
     r->ts.pos = 0;
     r->ts.mu = 0.0f;
@@ -969,10 +886,7 @@ int sfe_dsp_rs_destroy(sfe_rs_t h)
         set_error("rs_destroy: a pipe still borrows this handle (sfe_dsp_pipe_destroy first)");
         return SFE_ESTATE;
     }
-    DeviceGuard g(r->device);
-    (void)hipDeviceSynchronize();
-    rs_free(r);
-    return SFE_OK;
+    return destroy_handle(r);
 }
 
 }  // extern "C"

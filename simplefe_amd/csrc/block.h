@@ -1,36 +1,64 @@
-// block.h -- what the handles of the streaming blocks share (api_chan.hip, api_combine.hip, api_ddc.hip, api_psd.hip,
-// api_corr.hip, api_iir.hip, api_beam.hip, api_cov.hip, api_mvdr.hip, api_eig.hip, api_burst.hip, api_vit.hip, api_mod.hip): owners of their device memory, the device scope of a create, the handle cast, the table
-// of the unit circle, and the checks every process_stream opens with.  HOST CODE ONLY, like host.h; include it after
-// host.h.  A block's struct names its magic as `static constexpr uint32_t MAGIC` and carries `magic` and `device`.
+// block.h -- what every handle of libsfe_dsp.so is built from: owners of its device memory, pinned host memory, streams and
+// events, the carried pair, the device scope of a create, the handle cast, the table of the unit circle, and the checks
+// every process_stream of a streaming block opens with.  The FIR, resampler and pipe handles (host.h, api_pipe.hip) and the
+// streaming blocks' (api_chan.hip ... api_mod.hip) all use it.  HOST CODE ONLY; host.h includes it.  A handle's struct names
+// its magic as `static constexpr uint32_t MAGIC` and carries `magic` and `device`.
 #pragma once
+#include <math.h>
+#include <stdint.h>
+
 #include <initializer_list>
 #include <memory>
+#include <utility>
+#include <vector>
 
-#include "host.h"
+#include "common.h"
 
 namespace sfe {
 
-// ---- device memory owned by a handle: freed with it
-template <class T>
-struct DevBuf {
+// DeviceGuard: common.h
+#define SFE_ON_DEVICE(dev)                                   \
+    DeviceGuard guard__(dev);                                \
+    if (!guard__.ok) {                                       \
+        set_error("cannot select device %d", (int)(dev));    \
+        return SFE_EHIP;                                     \
+    }
+
+bool ranges_overlap(const void *a, size_t an, const void *b, size_t bn);      // [a, a + an) and [b, b + bn) share a byte
+int use_device(int device);                                                    // hipSetDevice with the range / no-GPU checks
+bool stream_is_capturing(hipStream_t s);
+
+// ---- memory owned by a handle: freed with it.  DevBuf: device memory; PinnedBuf: pinned host memory
+template <class T, bool PINNED>
+struct Buf {
     T *p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { release(); }
+    Buf() = default;
+    Buf(Buf &&o) noexcept : p(std::exchange(o.p, nullptr)) {}
+    Buf &operator=(Buf &&o) noexcept       // what this held goes to `o` and is freed with it
+    {
+        std::swap(p, o.p);
+        return *this;
+    }
+    ~Buf() { release(); }
     void release()
     {
-        if (p) (void)hipFree(p);
+        if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p));
         p = nullptr;
     }
     operator T *() const { return p; }
     int alloc(size_t n)
     {
-        SFE_HIP(hipMalloc(&p, n * sizeof(T)));
+        SFE_HIP(PINNED ? hipHostMalloc((void **)&p, n * sizeof(T)) : hipMalloc((void **)&p, n * sizeof(T)));
         return SFE_OK;
     }
-    int upload(const T *src, size_t n)
+    int grow(size_t n)      // for a caller that keeps its own capacity: the old buffer goes first (peak memory: one of the two)
     {
+        release();
+        return alloc(n);
+    }
+    int upload(const T *src, size_t n)      // (upload, alloc_zero: device buffers only)
+    {
+        static_assert(!PINNED, "device buffers only");
         SFE_HIP(hipMalloc(&p, n * sizeof(T)));
         SFE_HIP(hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
         return SFE_OK;
@@ -38,8 +66,45 @@ struct DevBuf {
     int upload(const std::vector<T> &v) { return upload(v.data(), v.size()); }
     int alloc_zero(size_t n)
     {
+        static_assert(!PINNED, "device buffers only");
         SFE_HIP(hipMalloc(&p, n * sizeof(T)));
         SFE_HIP(hipMemset(p, 0, n * sizeof(T)));
+        return SFE_OK;
+    }
+};
+template <class T> using DevBuf = Buf<T, false>;
+template <class T> using PinnedBuf = Buf<T, true>;
+
+// a stream the handle created (a caller's stream is borrowed and stays a raw hipStream_t), an event: destroyed with the handle
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream &) = delete;
+    Stream &operator=(const Stream &) = delete;
+    ~Stream()
+    {
+        if (s) (void)hipStreamDestroy(s);
+    }
+    operator hipStream_t() const { return s; }
+    int create()
+    {
+        SFE_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        return SFE_OK;
+    }
+};
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    ~Event()
+    {
+        if (e) (void)hipEventDestroy(e);
+    }
+    operator hipEvent_t() const { return e; }
+    int create(unsigned flags = hipEventDisableTiming)
+    {
+        SFE_HIP(hipEventCreateWithFlags(&e, flags));
         return SFE_OK;
     }
 };
@@ -63,9 +128,17 @@ struct CarriedPair {
         for (auto &d : b) SFE_HIP(hipMemset(d.p, 0, bytes));
         return SFE_OK;
     }
-    template <class T> T *cur() const { return reinterpret_cast<T *>(b[c].p); }
-    template <class T> T *next() const { return reinterpret_cast<T *>(b[c ^ 1].p); }
+    template <class T = void> T *cur() const { return reinterpret_cast<T *>(b[c].p); }
+    template <class T = void> T *next() const { return reinterpret_cast<T *>(b[c ^ 1].p); }
     void flip() { c ^= 1; }
+    // behind a launch that wrote next().  `captured`: a hipGraph names cur(), so the state stays there for good -- the new
+    // state is copied back instead of flipping (a replay after an eager call would read the stale buffer)
+    int carry(bool captured, hipStream_t s)
+    {
+        if (captured) SFE_HIP(hipMemcpyAsync(b[c].p, b[c ^ 1].p, bytes, hipMemcpyDeviceToDevice, s));
+        else flip();
+        return SFE_OK;
+    }
 };
 
 // Scratch of one call that only grows: the one allocation (and device sync) a process_stream may make, when a larger
@@ -77,9 +150,8 @@ struct GrowScratch {
     {
         if (need <= bytes) return SFE_OK;
         SFE_HIP(hipDeviceSynchronize());
-        d.release();
         bytes = 0;
-        const int rc = d.alloc(need);
+        const int rc = d.grow(need);
         if (rc == SFE_OK) bytes = need;
         return rc;
     }
