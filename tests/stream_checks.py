@@ -6,7 +6,9 @@ Two layers:
     check_counts, check_values, and the two per-sample bounds direct_bound / transform_bound;
   * GPU runners run_rs / run_fir, which make the calls Rs.resample_array / Fir.filter make, but into an output that
     is poisoned before EVERY call and sits between guards, from an input that sits at an offset inside a larger
-    buffer whose every other word is NaN; after each call both buffers are read back whole and judged.
+    buffer whose every other word is NaN; after each call both buffers are read back whole and judged;
+  * run_psd / run_corr / run_iir, the same for the three streaming measurement blocks, with a gap between the streams of
+    the input and between the rows of every output as well (tests/test_measure_checks_host.py holds their negative controls).
 
 Each verdict raises its own exception (all of them AssertionErrors), so a negative control can tell WHICH check
 caught a corruption: WrittenError, InputError, CountError, ValuesError (its .gate names the gate that failed:
@@ -484,6 +486,166 @@ def resample_array(api, r, x, rate, chunk=None, **kw):
 def fir_filter(api, f, x, **kw):
     """Fir.filter(x) through run_fir."""
     return run_fir(api, f, x, **kw)
+
+
+# ------------------------------------------------------------------------------------------------ the measurement blocks
+# run_psd / run_corr / run_iir: the calls Psd / Corr / Iir.process_stream make, every stream of the input at an offset inside
+# a buffer of poison with in_stride > n_in, every output poisoned before EVERY call with a front guard, gaps between its
+# rows and a tail guard, every stride greater than its payload.  After each call every buffer is read back whole:
+# check_written with cap == k (none of the three contracts grants slack: include/sfe_dsp.h names exactly what a call
+# writes), then check_input_intact.  Counts are closed forms, checked before the bytes; a wrong one raises CountError.
+def _odd_stride(n_items, item, unit, gap):
+    """The smallest stride (items) >= n_items + gap whose bytes are an ODD multiple of `unit` bytes."""
+    s = n_items + gap
+    while (s * item) % unit or ((s * item) // unit) % 2 == 0:
+        s += 1
+    return s
+
+
+def measure_strides(n_in, in_item, n_out, out_item, aligned=True):
+    """(in_stride, out_stride) in items: both greater than their payloads, different from one another where the items are
+    the same size, odd multiples of 16 bytes (aligned) or odd counts of items (else)."""
+    si = _odd_stride(n_in, in_item, 16 if aligned else in_item, 7)
+    so = _odd_stride(n_out, out_item, 16 if aligned else out_item, 5)
+    if si == so:
+        si = _odd_stride(n_in, in_item, 16 if aligned else in_item, si - n_in + 1)
+    return si, so
+
+
+def _measure_input(x, nch, item, a, b, aligned, stride):
+    """_lay_input at a stride of the caller's: front 64 bytes, one item more when not aligned (cf32 8 bytes, u8 2 bytes, a
+    real stream 4 bytes past a 16-byte boundary)."""
+    lay = Layout(nch, item, b - a, stride, 64 + (0 if aligned else item), 64, 4)
+    raw = lay.poisoned()
+    rows = np.ascontiguousarray(x).reshape(nch, -1).view(np.uint8)
+    for c in range(nch):
+        lay.put(raw, c, rows[c, a * item:b * item])
+    return lay, raw
+
+
+def _measure_x(h, x, in_u8, w):
+    nch = h.n_streams
+    x = np.ascontiguousarray(x, dtype=np.uint8 if in_u8 else np.float32 if w == 1 else np.complex64).reshape(nch, -1)
+    item = 2 if in_u8 else 4 * w
+    return x, item, x.view(np.uint8).shape[1] // item
+
+
+def psd_rows_of_call(segments_before, n_in, H, A):
+    """include/sfe_dsp.h: *n_rows = floor((segments_before mod A + n_in / H) / A)."""
+    return (segments_before % A + n_in // H) // A
+
+
+def run_psd(api, ps, x, cuts=None, in_u8=False, aligned=True, segments_before=None, strides=None):
+    """Psd.process_stream through poisoned, guarded buffers: x (n_streams, n) complex64 -- (n_streams, 2n) uint8 with in_u8
+    -- fed in the calls [cuts[i], cuts[i+1]) (samples, multiples of hop).  The runner counts the segments itself (from
+    `segments_before`, else from what earlier run_psd calls on this handle left, else 0; after a reset pass 0) and holds every call to
+    rows = floor((segments_before mod A + n_in/H) / A).  A call that completes no row must leave its whole output buffer
+    (room for a row per stream, and the guards) poison.  Returns ((n_streams, rows, N) float32, the per-call counts)."""
+    S, N, H, A = ps.n_streams, ps.n_fft, ps.hop, ps.n_avg
+    x, item, n = _measure_x(ps, x, in_u8, 2)
+    cuts = _cuts(cuts, n)
+    seen = int(getattr(ps, "_segments_seen", 0) if segments_before is None else segments_before)
+    outs, counts = [], []
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        m = b - a
+        assert m % H == 0 and m > 0
+        want = psd_rows_of_call(seen, m, H, A)
+        si, so = strides(m, want * N) if strides else measure_strides(m, item, want * N, 4, aligned)
+        ilay, iraw = _measure_input(x, S, item, a, b, aligned, si)
+        # no row due: the declared range is empty, and a row stored by mistake for any stream still lands in the tail guard
+        olay = Layout(S, 4, want * N, so, 256, 256 + (0 if want else 4 * N))
+        d_in, d_out = _upload(api, iraw), _upload(api, olay.poisoned())
+        try:
+            k = ps.process_stream(d_in.ptr + ilay.front, m, d_out.ptr + olay.front, in_stride=si, out_stride=so)
+            oraw, iafter = _download(d_out), _download(d_in)
+        finally:
+            d_in.free()
+            d_out.free()
+        seen += m // H
+        ps._segments_seen = seen
+        if k != want:
+            raise CountError("call [%d, %d): %d rows, floor((%d mod %d + %d) / %d) = %d" % (a, b, k, seen - m // H, A, m // H, A, want))
+        check_written(oraw, olay, want * N)
+        check_input_intact(iafter, iraw)
+        counts.append(k)
+        outs.append(np.stack([olay.take(oraw, s, want * N) for s in range(S)]).reshape(S, want, N))
+    y = np.concatenate(outs, axis=1) if outs else np.zeros((S, 0, N), np.float32)
+    return y, counts
+
+
+def run_corr(api, cr, x, cuts=None, in_u8=False, aligned=True, dense=True, strides=None):
+    """Corr.process_stream through poisoned, guarded buffers: x (n_streams, n) complex64 -- (n_streams, 2n) uint8 with in_u8
+    -- fed in the calls [cuts[i], cuts[i+1]) (samples, multiples of block).  peak_val, peak_idx and (dense) the metric each
+    sit in a buffer of their own with a front guard, gaps between the (stream, template) rows and a tail guard; exactly
+    n_in / B cells per row of each peak array and n_in per row of the metric lose their poison.  Returns (peak_val
+    (n_streams, K, blocks) float32, peak_idx uint32, m (n_streams, K, n) float32 or None, the per-call block counts)."""
+    S, K, B = cr.n_streams, cr.n_templates, cr.block
+    x, item, n = _measure_x(cr, x, in_u8, 2)
+    cuts = _cuts(cuts, n)
+    vals, idxs, ms, counts = [], [], [], []
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        m = b - a
+        assert m % B == 0 and m > 0
+        want = m // B
+        si, sp = strides(m, want) if strides else measure_strides(m, item, want, 4, aligned)
+        sm = _odd_stride(m, 4, 16 if aligned else 4, 9)
+        ilay, iraw = _measure_input(x, S, item, a, b, aligned, si)
+        play = Layout(S * K, 4, want, sp, 256, 256)
+        mlay = Layout(S * K, 4, m, sm, 256, 256)
+        d_in, d_val, d_idx = _upload(api, iraw), _upload(api, play.poisoned()), _upload(api, play.poisoned())
+        d_m = _upload(api, mlay.poisoned()) if dense else None
+        try:
+            k = cr.process_stream(d_in.ptr + ilay.front, m, d_val.ptr + play.front, d_idx.ptr + play.front,
+                                  d_m.ptr + mlay.front if dense else None, in_stride=si, peak_stride=sp, metric_stride=sm)
+            vraw, xraw, iafter = _download(d_val), _download(d_idx), _download(d_in)
+            mraw = _download(d_m) if dense else None
+        finally:
+            for d in (d_in, d_val, d_idx, d_m):
+                if d is not None:
+                    d.free()
+        if k != want:
+            raise CountError("call [%d, %d): %d blocks, n_in / B = %d" % (a, b, k, want))
+        check_written(vraw, play, want)
+        check_written(xraw, play, want)
+        if dense:
+            check_written(mraw, mlay, m)
+        check_input_intact(iafter, iraw)
+        counts.append(k)
+        vals.append(np.stack([play.take(vraw, r, want) for r in range(S * K)]).reshape(S, K, want))
+        idxs.append(np.stack([play.take(xraw, r, want, np.uint32) for r in range(S * K)]).reshape(S, K, want))
+        if dense:
+            ms.append(np.stack([mlay.take(mraw, r, m) for r in range(S * K)]).reshape(S, K, m))
+    return np.concatenate(vals, axis=2), np.concatenate(idxs, axis=2), np.concatenate(ms, axis=2) if dense else None, counts
+
+
+def run_iir(api, f, x, cuts=None, in_u8=False, aligned=True, strides=None):
+    """Iir.process_stream through poisoned, guarded buffers: x (n_streams, n) complex64 -- float32 on a real handle,
+    (n_streams, 2n) uint8 with in_u8 -- fed in the calls [cuts[i], cuts[i+1]) (samples, multiples of the block).  strides:
+    a function (n_in, n_out) -> (in_stride, out_stride) in items, else measure_strides.  n_out == n_in, or CountError.
+    Returns (n_streams, n) complex64 / float32."""
+    S, w = f.n_streams, 2 if f.data_complex else 1
+    x, item, n = _measure_x(f, x, in_u8, w)
+    cuts = _cuts(cuts, n)
+    outs = []
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        m = b - a
+        assert m > 0
+        si, so = strides(m, m) if strides else measure_strides(m, item, m, 4 * w, aligned)
+        ilay, iraw = _measure_input(x, S, item, a, b, aligned, si)
+        olay = Layout(S, 4 * w, m, so, 256, 256)
+        d_in, d_out = _upload(api, iraw), _upload(api, olay.poisoned())
+        try:
+            k = f.process_stream(d_in.ptr + ilay.front, m, d_out.ptr + olay.front, in_stride=si, out_stride=so)
+            oraw, iafter = _download(d_out), _download(d_in)
+        finally:
+            d_in.free()
+            d_out.free()
+        if k != m:
+            raise CountError("call [%d, %d): n_out %d, n_in %d" % (a, b, k, m))
+        check_written(oraw, olay, m)
+        check_input_intact(iafter, iraw)
+        outs.append(np.stack([olay.take(oraw, s, m, np.complex64 if w == 2 else np.float32) for s in range(S)]))
+    return np.concatenate(outs, axis=1)
 
 
 # ------------------------------------------------------------------------------------------------ guarded buffers in place

@@ -107,6 +107,9 @@ def test_parity_grid(api, N, hop_of, A, n_streams):
     (4096, 4096, 5, [2, 2, 1, 3, 13, 1]),
     # C = 2, a chunk is a whole row (no row fold), four segments to a batch of the N = 256 kernel: inside a row, on row edges
     (256, 97, 2, [1, 2, 3, 1, 4, 2]),
+    # the two sizes whose first pass is the radix-2 one; N = 512 has two segments to a batch.  C = 8 and C = 4 as above
+    (512, 201, 37, [3, 5, 20, 9, 45, 1, 60]),
+    (2048, 2048, 5, [2, 2, 1, 3, 13, 1]),
 ])
 def test_cutting_the_stream_gives_the_same_bits(api, N, H, A, irregular):
     assert api.psd_plan(N, H, A)[0] == {37: 8, 5: 4, 2: 2}[A]
@@ -127,7 +130,7 @@ def test_cutting_the_stream_gives_the_same_bits(api, N, H, A, irregular):
 
 @pytest.mark.timeout(300)
 @pytest.mark.parametrize("offset", [0, 2, 6])
-@pytest.mark.parametrize("N, H, A", [(256, 97, 5), (1024, 1024, 3), (4096, 2048, 4)])
+@pytest.mark.parametrize("N, H, A", [(256, 97, 5), (1024, 1024, 3), (4096, 2048, 4), (512, 201, 3), (2048, 1024, 4)])
 def test_u8_input_equals_converted_cf32(api, L, N, H, A, offset):
     segs = 3 * A + 2
     n = segs * H
@@ -171,10 +174,11 @@ def test_u8_input_equals_converted_cf32(api, L, N, H, A, offset):
 
 
 @pytest.mark.timeout(300)
-@pytest.mark.parametrize("N", [256, 1024, 4096])
+@pytest.mark.parametrize("N", [256, 1024, 4096, 512, 2048])
 def test_a_tone_lands_in_its_bin(api, N):
     H, A, a, scale = N, 6, 0.375, 0.5
-    for k0 in (3, N - 3):
+    # 1, N/2 - 1, N/2, N/2 + 1: the bins an even/odd mix-up in the first pass would swap
+    for k0 in (3, N - 3, 1, N // 2 - 1, N // 2, N // 2 + 1):
         x = (a * np.exp(2j * np.pi * k0 * np.arange(2 * A * H) / N)).astype(np.complex64)
         rows = api.Psd(np.ones(N, np.float32), H, A, scale=scale).spectrum(x)[0]
         assert rows.shape == (2, N)
