@@ -1382,6 +1382,77 @@ int sfe_dsp_mod_process_stream(sfe_mod_t h, const void *d_bytes, size_t in_strid
                                size_t *n_written, sfe_stream_t stream);
 int sfe_dsp_mod_destroy(sfe_mod_t h);
 
+/* ------------------------------------------------- streaming FM, phase and envelope detector
+ * The stage between a tuned complex stream and a real signal: one real float32 output per complex
+ * input sample of every stream, by one of three laws fixed at create.  With n the absolute sample
+ * index since create / reset and x[-1] = 0 + 0j:
+ *     SFE_POLAR_FM   y[n] = gain at2(im, re) of x[n] conj(x[n-1])     the quadrature discriminator
+ *     SFE_POLAR_PM   y[n] = gain at2(x.i, x.r)
+ *     SFE_POLAR_AM   y[n] = gain sqrtf(fmaf(x.r, x.r, x.i x.i))
+ * so FM's first output on a fresh handle is +0.  Behind sfe_dsp_ddc_* (K tunings in one pass) and in
+ * front of a real decimator and sfe_dsp_iir_* (de-emphasis, DC blocker) this is K FM, FSK or AM
+ * receivers that never leave the device.
+ * The law is csrc/polar_law.h, one header the kernel and the host plan both compile; every multiply
+ * that feeds an add is an explicit fmaf and everything else is one IEEE float32 operation:
+ *     FM:  re = fmaf(x.r, p.r, x.i p.i);   im = fmaf(x.i, p.r, -(x.r p.i));        p = x[n-1]
+ *     at2(y, x):
+ *       ax = |x|; ay = |y|; mx = max(ax, ay); mn = min(ax, ay);
+ *       z = (mx == 0) ? 0 : mn / mx                       one correctly rounded division
+ *       s = z z;  q = C8;  q = fmaf(q, s, C7); ... q = fmaf(q, s, C0);  r = q z
+ *       if (ay > ax) r = PI_2 - r;   if (x < 0) r = PI - r;   if (y < 0) r = -r     (-0 is not below 0)
+ * with PI_2 = 0x1.921fb6p+0f, PI = 0x1.921fb6p+1f and C0 .. C8 the literals of the header (a
+ * weighted least-squares fit of atan(z)/z in z^2).  at2 is within 2 ulp(pi) = 4.77e-7 rad of atan2,
+ * FM within 3 ulp(pi) = 7.15e-7 rad of the angle of the exact product, AM within 1.3e-7 relative
+ * (DESIGN.md 4.19 has the measured figures).  at2(0, 0) = +0, at2(0, -1) = PI, at2(-0, -1) = PI.
+ * Input: cf32, or SFE_FMT_U8 (I,Q) byte pairs converted (b-128)*(1/127) exactly as
+ * sfe_dsp_rx_u8_to_f32 converts them; the law then runs on the converted floats.
+ * Contracts about bits, for finite input:
+ *   1. the device's output equals sfe_dsp_polar_plan's bit for bit;
+ *   2. cutting the stream into calls of ANY sizes >= 1 gives the one-call output bit for bit, and so
+ *      does moving a buffer to any element-aligned address or changing the strides: there is NO
+ *      GRANULE;
+ *   3. u8 input gives the bits of the cf32 path on the converted samples, and the format may change
+ *      between calls (the carried sample is kept as float32);
+ *   4. stream s of an n-stream handle gives the bits of a one-stream handle fed that stream;
+ *   5. reset makes a fresh handle.
+ * A non-finite sample makes at most the outputs that read it non-finite (two in FM, one otherwise);
+ * nothing persists. */
+#define SFE_POLAR_FM 0
+#define SFE_POLAR_PM 1
+#define SFE_POLAR_AM 2
+typedef void *sfe_polar_t; /* opaque: one detector over n_streams streams */
+/* Host-only (no GPU): the law on n_in samples of one stream in host memory (fmt: SFE_FMT_F32, n_in
+ * (re, im) float32 pairs; SFE_FMT_U8, n_in (I,Q) byte pairs; any alignment), written to out[0 .. n_in).
+ * prev is the carried sample, in and out: (re, im) of x[-1] on entry (0, 0 for a fresh stream),
+ * the last sample as float32 on return (unchanged by n_in = 0); NULL stands for a fresh stream and
+ * returns nothing.  Carried in every mode, read in FM only.  A mode or format other than the above,
+ * a non-finite gain and a null buffer with n_in > 0 are SFE_EINVAL with a message that starts with
+ * "polar: ". */
+int sfe_dsp_polar_plan(int mode, float gain, int fmt, const void *in, size_t n_in, float prev[2],
+                       float *out);
+/*   n_streams  independent streams, each with its own carried sample (1 .. 32767).
+ * mode, gain and n_streams are checked before the device ("polar: ..."): SFE_EINVAL for those on
+ * any machine, SFE_ENODEV without a GPU. */
+int sfe_dsp_polar_create(int mode, float gain, int n_streams, int device, sfe_polar_t *out);
+/* SFE_FMT_F32 (cf32 input, 8-byte aligned) or SFE_FMT_U8 ((I,Q) byte pairs, 2-byte aligned); any
+ * other format is SFE_EINVAL ("polar: ...").  A captured call keeps the format it was captured with. */
+int sfe_dsp_polar_set_input_format(sfe_polar_t h, int fmt);
+/* n_in samples of every stream: stream s at d_in + s*in_stride (samples of the input format) goes
+ * to d_out + s*out_stride (float32, 4-byte aligned).  *n_out = n_in.  Any n_in >= 1 below 2^31;
+ * n_in = 0 is a no-op.  out_stride < n_in is SFE_ERANGE; null or misaligned buffers, in_stride <
+ * n_in with more than one stream, overlapping input and output byte ranges and n_in >= 2^31 are
+ * SFE_EINVAL, each with a message that starts with "polar_process_stream: "; nothing is launched
+ * on a refusal.  Asynchronous on `stream`; one kernel launch: allocates nothing, does not
+ * synchronise the host and keeps no host counter, so a call on a stream under graph capture IS
+ * supported: the carried sample is then copied back behind the launch instead of changing
+ * buffers, so that every replay is the next call of the stream, and eager calls and replays may
+ * interleave on one handle. */
+int sfe_dsp_polar_process_stream(sfe_polar_t h, const void *d_in, size_t n_in, size_t in_stride,
+                                 float *d_out, size_t out_stride, size_t *n_out, sfe_stream_t stream);
+/* Zero the carried samples (a fresh handle). */
+int sfe_dsp_polar_reset(sfe_polar_t h);
+int sfe_dsp_polar_destroy(sfe_polar_t h);
+
 #ifdef __cplusplus
 }
 #endif

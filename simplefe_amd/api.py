@@ -10,7 +10,8 @@ Two layers, both thin:
     transpose, the synthesis filter bank (sfe_dsp_combine_*); `Psd`, the streaming Welch spectrum estimator (sfe_dsp_psd_*);
     `Corr`, the streaming preamble correlator bank (sfe_dsp_corr_*); `Iir`, the streaming biquad-cascade IIR filter
     (sfe_dsp_iir_*); `Beam`, the multi-stream beamformer / stream-mixing bank (sfe_dsp_beam_*); `Cov`, the streaming
-    spatial covariance estimator (sfe_dsp_cov_*); `Mod`, the burst modulator (sfe_dsp_mod_*).
+    spatial covariance estimator (sfe_dsp_cov_*); `Mod`, the burst modulator (sfe_dsp_mod_*); `Polar`, the FM, phase and
+    envelope detector (sfe_dsp_polar_*).
 
 Everything computes on the GPU through the C ABI; numpy is only the host container.
 """
@@ -1406,6 +1407,63 @@ class Mod(_Block):
             for x in held:
                 x.free()
         return np.ascontiguousarray(raw) if tx10 else np.ascontiguousarray(raw).view(np.complex64)
+
+
+def polar_plan(x, mode, gain, prev=None, in_u8=False):
+    """sfe_dsp_polar_plan (host only, no GPU): the detector's law on one stream, bit for bit what the device computes.  x is
+    (n,) complex64, or with in_u8 the 2n (I,Q) bytes; prev the carried sample (complex; None: a fresh stream).  Returns
+    (y (n,) float32, the carried sample after x as complex64)."""
+    if in_u8:
+        a = np.ascontiguousarray(x, dtype=np.uint8).reshape(-1)
+        n = a.size // 2
+    else:
+        a = np.ascontiguousarray(x, dtype=np.complex64).reshape(-1)
+        n = a.size
+    p = np.zeros(2, np.float32)
+    if prev is not None:
+        p[:] = (np.complex64(prev).real, np.complex64(prev).imag)
+    y = np.empty(n, np.float32)
+    check(_l.load().sfe_dsp_polar_plan(int(mode), float(gain), _l.FMT_U8 if in_u8 else _l.FMT_F32, a.ctypes.data if n else None, n,
+                                       p.ctypes.data_as(_l.fp), y.ctypes.data_as(_l.fp)))
+    return y, p.view(np.complex64)[0]
+
+
+class Polar(_Block):
+    """Streaming FM, phase and envelope detector (sfe_dsp_polar_*): one real float32 output per complex sample of each of
+    n_streams streams; mode is lib.POLAR_FM (gain * angle of x[n] conj(x[n-1])), POLAR_PM (gain * angle of x[n]) or
+    POLAR_AM (gain * |x[n]|).  Any call size; FM carries the last sample from call to call."""
+    _prefix = "polar"
+
+    def __init__(self, mode, gain=1.0, n_streams=1, device=0):
+        self.mode, self.gain, self.n_streams = int(mode), float(gain), int(n_streams)
+        self.in_u8 = False
+        self._create(self.mode, self.gain, self.n_streams, device)
+
+    def set_input_format(self, fmt):
+        """lib.FMT_F32 (cf32) or lib.FMT_U8 ((I,Q) byte pairs, converted on load)."""
+        self._set_input_format(fmt)
+
+    def process_stream(self, d_in, n_in, d_out, in_stride=None, out_stride=None, stream=None):
+        """d_in / d_out: DeviceArray or raw device pointers; n_in >= 1 samples per stream.  Stream s goes from
+        d_in + s*in_stride samples of the input format to d_out + s*out_stride floats; both strides default to n_in.
+        Returns n_out = n_in."""
+        return self._process_stream(d_in, n_in, in_stride, d_out, int(n_in) if out_stride is None else out_stride, stream)
+
+    def detect(self, x):
+        """Host convenience, computed on the GPU, continuing the handle's state: x is (n_streams, n) complex64, or with
+        FMT_U8 uint8 (I,Q) pairs with a last axis of 2n ((n,) / (2n,) for one stream).  Returns (n_streams, n) ((n,))
+        float32."""
+        one = self.n_streams == 1 and np.ndim(x) == 1
+        d_in, n = self._upload_input(x)
+        d_out = DeviceArray(max(1, self.n_streams * n))
+        try:
+            if n:
+                self.process_stream(d_in, n, d_out)
+            y = d_out.to_numpy(self.n_streams * n).reshape(self.n_streams, n)
+        finally:
+            d_in.free()
+            d_out.free()
+        return np.ascontiguousarray(y[0] if one else y)
 
 
 def rs_plan(state, upsample, n_in, out_len, rate):

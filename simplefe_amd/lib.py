@@ -18,6 +18,7 @@ RS_RESAMPLE, RS_DECIMATE = 0, 1
 RS_ALGO_AUTO, RS_ALGO_DIRECT, RS_ALGO_FFT, RS_ALGO_MFMA = 0, 1, 2, 3
 FMT_F32, FMT_U8, FMT_TX10 = 0, 1, 2
 VIT_IN_SOFT, VIT_IN_BPSK, VIT_IN_QPSK = 0, 1, 2      # sfe_dsp_vit_*: what d_in holds
+POLAR_FM, POLAR_PM, POLAR_AM = 0, 1, 2               # sfe_dsp_polar_*: the law fixed at create
 
 
 class TimeState(C.Structure):
@@ -190,6 +191,12 @@ SIGNATURES = {
                                  C.POINTER(vp)]),
     "sfe_dsp_mod_process_stream": (i32, [vp, vp, sz, sz, C.c_int64, C.c_int64, vp, sz, C.POINTER(sz), vp]),
     "sfe_dsp_mod_destroy": (i32, [vp]),
+    "sfe_dsp_polar_plan": (i32, [i32, f32, i32, vp, sz, fp, fp]),
+    "sfe_dsp_polar_create": (i32, [i32, f32, i32, i32, C.POINTER(vp)]),
+    "sfe_dsp_polar_set_input_format": (i32, [vp, i32]),
+    "sfe_dsp_polar_process_stream": (i32, [vp, vp, sz, sz, vp, sz, C.POINTER(sz), vp]),
+    "sfe_dsp_polar_reset": (i32, [vp]),
+    "sfe_dsp_polar_destroy": (i32, [vp]),
 }
 
 # the diagnostic library only (simplefe_amd/csrc/diag/sfe_dsp_diag.h; scripts/ load it by pointing LIB_PATH at it): bound when present

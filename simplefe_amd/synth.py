@@ -451,6 +451,28 @@ def iir_grid_filters():
             "dc(0.999)+butter(8,0.1)": np.vstack([iir_dc_blocker(0.999), iir_butter_lowpass(8, 0.1)])}
 
 
+# ---- the FM, phase and envelope detector (sfe_dsp_polar_*)
+POLAR_FM, POLAR_PM, POLAR_AM = 0, 1, 2
+
+
+def polar_reference(x, mode, gain=1.0, prev=0.0):
+    """The law of sfe_dsp_polar_* in float64 on the samples as given: x is (..., n) complex; `prev` (a scalar, or one value
+    per stream) stands before x[..., 0] in FM.  FM: gain * angle of the exact product x[n] conj(x[n-1]); PM: gain * angle
+    of x[n]; AM: gain * |x[n]|.  Returns (..., n) float64."""
+    x = np.asarray(x).astype(np.complex128)
+    gain = float(np.float32(gain))
+    if mode == POLAR_FM:
+        p = np.concatenate([np.broadcast_to(np.asarray(prev, np.complex128), x.shape[:-1])[..., None], x[..., :-1]], axis=-1)
+        # the product's parts as sums of two exact float64 products of float32 values: one rounding each
+        # (+ 0.0: a product that vanishes has the angle 0, whatever the signs of its zeros)
+        return gain * np.arctan2(x.imag * p.real - x.real * p.imag + 0.0, x.real * p.real + x.imag * p.imag + 0.0)
+    if mode == POLAR_PM:
+        return gain * np.arctan2(x.imag, x.real)
+    if mode == POLAR_AM:
+        return gain * np.hypot(x.real, x.imag)
+    raise ValueError("polar_reference: mode %r" % (mode,))
+
+
 # ---- the beamformer / stream-mixing bank (sfe_dsp_beam_*): weights are (M, B, S) complex64 ((B, S): one band)
 def _beam_weights(W, V):
     W = np.asarray(W, dtype=np.complex64)
