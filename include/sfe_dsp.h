@@ -1453,6 +1453,94 @@ int sfe_dsp_polar_process_stream(sfe_polar_t h, const void *d_in, size_t n_in, s
 int sfe_dsp_polar_reset(sfe_polar_t h);
 int sfe_dsp_polar_destroy(sfe_polar_t h);
 
+/* ------------------------------------------------- spectrum occupancy detector over psd rows
+ * From a row of N float32 spectrum bins to a decision, on the device: a robust noise floor (an exact
+ * order statistic), a threshold, a morphological closing, and one compact record per emission --
+ * where it is, how wide, its peak, its power and its first moment -- beside an optional per-bin
+ * mask.  sfe_dsp_psd_* leaves its rows exactly where this block reads them, so psd -> occ runs
+ * without the host, and a row of 16 KB goes down as 16 + 32 E bytes.  Stateless per row: no reset,
+ * no host counter, nothing carried.
+ * The law is csrc/occ_law.h, one header the kernel and the host plan both compile.  A row is
+ * x[0..N); the parameters, fixed at create, are
+ *     n_bins = N   8 <= N <= 4096, any integer; even when shift is set
+ *     rank         0 <= rank < N          factor     float32, finite, > 0
+ *     min_level    float32, finite        gap        0 <= gap < N
+ *     min_width    1 <= min_width <= N    max_emissions = E, 1 <= E <= 64        shift  0 or 1
+ *  1. Scan order.  xs[p] = x[(p + N - o) mod N], o = N/2 with shift and 0 without.  With shift, p
+ *     walks psd's bins from frequency -1/2 upwards, so an emission across DC is one run.  The signed
+ *     bin of position p is j = p - o: with shift, frequency j/N cycles per sample (what ddc wants).
+ *  2. Non-finite rows.  If any value of the row is a NaN or an infinity: status bit 0 is set,
+ *     count = 0, floor and thr are the word 0x7fc00000, all E records and the mask row are zero
+ *     bytes, and nothing else is computed.
+ *  3. Floor.  floor is the value of rank `rank` (0 = the smallest) of the row, in the total order of
+ *     the keys  bits ^ (sign ? 0xffffffff : 0x80000000)  -- so -0 sorts below +0.  An exact
+ *     selection: floor's bit pattern is that of an element of the row.
+ *  4. Threshold and occupancy.  thr = fmaxf(factor * floor, min_level): one float32 multiply, and the
+ *     greater of the two in the order of the keys (so of -0 and +0 it is +0: IEEE 754-2019's
+ *     maximum).  occ[p] = xs[p] > thr, the float32 comparison.
+ *  5. Closing.  c[p] is true when occ[p] is, or when there are occupied positions a < p < b, the
+ *     nearest on each side, with b - a - 1 <= gap.  No wrap across the ends of the scan.
+ *  6. Emissions.  The maximal runs [lo, hi] of c with hi - lo + 1 >= min_width, in ascending lo;
+ *     count is how many there are.  count may exceed E: status bit 1 is set and the first E are
+ *     recorded.
+ *  7. Per emission.  peak_val is the maximum of xs over the run (the float32 comparison) and peak
+ *     the smallest position that attains it.  sum and moment are folded over tiles of 16 aligned
+ *     scan positions [16t, 16t + 16): a tile partial is the float32 left fold from +0, in ascending p
+ *     over run and tile, of  acc + xs[p]  (sum)  and of  fmaf((float)(p - lo), xs[p], acc)  (moment);
+ *     the emission's value is the float32 left fold from +0 of its tile partials in ascending t.
+ *     The order is a function of positions only.  The caller's centroid is lo + moment / sum.
+ *  8. Outputs for row slot q.  info[q]: floor, thr, count, status.  rec[q E + r], r < min(count, E):
+ *     lo, hi, peak in signed bins, peak_val, sum, moment, two zero words; records r >= min(count, E)
+ *     are zero bytes, so every byte of every output is written by every call.  The optional
+ *     mask[q N + k] is 1 where bin k -- in the row's OWN numbering, whatever shift is -- lies in one
+ *     of the `count` emissions (those beyond E included) and 0 elsewhere: used directly, a
+ *     per-channel gate for a channelizer's output.
+ * The only fused operation of the law is the fmaf of step 7; everything else is one IEEE float32
+ * operation, a comparison, or integer work.
+ * Contracts about bits:
+ *   1. the device's bytes equal sfe_dsp_occ_plan's;
+ *   2. a row's outputs depend on that row and the parameters only: never on its neighbours, its
+ *      address, the strides, the call's size or the grid;
+ *   3. with and without d_mask, info and rec are the same bytes. */
+#define SFE_OCC_NONFINITE 1u /* status bit 0: the row held a NaN or an infinity */
+#define SFE_OCC_TRUNCATED 2u /* status bit 1: count > max_emissions */
+typedef struct {
+    float floor, thr;
+    uint32_t count, status;
+} sfe_occ_info; /* 16 bytes */
+typedef struct {
+    int32_t lo, hi, peak; /* signed bins */
+    float peak_val, sum, moment;
+    uint32_t zero[2];
+} sfe_occ_rec;            /* 32 bytes */
+typedef void *sfe_occ_t; /* opaque: one detector */
+/* Host-only (no GPU): the law on n_rows rows of n_bins float32 in host memory, row i at
+ * rows + i*n_bins; info[i], rec[i*E ..], mask[i*n_bins ..].  Any output may be NULL.  Parameters
+ * outside the ranges above are SFE_EINVAL with a message that starts with "occ: "; so is a null
+ * `rows` with n_rows > 0.  With n_rows = 0 it validates the parameters. */
+int sfe_dsp_occ_plan(int n_bins, int rank, float factor, float min_level, int gap, int min_width,
+                     int max_emissions, int shift, const float *rows, size_t n_rows,
+                     sfe_occ_info *info, sfe_occ_rec *rec, uint8_t *mask);
+/* The parameters are checked before the device is touched ("occ: ..."): SFE_EINVAL for those on any
+ * machine, SFE_ENODEV without a GPU. */
+int sfe_dsp_occ_create(int n_bins, int rank, float factor, float min_level, int gap, int min_width,
+                       int max_emissions, int shift, int device, sfe_occ_t *out);
+/* n_rows rows of each of n_streams streams: row j of stream s is read at d_in + s*in_stride + j*N
+ * floats -- where sfe_dsp_psd_process_stream leaves its rows -- and goes to slot q = s*out_stride + j
+ * of every output: d_info[q], d_rec[q*E ..], d_mask[q*N ..] (d_mask may be NULL).
+ * *n_done = n_streams * n_rows.  n_rows = 0 or n_streams = 0 is a no-op.  out_stride < n_rows is
+ * SFE_ERANGE; null or misaligned buffers (float32, info and records 4 bytes), in_stride < n_rows*N
+ * with more than one stream, an overlap between the input and any output or between two outputs,
+ * and 2^31 or more rows are SFE_EINVAL, each with a message that starts with
+ * "occ_process_stream: "; nothing is launched on a refusal.  Asynchronous on `stream`; one kernel
+ * launch and nothing else: allocates nothing, does not synchronise the host, keeps no counter, so a
+ * call on a stream under graph capture IS supported. */
+int sfe_dsp_occ_process_stream(sfe_occ_t h, const float *d_in, size_t n_streams, size_t n_rows,
+                               size_t in_stride, sfe_occ_info *d_info, sfe_occ_rec *d_rec,
+                               uint8_t *d_mask, size_t out_stride, size_t *n_done,
+                               sfe_stream_t stream);
+int sfe_dsp_occ_destroy(sfe_occ_t h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,7 @@ Two layers, both thin:
     `Corr`, the streaming preamble correlator bank (sfe_dsp_corr_*); `Iir`, the streaming biquad-cascade IIR filter
     (sfe_dsp_iir_*); `Beam`, the multi-stream beamformer / stream-mixing bank (sfe_dsp_beam_*); `Cov`, the streaming
     spatial covariance estimator (sfe_dsp_cov_*); `Mod`, the burst modulator (sfe_dsp_mod_*); `Polar`, the FM, phase and
-    envelope detector (sfe_dsp_polar_*).
+    envelope detector (sfe_dsp_polar_*); `Occ`, the spectrum occupancy detector over a Psd's rows (sfe_dsp_occ_*).
 
 Everything computes on the GPU through the C ABI; numpy is only the host container.
 """
@@ -1464,6 +1464,77 @@ class Polar(_Block):
             d_in.free()
             d_out.free()
         return np.ascontiguousarray(y[0] if one else y)
+
+
+# sfe_occ_info and sfe_occ_rec of include/sfe_dsp.h
+OCC_INFO = np.dtype([("floor", "<f4"), ("thr", "<f4"), ("count", "<u4"), ("status", "<u4")])
+OCC_REC = np.dtype([("lo", "<i4"), ("hi", "<i4"), ("peak", "<i4"), ("peak_val", "<f4"), ("sum", "<f4"), ("moment", "<f4"),
+                    ("zero", "<u4", (2,))])
+
+
+def _occ_params(n_bins, rank, factor, min_level, gap, min_width, max_emissions, shift):
+    return (int(n_bins), int(rank), float(factor), float(min_level), int(gap), int(min_width), int(max_emissions), int(shift))
+
+
+def occ_plan(rows, rank, factor, min_level=0.0, gap=0, min_width=1, max_emissions=16, shift=False, n_bins=None):
+    """sfe_dsp_occ_plan (host only, no GPU): the occupancy detector's law on rows (..., n_bins) float32, byte for byte what
+    the device computes.  Returns (info (rows,) OCC_INFO, rec (rows, max_emissions) OCC_REC, mask (rows, n_bins) uint8).
+    Raises SfeError on parameters the block refuses; rows None (with n_bins) only validates them."""
+    if rows is None:
+        check(_l.load().sfe_dsp_occ_plan(*_occ_params(n_bins, rank, factor, min_level, gap, min_width, max_emissions, shift), None, 0, None,
+                                         None, None))
+        return None
+    x = np.ascontiguousarray(rows, dtype=np.float32)
+    x = x.reshape(1, -1) if x.ndim == 1 else x.reshape(-1, x.shape[-1])
+    R, N = x.shape
+    E = int(max_emissions)
+    info, rec, mask = np.empty(R, OCC_INFO), np.empty((R, max(E, 0)), OCC_REC), np.empty((R, N), np.uint8)
+    check(_l.load().sfe_dsp_occ_plan(*_occ_params(N, rank, factor, min_level, gap, min_width, E, shift), x.ctypes.data_as(_l.fp), R,
+                                     info.ctypes.data, rec.ctypes.data, mask.ctypes.data))       # (the parameters are checked first)
+    return info, rec, mask
+
+
+class Occ(_Block):
+    """Spectrum occupancy detector (sfe_dsp_occ_*): per row of n_bins float32 spectrum bins -- a Psd's rows where it left
+    them -- the floor (the value of rank `rank`), the threshold max(factor * floor, min_level), and one record per emission
+    (a run of bins above the threshold, gaps of at most `gap` bins closed, at least min_width wide): bounds and peak in
+    signed bins, peak value, sum and first moment.  The device's bytes are occ_plan's.  Stateless: there is no reset."""
+    _prefix = "occ"
+
+    def __init__(self, n_bins, rank, factor, min_level=0.0, gap=0, min_width=1, max_emissions=16, shift=False, device=0):
+        self.n_bins, self.max_emissions, self.shift = int(n_bins), int(max_emissions), bool(shift)
+        self._create(*_occ_params(n_bins, rank, factor, min_level, gap, min_width, max_emissions, shift), device)
+
+    def process_stream(self, d_in, n_rows, d_info, d_rec, d_mask=None, n_streams=1, in_stride=None, out_stride=None, stream=None):
+        """d_*: DeviceArray or raw device pointers.  Row j of stream s is read at d_in + s*in_stride + j*n_bins floats
+        (in_stride defaults to n_rows*n_bins) and goes to slot s*out_stride + j (out_stride defaults to n_rows) of d_info
+        (16 bytes a slot), d_rec (32*max_emissions) and, if given, d_mask (n_bins).  Returns the rows done."""
+        k = C.c_size_t(0)
+        check(self._fn("process_stream")(self._h, self._ptr(d_in), int(n_streams), int(n_rows),
+                                         int(n_rows) * self.n_bins if in_stride is None else int(in_stride), self._ptr(d_info),
+                                         self._ptr(d_rec), self._ptr(d_mask), int(n_rows) if out_stride is None else int(out_stride),
+                                         C.byref(k), stream))
+        return k.value
+
+    def reset(self):
+        raise AttributeError("Occ has no reset: it carries no state")
+
+    def detect(self, rows, mask=True):
+        """Host convenience, computed on the GPU: rows is (..., n_bins) float32; returns what occ_plan returns (mask None
+        without `mask`)."""
+        x = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, self.n_bins)
+        R, N, E = x.shape[0], self.n_bins, self.max_emissions
+        held = [DeviceArray.from_numpy(x), DeviceArray(max(1, 4 * R)), DeviceArray(max(1, 8 * E * R)), DeviceArray(max(1, (R * N + 3) // 4))]
+        try:
+            if R:
+                self.process_stream(held[0], R, held[1], held[2], held[3] if mask else None)
+            info = held[1].to_numpy(4 * R).view(OCC_INFO)
+            rec = held[2].to_numpy(8 * E * R).view(OCC_REC).reshape(R, E)
+            m = held[3].to_numpy().view(np.uint8)[:R * N].reshape(R, N) if mask else None
+        finally:
+            for d in held:
+                d.free()
+        return info, rec, (np.ascontiguousarray(m) if mask else None)
 
 
 def rs_plan(state, upsample, n_in, out_len, rate):

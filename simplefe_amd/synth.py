@@ -473,6 +473,81 @@ def polar_reference(x, mode, gain=1.0, prev=0.0):
     raise ValueError("polar_reference: mode %r" % (mode,))
 
 
+# ---- the spectrum occupancy detector (sfe_dsp_occ_*)
+OCC_INFO = np.dtype([("floor", "<f4"), ("thr", "<f4"), ("count", "<u4"), ("status", "<u4")])
+OCC_REC = np.dtype([("lo", "<i4"), ("hi", "<i4"), ("peak", "<i4"), ("peak_val", "<f4"), ("sum", "<f4"), ("moment", "<f4"),
+                    ("zero", "<u4", (2,))])
+
+
+def _occ_keys(v):
+    """The total order of the law's step 3 as uint32: ascending keys are ascending float32 values, -0 below +0."""
+    b = np.ascontiguousarray(v, dtype=np.float32).view(np.uint32)
+    return b ^ np.where(b >> 31, np.uint32(0xFFFFFFFF), np.uint32(0x80000000))
+
+
+def _fma32(a, b, c):
+    """fmaf(a, b, c) of float32 values whose product a b is exact in float64 (a is a small integer): the float64 sum is
+    rounded to odd (its rounding error from TwoSum), so that the rounding to float32 is the only one that counts."""
+    import math
+    import struct
+    p = float(a) * float(b)
+    s = p + float(c)
+    if math.isfinite(s):
+        t = s - p
+        err = (p - (s - t)) + (float(c) - t)
+        if err != 0.0 and not struct.unpack("<q", struct.pack("<d", s))[0] & 1:
+            s = math.nextafter(s, math.inf if err > 0 else -math.inf)
+    return np.float32(s)
+
+
+def occ_reference(rows, rank, factor, min_level=0.0, gap=0, min_width=1, max_emissions=16, shift=False):
+    """The law of sfe_dsp_occ_* (include/sfe_dsp.h) restated in numpy on rows (..., N) float32: the floor by np.sort of the
+    keys, the runs from the distances between occupied positions, the folds as explicit float32 operations.  Returns
+    (info (rows,) OCC_INFO, rec (rows, max_emissions) OCC_REC, mask (rows, N) uint8)."""
+    x = np.ascontiguousarray(rows, dtype=np.float32)
+    x = x.reshape(1, -1) if x.ndim == 1 else x.reshape(-1, x.shape[-1])
+    R, N = x.shape
+    E, o = int(max_emissions), (N // 2 if shift else 0)
+    info, rec, mask = np.zeros(R, OCC_INFO), np.zeros((R, E), OCC_REC), np.zeros((R, N), np.uint8)
+    own = (np.arange(N) + N - o) % N                    # the row's own index of scan position p
+    f32 = np.float32
+    for i in range(R):
+        xs = x[i, own]
+        if not np.isfinite(xs).all():
+            info[i] = (0, 0, 0, 1)
+            info[i:i + 1].view(np.uint32)[:2] = 0x7FC00000
+            continue
+        keys = np.sort(_occ_keys(xs))
+        k = keys[rank:rank + 1]
+        floor = (k ^ np.where(k >> 31, np.uint32(0x80000000), np.uint32(0xFFFFFFFF))).view(np.float32)[0]
+        with np.errstate(over="ignore"):
+            t = f32(factor) * floor
+        m = f32(min_level)
+        thr = t if _occ_keys(t)[()] >= _occ_keys(m)[()] else m
+        at = np.flatnonzero(xs > thr)
+        count = 0
+        if at.size:
+            cut = np.flatnonzero(np.diff(at) - 1 > gap)             # the gaps the closing leaves open
+            los, his = at[np.r_[0, cut + 1]], at[np.r_[cut, at.size - 1]]
+            wide = his - los + 1 >= min_width
+            for lo, hi in zip(los[wide].tolist(), his[wide].tolist()):
+                mask[i, own[lo:hi + 1]] = 1
+                if count < E:
+                    seg = xs[lo:hi + 1]
+                    peak = lo + int(np.argmax(seg))                 # the first of equal maxima
+                    total, moment = f32(0), f32(0)
+                    for t0 in range(lo - lo % 16, hi + 1, 16):
+                        ps, pm = f32(0), f32(0)
+                        for p in range(max(lo, t0), min(hi, t0 + 15) + 1):
+                            ps = ps + xs[p]
+                            pm = _fma32(p - lo, xs[p], pm)
+                        total, moment = total + ps, moment + pm
+                    rec[i, count] = (lo - o, hi - o, peak - o, xs[peak], total, moment, (0, 0))
+                count += 1
+        info[i] = (floor, thr, count, 2 if count > E else 0)
+    return info, rec, mask
+
+
 # ---- the beamformer / stream-mixing bank (sfe_dsp_beam_*): weights are (M, B, S) complex64 ((B, S): one band)
 def _beam_weights(W, V):
     W = np.asarray(W, dtype=np.complex64)
