@@ -1541,6 +1541,87 @@ int sfe_dsp_occ_process_stream(sfe_occ_t h, const float *d_in, size_t n_streams,
                                sfe_stream_t stream);
 int sfe_dsp_occ_destroy(sfe_occ_t h);
 
+/* ------------------------------------------------- Reed-Solomon outer code, interleaved
+ * What stands outside the convolutional code on a link: behind sfe_dsp_vit_* the decoder of an
+ * interleaved Reed-Solomon code over GF(2^8), in front of sfe_dsp_mod_* its encoder, on the device.
+ * A Viterbi decoder fails in bursts of wrong bytes; the interleave spreads a burst over I
+ * codewords, the code corrects up to t bytes in each and says which codewords it could not
+ * correct.  Frames are independent; nothing is carried.  Integer arithmetic only.
+ * The law is csrc/reed_law.h, one header the kernels and the host plan both compile.
+ * Field: GF(2^8) modulo prim, a 9-bit polynomial in [0x100, 0x1ff]; alpha is the element 0x02, and
+ * prim is refused unless alpha has order 255 (0x11d and 0x187 pass; 0x11b does not: there x has
+ * order 51).  The representation is the conventional one; there is no dual basis.
+ * Code: n in [3, 255] (below 255: a shortened code), n_par in [2, 64] and n_par < n,
+ * k = n - n_par, t = floor(n_par / 2); fcr in [0, 254]; step in [1, 254] with gcd(step, 255) = 1.
+ * Byte j of a codeword is the coefficient of x^(n-1-j).  C is the set of words c of n bytes with
+ * c(alpha^(step (fcr + i))) = 0 for i = 0 .. n_par-1.  Systematic: bytes 0 .. k-1 are the message,
+ * the last n_par bytes are x^n_par m(x) mod g(x), g(x) the product of (x - alpha^(step (fcr + i))).
+ * Interleave: depth I in [1, 16].  A payload is P = I k bytes, a frame Fb = I n bytes.  Message
+ * byte j of codeword i is payload[j I + i]; codeword byte j of codeword i is frame[j I + i].  So
+ * frame[0 .. P) is the payload as it lies, and the I n_par parity bytes follow.  A run of up to I t
+ * consecutive wrong channel bytes is therefore always corrected: it puts at most t into any one
+ * codeword.
+ * Whitening: whiten is NULL or Fb bytes, copied at create.  The channel bytes are frame XOR whiten;
+ * the decoder XORs first.  The sequence is the caller's: a PN generator stays outside the library.
+ * Decode, per codeword: r is the de-whitened received word.  If some c in C has d(r, c) <= t it is
+ * unique: the output message is c's and the codeword's count is d(r, c) (errors in parity bytes
+ * count).  Otherwise the codeword is UNCORRECTABLE and its message bytes are r's as received.  For a
+ * shortened code C holds only words of length n: an r whose nearest word of the full-length code
+ * differs from it in a padded position is uncorrectable, not corrected.  There are no erasures:
+ * sfe_dsp_vit_* delivers no per-byte reliability to feed them.  No CRC either: beyond t errors a
+ * word may lie within t of ANOTHER codeword and decode to it (a miscorrection, by the same law).
+ * Decode, per frame b: P bytes at d_out + b*out_stride; two uint32 words at d_rec + 2b -- the sum of
+ * the counts of the corrected codewords, and a mask whose bit i is set iff codeword i is
+ * uncorrectable; an int32 status at d_status + b:
+ *   0  every codeword decoded
+ *   1  at least one codeword is uncorrectable (the others are still corrected)
+ *   2  d_status_in is given and its word for this frame is not 0: no input is read, the bytes are
+ *      0, the record (0, 2^I - 1)
+ * Encode, per frame: P payload bytes at d_payload + b*in_stride become Fb channel bytes at
+ * d_frame + b*out_stride.
+ * Promised about bytes: the same call gives the same bytes on every run; a frame's output depends
+ * on its bytes and the handle only -- never on b, n_frames, addresses, alignment or strides; the
+ * device's bytes, record and status EQUAL sfe_dsp_reed_plan's for every input, none excluded;
+ * nothing outside the slots named is written, to the byte.  Payloads and frames need no alignment;
+ * records and statuses 4 bytes.
+ * Glue.  Behind sfe_dsp_vit_*: n_info = 8 Fb, so Fb <= 1024 (RS(255,223) at depth 4 is 1020 bytes);
+ * the decoder's d_bits, out_stride and d_status are the whole glue.  In front of sfe_dsp_mod_*:
+ * d_frame and out_stride are the whole glue.
+ * A bad argument is SFE_EINVAL on any machine, with a message that starts with "reed: ". */
+typedef void *sfe_reed_t; /* opaque: one code; it owns its tables (roots, generator, locators, whitening) on the device and nothing in it changes after create */
+/* Host-only (no GPU): validates what create validates and reports P and Fb (each pointer may be
+ * NULL).  With in != NULL -- host memory laid out as d_frame of process_stream (encode = 0) or as
+ * d_payload of encode_stream (encode = 1) -- it runs n_frames frames by the law above, exactly as
+ * stated, into out (frame b at out + b*out_stride), record [n_frames][2] and status [n_frames];
+ * each of the three may be NULL.  status_in [n_frames] or NULL; with encode = 1 status_in, record
+ * and status are ignored.  The reference of the device's bytes.  Short strides are SFE_ERANGE. */
+int sfe_dsp_reed_plan(int prim, int fcr, int step, int n, int n_par, int depth,
+                      const uint8_t *whiten, int encode, const uint8_t *in, size_t in_stride,
+                      const int *status_in, size_t n_frames, uint8_t *out, size_t out_stride,
+                      uint32_t *record, int *status, int *payload_bytes, int *frame_bytes);
+/* Arguments are checked before the device is touched: SFE_EINVAL for a bad one on any machine,
+ * SFE_ENODEV without a GPU.  whiten is copied. */
+int sfe_dsp_reed_create(int prim, int fcr, int step, int n, int n_par, int depth,
+                        const uint8_t *whiten, int device, sfe_reed_t *out);
+/* n_frames frames each way.  d_status_in, d_rec and d_status may each be NULL.  *n_out = n_frames;
+ * n_frames = 0 is a no-op.  A stride below the bytes a frame reads or writes (P, Fb) is SFE_ERANGE;
+ * a null d_payload, d_frame or d_out, a misaligned record or status pointer, n_frames >= 2^31, a
+ * stride that takes a buffer's byte range to 2^62, and any output byte range that overlaps an
+ * input's or another output's are SFE_EINVAL, each with a message that starts with
+ * "reed_encode_stream: " or "reed_process_stream: "; nothing is launched on a refusal.
+ * Asynchronous on `stream`; one kernel launch and nothing else: allocates nothing, does not
+ * synchronise the host, carries no state (there is no reset, and a handle has no setter), so a call
+ * on a stream under graph capture IS supported.  Every loop of the kernels runs a number of times
+ * fixed by (n, n_par): a corrupt frame cannot lengthen a launch. */
+int sfe_dsp_reed_encode_stream(sfe_reed_t h, const void *d_payload, size_t in_stride,
+                               size_t n_frames, void *d_frame, size_t out_stride, size_t *n_out,
+                               sfe_stream_t stream);
+int sfe_dsp_reed_process_stream(sfe_reed_t h, const void *d_frame, size_t in_stride,
+                                const void *d_status_in, size_t n_frames, void *d_out,
+                                size_t out_stride, void *d_rec, void *d_status, size_t *n_out,
+                                sfe_stream_t stream);
+int sfe_dsp_reed_destroy(sfe_reed_t h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,8 @@ Two layers, both thin:
     `Corr`, the streaming preamble correlator bank (sfe_dsp_corr_*); `Iir`, the streaming biquad-cascade IIR filter
     (sfe_dsp_iir_*); `Beam`, the multi-stream beamformer / stream-mixing bank (sfe_dsp_beam_*); `Cov`, the streaming
     spatial covariance estimator (sfe_dsp_cov_*); `Mod`, the burst modulator (sfe_dsp_mod_*); `Polar`, the FM, phase and
-    envelope detector (sfe_dsp_polar_*); `Occ`, the spectrum occupancy detector over a Psd's rows (sfe_dsp_occ_*).
+    envelope detector (sfe_dsp_polar_*); `Occ`, the spectrum occupancy detector over a Psd's rows (sfe_dsp_occ_*);
+    `Reed`, the interleaved Reed-Solomon outer code behind a Vit and in front of a Mod (sfe_dsp_reed_*).
 
 Everything computes on the GPU through the C ABI; numpy is only the host container.
 """
@@ -1535,6 +1536,113 @@ class Occ(_Block):
             for d in held:
                 d.free()
         return info, rec, (np.ascontiguousarray(m) if mask else None)
+
+
+def _reed_shape(prim, fcr, step, n, n_par, depth, whiten):
+    """The shape arguments sfe_dsp_reed_plan and sfe_dsp_reed_create share, and what keeps the whitening bytes alive."""
+    w = None if whiten is None else np.ascontiguousarray(np.asarray(whiten, dtype=np.uint8).ravel())
+    if w is not None and w.size != max(int(depth), 0) * max(int(n), 0):
+        raise ValueError("reed: whiten has %d bytes for a frame of depth * n = %d" % (w.size, int(depth) * int(n)))
+    return (int(prim), int(fcr), int(step), int(n), int(n_par), int(depth), None if w is None else w.ctypes.data), w
+
+
+def reed_plan(prim, fcr, step, n, n_par, depth, whiten=None, data=None, encode=False, status_in=None):
+    """sfe_dsp_reed_plan (host only, no GPU): validates and, without data, returns (payload_bytes, frame_bytes).  With data
+    and encode -- (n_frames, >= payload_bytes) uint8 -- it returns the frames (n_frames, frame_bytes) uint8; with data and not
+    encode -- (n_frames, >= frame_bytes) uint8 channel bytes -- it returns (bytes (n_frames, payload_bytes) uint8, record
+    (n_frames, 2) uint32 -- the corrected byte count, the mask of uncorrectable codewords -- and status (n_frames,) int32).
+    These are the device's bytes.  status_in: int32 per frame or None.  Raises SfeError on arguments the block refuses."""
+    head, _alive = _reed_shape(prim, fcr, step, n, n_par, depth, whiten)
+    L, P, Fb = _l.load(), C.c_int(0), C.c_int(0)
+    if data is None:
+        check(L.sfe_dsp_reed_plan(*head, int(bool(encode)), None, 0, None, 0, None, 0, None, None, C.byref(P), C.byref(Fb)))
+        return P.value, Fb.value
+    check(L.sfe_dsp_reed_plan(*head, int(bool(encode)), None, 0, None, 0, None, 0, None, None, C.byref(P), C.byref(Fb)))
+    d = np.asarray(data, dtype=np.uint8)
+    d = np.ascontiguousarray(d.reshape(1, -1) if d.ndim == 1 else d)
+    nf = d.shape[0]
+    if status_in is not None:
+        status_in = np.ascontiguousarray(status_in, dtype=np.int32).ravel()
+        if status_in.size != nf:
+            raise ValueError("reed_plan: status_in has %d entries for %d frames" % (status_in.size, nf))
+    out = np.empty((nf, Fb.value if encode else P.value), np.uint8)
+    rec, st = np.empty((nf, 2), np.uint32), np.empty(nf, np.int32)
+    check(L.sfe_dsp_reed_plan(*head, int(bool(encode)), d.ctypes.data if d.size else None, d.shape[1],
+                              None if status_in is None else status_in.ctypes.data, nf, out.ctypes.data, out.shape[1], rec.ctypes.data,
+                              st.ctypes.data, None, None))
+    return out if encode else (out, rec, st)
+
+
+class Reed(_Block):
+    """Interleaved Reed-Solomon outer code over GF(2^8) (sfe_dsp_reed_*): encode_stream turns payload_bytes = depth * (n - n_par)
+    bytes per frame into frame_bytes = depth * n channel bytes (in front of a Mod), process_stream turns channel bytes -- what
+    a Vit wrote -- back into payloads, correcting up to t = n_par // 2 wrong bytes in each of a frame's `depth` codewords, with
+    a record (bytes corrected, mask of uncorrectable codewords) and a status per frame.  The device's bytes are reed_plan's."""
+    _prefix = "reed"
+
+    def __init__(self, prim, fcr, step, n, n_par, depth, whiten=None, device=0):
+        head, _alive = _reed_shape(prim, fcr, step, n, n_par, depth, whiten)
+        self.n, self.n_par, self.depth, self.t = int(n), int(n_par), int(depth), int(n_par) // 2
+        self._create(*head, device)
+        self.payload_bytes, self.frame_bytes = self.depth * (self.n - self.n_par), self.depth * self.n
+
+    def encode_stream(self, d_payload, n_frames, d_frame, in_stride=None, out_stride=None, stream=None):
+        """d_*: DeviceArray or raw device pointers.  Frame b reads payload_bytes bytes at d_payload + b*in_stride (default
+        payload_bytes) and writes frame_bytes bytes at d_frame + b*out_stride (default frame_bytes).  Returns n_frames."""
+        k = C.c_size_t(0)
+        check(self._fn("encode_stream")(self._h, self._ptr(d_payload), self.payload_bytes if in_stride is None else int(in_stride), int(n_frames),
+                                        self._ptr(d_frame), self.frame_bytes if out_stride is None else int(out_stride), C.byref(k), stream))
+        return k.value
+
+    def process_stream(self, d_frame, n_frames, d_out, d_rec=None, d_status=None, d_status_in=None, in_stride=None, out_stride=None, stream=None):
+        """d_*: DeviceArray or raw device pointers.  Frame b reads frame_bytes bytes at d_frame + b*in_stride (default
+        frame_bytes) and, with d_status_in, the int32 at d_status_in + b; it writes payload_bytes bytes at d_out + b*out_stride
+        (default payload_bytes), two words at d_rec + 2b and an int32 at d_status + b.  Returns n_frames."""
+        k = C.c_size_t(0)
+        check(self._fn("process_stream")(self._h, self._ptr(d_frame), self.frame_bytes if in_stride is None else int(in_stride),
+                                         self._ptr(d_status_in), int(n_frames), self._ptr(d_out),
+                                         self.payload_bytes if out_stride is None else int(out_stride), self._ptr(d_rec), self._ptr(d_status),
+                                         C.byref(k), stream))
+        return k.value
+
+    def reset(self):
+        raise AttributeError("Reed has no reset: it carries no state")
+
+    def encode(self, data):
+        """Host convenience, computed on the GPU: data is (n_frames, payload_bytes) uint8; returns (n_frames, frame_bytes)."""
+        d = np.asarray(data, dtype=np.uint8)
+        d = np.ascontiguousarray(d.reshape(1, -1) if d.ndim == 1 else d)
+        nf = d.shape[0]
+        held = [DeviceArray.from_bytes(d), DeviceArray(max(1, (nf * self.frame_bytes + 3) // 4))]
+        try:
+            if nf:
+                self.encode_stream(held[0], nf, held[1], in_stride=d.shape[1])
+            raw = held[1].to_numpy().view(np.uint8)[:nf * self.frame_bytes].reshape(nf, self.frame_bytes)
+        finally:
+            for x in held:
+                x.free()
+        return np.ascontiguousarray(raw)
+
+    def decode(self, frames, status_in=None):
+        """Host convenience, computed on the GPU: frames is (n_frames, frame_bytes) uint8; returns what reed_plan returns."""
+        d = np.asarray(frames, dtype=np.uint8)
+        d = np.ascontiguousarray(d.reshape(1, -1) if d.ndim == 1 else d)
+        nf, P = d.shape[0], self.payload_bytes
+        held = [DeviceArray.from_bytes(d), DeviceArray(max(1, (nf * P + 3) // 4)), DeviceArray(max(1, 2 * nf)), DeviceArray(max(1, nf))]
+        try:
+            d_si = None
+            if status_in is not None:
+                d_si = DeviceArray.from_numpy(np.ascontiguousarray(status_in, dtype=np.int32).reshape(nf).view(np.float32))
+                held.append(d_si)
+            if nf:
+                self.process_stream(held[0], nf, held[1], held[2], held[3], d_si, in_stride=d.shape[1])
+            by = held[1].to_numpy().view(np.uint8)[:nf * P].reshape(nf, P)
+            rec = held[2].to_numpy(2 * nf).view(np.uint32).reshape(nf, 2)
+            st = held[3].to_numpy(nf).view(np.int32)
+        finally:
+            for x in held:
+                x.free()
+        return np.ascontiguousarray(by), np.ascontiguousarray(rec), np.ascontiguousarray(st)
 
 
 def rs_plan(state, upsample, n_in, out_len, rate):

@@ -20,6 +20,7 @@ FMT_F32, FMT_U8, FMT_TX10 = 0, 1, 2
 VIT_IN_SOFT, VIT_IN_BPSK, VIT_IN_QPSK = 0, 1, 2      # sfe_dsp_vit_*: what d_in holds
 POLAR_FM, POLAR_PM, POLAR_AM = 0, 1, 2               # sfe_dsp_polar_*: the law fixed at create
 OCC_NONFINITE, OCC_TRUNCATED = 1, 2                  # sfe_dsp_occ_*: the bits of a row's status
+REED_OK, REED_UNCORRECTABLE, REED_UPSTREAM = 0, 1, 2 # sfe_dsp_reed_*: a frame's status
 
 
 class TimeState(C.Structure):
@@ -202,6 +203,11 @@ SIGNATURES = {
     "sfe_dsp_occ_create": (i32, [i32, i32, f32, f32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
     "sfe_dsp_occ_process_stream": (i32, [vp, vp, sz, sz, sz, vp, vp, vp, sz, C.POINTER(sz), vp]),
     "sfe_dsp_occ_destroy": (i32, [vp]),
+    "sfe_dsp_reed_plan": (i32, [i32, i32, i32, i32, i32, i32, vp, i32, vp, sz, vp, sz, vp, sz, vp, vp, C.POINTER(i32), C.POINTER(i32)]),
+    "sfe_dsp_reed_create": (i32, [i32, i32, i32, i32, i32, i32, vp, i32, C.POINTER(vp)]),
+    "sfe_dsp_reed_encode_stream": (i32, [vp, vp, sz, sz, vp, sz, C.POINTER(sz), vp]),
+    "sfe_dsp_reed_process_stream": (i32, [vp, vp, sz, vp, sz, vp, sz, vp, vp, C.POINTER(sz), vp]),
+    "sfe_dsp_reed_destroy": (i32, [vp]),
 }
 
 # the diagnostic library only (simplefe_amd/csrc/diag/sfe_dsp_diag.h; scripts/ load it by pointing LIB_PATH at it): bound when present

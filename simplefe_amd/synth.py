@@ -548,6 +548,184 @@ def occ_reference(rows, rank, factor, min_level=0.0, gap=0, min_width=1, max_emi
     return info, rec, mask
 
 
+# ---- the Reed-Solomon outer code (sfe_dsp_reed_*): an independent restatement.  The field multiply is shift-and-xor on numpy
+# arrays (no table, nothing shared with the library); encoding is a polynomial remainder; decoding is
+# Peterson-Gorenstein-Zierler -- linear algebra on the syndromes, no Berlekamp-Massey -- and every proposed correction is kept
+# only if the corrected word's syndromes are all zero, so what it returns is a codeword within distance t or nothing.
+def reed_gf_mul(a, b, prim):
+    """a * b in GF(2^8) modulo the 9-bit polynomial prim, elementwise with broadcasting."""
+    a, b = np.broadcast_arrays(np.asarray(a, np.uint32), np.asarray(b, np.uint32))
+    a, r = a.copy(), np.zeros(a.shape, np.uint32)
+    for i in range(8):
+        r ^= np.where((b >> i) & 1, a, 0).astype(np.uint32)
+        a = a << 1
+        a ^= np.where(a & 0x100, np.uint32(prim), 0).astype(np.uint32)
+    return r
+
+
+def reed_gf_pow(a, e, prim):
+    """a ** e elementwise, e a non-negative integer."""
+    a = np.asarray(a, np.uint32)
+    r = np.ones(a.shape, np.uint32)
+    while e:
+        if e & 1:
+            r = reed_gf_mul(r, a, prim)
+        a, e = reed_gf_mul(a, a, prim), e >> 1
+    return r
+
+
+_reed_tables = {}
+
+
+def reed_tables(prim, fcr, step, n, n_par):
+    """(the n_par roots alpha^(step (fcr + i)), the locators X_j = alpha^(step (n - 1 - j)) of the byte positions j < n,
+    g(x) as coefficients from x^n_par down to x^0).  Kept per shape; the arrays are not to be written to."""
+    key = (prim, fcr, step, n, n_par)
+    if key not in _reed_tables:
+        _reed_tables[key] = _reed_make_tables(*key)
+    return _reed_tables[key]
+
+
+def _reed_make_tables(prim, fcr, step, n, n_par):
+    roots = np.array([reed_gf_pow(2, step * (fcr + i) % 255, prim) for i in range(n_par)], np.uint32)
+    X = np.array([reed_gf_pow(2, step * (n - 1 - j) % 255, prim) for j in range(n)], np.uint32)
+    g = np.array([1], np.uint32)
+    for r in roots:
+        g = np.concatenate([g, [0]]) ^ np.concatenate([[0], reed_gf_mul(g, r, prim)]).astype(np.uint32)
+    return roots, X, g
+
+
+def reed_syndromes(words, roots, prim):
+    """words (m, n) -> (m, n_par): word(root_i), byte j the coefficient of x^(n - 1 - j)."""
+    words = np.asarray(words, np.uint32)
+    S = np.zeros((words.shape[0], roots.size), np.uint32)
+    for j in range(words.shape[1]):
+        S = reed_gf_mul(S, roots[None, :], prim) ^ words[:, j:j + 1]
+    return S
+
+
+def reed_encode_words(msgs, g, prim):
+    """msgs (m, k) -> codewords (m, n): the message, then x^n_par m(x) mod g(x) by long division."""
+    msgs = np.asarray(msgs, np.uint32)
+    k, n_par = msgs.shape[1], g.size - 1
+    work = np.concatenate([msgs, np.zeros((msgs.shape[0], n_par), np.uint32)], axis=1)
+    for j in range(k):
+        work[:, j:j + n_par + 1] ^= reed_gf_mul(work[:, j:j + 1].copy(), g[None, :], prim)
+    return np.concatenate([msgs, work[:, k:]], axis=1)
+
+
+def _reed_eliminate(A, b, prim):
+    """Gaussian elimination of A x = b over the field: (rank of A, x where A is square and nonsingular, else None)."""
+    A = np.concatenate([np.asarray(A, np.uint32), np.asarray(b, np.uint32).reshape(-1, 1)], axis=1)
+    rows, cols = A.shape[0], A.shape[1] - 1
+    rank = 0
+    for c in range(cols):
+        nz = np.flatnonzero(A[rank:, c]) if rank < rows else np.array([], int)
+        if nz.size == 0:
+            continue
+        p = rank + int(nz[0])
+        A[[rank, p]] = A[[p, rank]]
+        A[rank] = reed_gf_mul(A[rank], reed_gf_pow(A[rank, c], 254, prim), prim)
+        f = A[:, c].copy()
+        f[rank] = 0
+        A ^= reed_gf_mul(f[:, None], A[rank][None, :], prim)
+        rank += 1
+    return rank, (A[:, cols].copy() if rank == rows == cols else None)
+
+
+def _reed_pgz(r, S, X, fcr, t, prim):
+    """One received word r (n,) with syndromes S, not all zero: the error values per position (n,) of a proposal with at
+    most t errors, or None."""
+    S = S.astype(np.uint32)
+    hankel = lambda e: np.array([[S[i + j] for j in range(e)] for i in range(e)], np.uint32)
+    e, lam = _reed_eliminate(hankel(t), np.zeros(t, np.uint32), prim)[0], None
+    while e >= 1:                                       # the largest e whose syndrome matrix is nonsingular
+        _, sol = _reed_eliminate(hankel(e), S[e:2 * e], prim)       # sum_j S[i + j] Lambda_(e - j) = S[i + e]
+        if sol is not None:
+            lam = np.concatenate([[1], sol[::-1]]).astype(np.uint32)     # Lambda_0 .. Lambda_e
+            break
+        e -= 1
+    if lam is None:
+        return None
+    z = reed_gf_pow(X, 254, prim)
+    val = np.zeros(X.size, np.uint32)
+    for c in lam[::-1]:
+        val = reed_gf_mul(val, z, prim) ^ c
+    at = np.flatnonzero(val == 0)                       # roots among the n positions of the code only
+    if at.size != e:
+        return None
+    V = np.array([reed_gf_pow(X[at], i, prim) for i in range(e)], np.uint32)
+    _, Y = _reed_eliminate(V, S[:e], prim)              # sum_k Y_k X_k^i = S_i, Y = value * X^fcr
+    if Y is None:
+        return None
+    err = np.zeros(X.size, np.uint32)
+    err[at] = reed_gf_mul(Y, reed_gf_pow(reed_gf_pow(X[at], fcr, prim), 254, prim), prim)
+    return err
+
+
+def reed_decode_words(words, prim, fcr, step, n_par, brute=False):
+    """words (m, n) de-whitened received words -> (words corrected where a codeword lies within t, counts (m,): the distance,
+    or -1 for an uncorrectable word, which stays as received).  brute (t = 1 only): instead of solving anything, try the word
+    itself and every word at distance 1."""
+    words = np.ascontiguousarray(words, np.uint8)
+    m, n = words.shape
+    t = n_par // 2
+    roots, X, _ = reed_tables(prim, fcr, step, n, n_par)
+    S = reed_syndromes(words, roots, prim)
+    out, counts = words.copy(), np.full(m, -1, np.int64)
+    counts[~S.any(axis=1)] = 0
+    dirty = np.flatnonzero(S.any(axis=1))
+    if brute:
+        assert t == 1
+        for w in dirty:
+            cand = np.repeat(words[w:w + 1], n * 255, axis=0)
+            cand[np.arange(n * 255), np.repeat(np.arange(n), 255)] ^= np.tile(np.arange(1, 256, dtype=np.uint8), n)
+            ok = np.flatnonzero(~reed_syndromes(cand, roots, prim).any(axis=1))
+            assert ok.size <= 1                         # minimum distance n_par + 1 >= 3
+            if ok.size:
+                out[w], counts[w] = cand[ok[0]], 1
+        return out, counts
+    tried = []
+    for w in dirty:
+        err = _reed_pgz(words[w], S[w], X, fcr, t, prim)
+        if err is not None and 1 <= np.count_nonzero(err) <= t:
+            tried.append((w, err.astype(np.uint8)))
+    if tried:
+        idx = np.array([w for w, _ in tried])
+        cand = words[idx] ^ np.stack([e for _, e in tried])
+        good = ~reed_syndromes(cand, roots, prim).any(axis=1)
+        for (w, e), c, g in zip(tried, cand, good):
+            if g:
+                out[w], counts[w] = c, np.count_nonzero(e)
+    return out, counts
+
+
+def reed_reference(prim, fcr, step, n, n_par, depth, data, whiten=None, encode=False, status_in=None, brute=False):
+    """The law of sfe_dsp_reed_* (include/sfe_dsp.h) restated in numpy, what api.reed_plan returns: with encode, payloads
+    (n_frames, depth (n - n_par)) -> frames (n_frames, depth n); without, channel bytes (n_frames, depth n) -> (bytes, record
+    (n_frames, 2) uint32, status (n_frames,) int32)."""
+    d = np.asarray(data, np.uint8)
+    d = d.reshape(1, -1) if d.ndim == 1 else d
+    nf, k, I = d.shape[0], n - n_par, depth
+    w = np.zeros(I * n, np.uint8) if whiten is None else np.asarray(whiten, np.uint8).ravel()
+    if encode:
+        _, _, g = reed_tables(prim, fcr, step, n, n_par)
+        msgs = d[:, :I * k].reshape(nf, k, I).transpose(0, 2, 1).reshape(nf * I, k)      # codeword i of a frame: bytes j I + i
+        code = reed_encode_words(msgs, g, prim).astype(np.uint8)
+        return np.ascontiguousarray(code.reshape(nf, I, n).transpose(0, 2, 1).reshape(nf, I * n)) ^ w[None, :]
+    up = np.zeros(nf, bool) if status_in is None else np.asarray(status_in).ravel() != 0
+    words = (d[:, :I * n] ^ w[None, :]).reshape(nf, n, I).transpose(0, 2, 1).reshape(nf * I, n)
+    fixed, counts = reed_decode_words(words, prim, fcr, step, n_par, brute=brute)
+    out = np.ascontiguousarray(fixed.reshape(nf, I, n)[:, :, :k].transpose(0, 2, 1).reshape(nf, I * k))
+    counts = counts.reshape(nf, I)
+    rec = np.zeros((nf, 2), np.uint32)
+    rec[:, 0] = np.where(counts > 0, counts, 0).sum(axis=1)
+    rec[:, 1] = ((counts < 0) << np.arange(I)[None, :]).sum(axis=1)
+    st = (rec[:, 1] != 0).astype(np.int32)
+    out[up], rec[up], st[up] = 0, (0, (1 << I) - 1), 2
+    return out, rec, st
+
+
 # ---- the beamformer / stream-mixing bank (sfe_dsp_beam_*): weights are (M, B, S) complex64 ((B, S): one band)
 def _beam_weights(W, V):
     W = np.asarray(W, dtype=np.complex64)
