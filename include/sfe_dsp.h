@@ -1622,6 +1622,99 @@ int sfe_dsp_reed_process_stream(sfe_reed_t h, const void *d_frame, size_t in_str
                                 sfe_stream_t stream);
 int sfe_dsp_reed_destroy(sfe_reed_t h);
 
+/* ------------------------------------------------- quasi-cyclic LDPC code, decoder and encoder
+ * The inner code of a modern link beside the convolutional one: behind sfe_dsp_burst_* a layered
+ * min-sum decoder, in front of sfe_dsp_mod_* (its uncoded mode, n_gen = 0) the encoder, on the
+ * device.  Its parallelism is across the codeword, and its syndrome is its own frame check.
+ * Codewords are independent; nothing is carried.  The decoder is integer arithmetic on a quantised
+ * input.  The law's arithmetic is csrc/ldpc_law.h, one header the kernels and the host plan compile.
+ * Code: a base matrix shift[mb][nb] of int16 (row-major) and a lifting size Z.  shift = -1 is an
+ * empty cell, 0 <= shift < Z a circulant: row r Z + i of H has a one in column
+ * c Z + (i + shift[r][c]) mod Z for every non-empty cell (r, c).  n = nb Z, m = mb Z, k = n - m.
+ * Limits: Z in [1, 512] (Z = 1 makes any small H expressible); 1 <= mb <= 64; mb < nb <= 256;
+ * n <= 8192; every block row has 2 to 32 cells; every block column at least one; cells Z <= 65 536.
+ * Out of scope: more than one circulant per cell, punctured or shortened columns, erasure input.
+ * Bits: a payload is k bits packed MSB-first into ceil(k / 8) bytes (the layout sfe_dsp_vit_*
+ * writes), a codeword n bits packed MSB-first into ceil(n / 8) bytes (the layout sfe_dsp_mod_*
+ * reads); pad bits are ignored on input and 0 on output.
+ * Encode: the codeword c has c[0 .. k) = payload and H c = 0 over GF(2).  It exists and is unique
+ * iff the last m columns of H are invertible: plan reports that as `encodable`; create accepts
+ * either kind of matrix; encode_stream on a handle that is not encodable is SFE_ESTATE and launches
+ * nothing.  The law names no algorithm for the parity bits.
+ * Soft input: r > 0 favours bit 0.  The three modes SFE_VIT_IN_SOFT / _BPSK / _QPSK with `skip`,
+ * exactly as sfe_dsp_vit_* defines them, on n soft values; in_stride counts elements of the mode's
+ * type.  Behind a burst demodulator: its d_out, its out_stride, skip = Lp and its d_status as
+ * d_status_in are the whole glue.
+ * Quantisation: L_v = clamp(rintf(r_v * scale), -127, 127); the product is one float32 IEEE
+ * multiply, rintf rounds ties to even, scale is finite and > 0 and fixed at create; a product that
+ * overflows to +-inf clamps; a non-finite r_v is status 1.
+ * Decoder: layered normalised and offset min-sum, all in integers.  State: APP[v], starting as L_v,
+ * and one message R per edge, starting at 0.  Parameters fixed at create: a in [1, 16],
+ * beta in [0, 127], max_iter in [1, 64].  One iteration visits the block rows l = 0 .. mb-1 in
+ * order, and within a block row every i in [0, Z) (the Z rows of a layer touch disjoint variables:
+ * their order cannot show).  For each row, with its cells j = 0 .. d-1 in increasing block column
+ * and v_j the variable of cell j:
+ *   Q_j = APP[v_j] - R_j;  neg_j = (Q_j < 0), zero counts as positive;  m1 = min_j |Q_j|;
+ *   j* the lowest j attaining m1;  m2 = min over j != j* of |Q_j|;  M_j = (j == j*) ? m2 : m1;
+ *   M'_j = min(max(((M_j a) >> 4) - beta, 0), 127);  S = XOR of all neg_j;
+ *   R'_j = (S ^ neg_j) ? -M'_j : M'_j;  APP[v_j] = Q_j + R'_j;  R_j = R'_j.
+ * Nothing else saturates: APP[v] always equals L_v plus the current messages of v's checks, so
+ * |APP| <= 127 (1 + mb) <= 8255, which fits int16.  Decision: x_v = (APP[v] < 0).  The syndrome of x
+ * is checked before the first iteration and after every complete one; decoding stops at the first
+ * zero syndrome, or after max_iter iterations -- so `iterations` can be 0.
+ * Output per codeword b: ceil(k / 8) bytes of x[0 .. k) at d_bits + b*out_stride; three uint32 at
+ * d_rec + 3b -- iterations run, unsatisfied checks at the end (0 iff converged), the number of v
+ * with L_v != 0 whose decision differs from the sign of L_v; an int32 status at d_status + b:
+ *   0  converged
+ *   1  a non-finite soft value: the bytes are 0, the record (0, 0, 0)
+ *   2  d_status_in is given and its word for b is not 0: nothing is read, outputs as for status 1
+ *   3  not converged after max_iter: the bytes are still the decisions
+ * Promised: the same call gives the same bytes on every run; a codeword's output depends on its n
+ * soft values and the handle only -- never on b, the count, addresses, strides or the input mode;
+ * the device's bytes, record and status EQUAL sfe_dsp_ldpc_plan's for every input whose soft values
+ * are finite, and a non-finite value is status 1 on both sides; nothing outside the slots named is
+ * written, to the byte; a launch runs at most max_iter iterations, whatever the data.
+ * A bad argument is SFE_EINVAL on any machine, with a message that starts with "ldpc: ". */
+typedef void *sfe_ldpc_t; /* opaque: one code and its decoder's parameters; it owns its tables (cells, the parity part's inverse) on the device and nothing in it changes after create */
+/* Host-only: the LDS a decoding workgroup uses and the codewords it holds (1, 2 or 4). */
+int sfe_dsp_ldpc_footprint(int mb, int nb, int Z, const int16_t *shift, size_t *lds_bytes,
+                           int *words_per_group);
+/* Host-only (no GPU): validates what create validates and reports n, k and encodable (each pointer
+ * may be NULL).  With in != NULL -- host memory laid out as d_in of process_stream (encode = 0) or
+ * as d_payload of encode_stream (encode = 1) -- it runs n_words codewords by the law above, exactly
+ * as stated, into out (word b at out + b*out_stride), record [n_words][3] and status [n_words];
+ * each of the three may be NULL.  status_in [n_words] or NULL; with encode = 1 status_in, record
+ * and status are ignored, and a code that is not encodable is SFE_ESTATE.  The reference of the
+ * device's bytes.  Short strides are SFE_ERANGE. */
+int sfe_dsp_ldpc_plan(int mb, int nb, int Z, const int16_t *shift, float scale, int a, int beta,
+                      int max_iter, int in_mode, int skip, int encode, const void *in,
+                      size_t in_stride, const int *status_in, size_t n_words, uint8_t *out,
+                      size_t out_stride, uint32_t *record, int *status, int *n, int *k,
+                      int *encodable);
+/* Arguments are checked before the device is touched: SFE_EINVAL for a bad one on any machine,
+ * SFE_ENODEV without a GPU.  shift is copied.  The parity part is inverted here, by elimination. */
+int sfe_dsp_ldpc_create(int mb, int nb, int Z, const int16_t *shift, float scale, int a, int beta,
+                        int max_iter, int in_mode, int skip, int device, sfe_ldpc_t *out);
+/* n_words codewords each way.  d_status_in, d_rec and d_status may each be NULL.  *n_out = n_words;
+ * n_words = 0 is a no-op.  A stride below what a codeword reads (n floats; skip + n or
+ * skip + ceil(n / 2) symbols; ceil(k / 8) payload bytes) or writes (ceil(k / 8), ceil(n / 8)
+ * bytes) is SFE_ERANGE; a null d_in, d_payload, d_bits or d_code, misaligned buffers (soft values,
+ * records and statuses 4 bytes, symbols 8; payloads and codewords need none), n_words >= 2^31, a
+ * stride that takes a buffer's byte range to 2^62, and any output byte range that overlaps an
+ * input's or another output's are SFE_EINVAL, each with a message that starts with
+ * "ldpc_process_stream: " or "ldpc_encode_stream: "; nothing is launched on a refusal.
+ * Asynchronous on `stream`; one kernel launch and nothing else: allocates nothing, does not
+ * synchronise the host, carries no state (there is no reset, and a handle has no setter), so a call
+ * on a stream under graph capture IS supported. */
+int sfe_dsp_ldpc_process_stream(sfe_ldpc_t h, const void *d_in, size_t in_stride,
+                                const void *d_status_in, size_t n_words, void *d_bits,
+                                size_t out_stride, void *d_rec, void *d_status, size_t *n_out,
+                                sfe_stream_t stream);
+int sfe_dsp_ldpc_encode_stream(sfe_ldpc_t h, const void *d_payload, size_t in_stride,
+                               size_t n_words, void *d_code, size_t out_stride, size_t *n_out,
+                               sfe_stream_t stream);
+int sfe_dsp_ldpc_destroy(sfe_ldpc_t h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1645,6 +1645,136 @@ class Reed(_Block):
         return np.ascontiguousarray(by), np.ascontiguousarray(rec), np.ascontiguousarray(st)
 
 
+def _ldpc_shape(shift, Z):
+    """(mb, nb, Z, the base matrix's pointer) as sfe_dsp_ldpc_* take them, and what keeps the matrix alive."""
+    s = np.ascontiguousarray(np.asarray(shift, dtype=np.int16))
+    if s.ndim != 2:
+        raise ValueError("ldpc: the base matrix must be (mb, nb), not %s" % (s.shape,))
+    return (s.shape[0], s.shape[1], int(Z), s.ctypes.data), s
+
+
+def _ldpc_rows(x, in_mode):
+    x = np.asarray(x)
+    return np.ascontiguousarray(x.reshape(1, -1) if x.ndim == 1 else x, dtype=np.float32 if in_mode == _l.VIT_IN_SOFT else np.complex64)
+
+
+def ldpc_footprint(shift, Z):
+    """sfe_dsp_ldpc_footprint (host only): (LDS bytes of a decoding workgroup, the codewords it holds)."""
+    head, _alive = _ldpc_shape(shift, Z)
+    by, w = C.c_size_t(0), C.c_int(0)
+    check(_l.load().sfe_dsp_ldpc_footprint(*head, C.byref(by), C.byref(w)))
+    return by.value, w.value
+
+
+def ldpc_plan(shift, Z, scale=8.0, a=12, beta=0, max_iter=32, in_mode=_l.VIT_IN_SOFT, skip=0, x=None, status_in=None, data=None):
+    """sfe_dsp_ldpc_plan (host only, no GPU): validates and, without x and data, returns (n, k, encodable).  With x --
+    (n_words, row) float32 soft values with VIT_IN_SOFT, complex symbols with VIT_IN_BPSK / VIT_IN_QPSK -- it decodes every
+    row by the law: returns (bytes (n_words, ceil(k / 8)) uint8, record (n_words, 3) uint32 -- iterations, unsatisfied
+    checks, decisions that left the input's sign -- and status (n_words,) int32).  With data -- (n_words, >= ceil(k / 8))
+    uint8 payload bytes -- it encodes: returns the codewords (n_words, ceil(n / 8)) uint8.  These are the device's bytes.
+    status_in: int32 per codeword or None.  Raises SfeError on arguments the block refuses."""
+    head, _alive = _ldpc_shape(shift, Z)
+    L, n, k, enc = _l.load(), C.c_int(0), C.c_int(0), C.c_int(0)
+    head = (*head, float(scale), int(a), int(beta), int(max_iter), int(in_mode), int(skip))
+    check(L.sfe_dsp_ldpc_plan(*head, 0, None, 0, None, 0, None, 0, None, None, C.byref(n), C.byref(k), C.byref(enc)))
+    if x is None and data is None:
+        return n.value, k.value, bool(enc.value)
+    kb, nbytes = (k.value + 7) // 8, (n.value + 7) // 8
+    if data is not None:
+        d = np.asarray(data, dtype=np.uint8)
+        d = np.ascontiguousarray(d.reshape(1, -1) if d.ndim == 1 else d)
+        out = np.empty((d.shape[0], nbytes), np.uint8)
+        check(L.sfe_dsp_ldpc_plan(*head, 1, d.ctypes.data if d.size else None, d.shape[1], None, d.shape[0], out.ctypes.data, nbytes, None, None,
+                                  None, None, None))
+        return out
+    x = _ldpc_rows(x, in_mode)
+    nw = x.shape[0]
+    if status_in is not None:
+        status_in = np.ascontiguousarray(status_in, dtype=np.int32).ravel()
+        if status_in.size != nw:
+            raise ValueError("ldpc_plan: status_in has %d entries for %d codewords" % (status_in.size, nw))
+    by, rec, st = np.empty((nw, kb), np.uint8), np.empty((nw, 3), np.uint32), np.empty(nw, np.int32)
+    check(L.sfe_dsp_ldpc_plan(*head, 0, x.ctypes.data if x.size else None, x.shape[1], None if status_in is None else status_in.ctypes.data, nw,
+                              by.ctypes.data, kb, rec.ctypes.data, st.ctypes.data, None, None, None))
+    return by, rec, st
+
+
+class Ldpc(_Block):
+    """Quasi-cyclic LDPC code (sfe_dsp_ldpc_*): encode_stream turns ceil(k / 8) payload bytes per codeword into ceil(n / 8)
+    codeword bytes (in front of an uncoded Mod), process_stream turns n soft values per codeword -- float32, or the components
+    of the symbols a Burst wrote -- back into payload bytes by layered min-sum decoding in integers, with a record
+    (iterations, unsatisfied checks, decisions that left the input's sign) and a status per codeword.  The device's bytes are
+    ldpc_plan's."""
+    _prefix = "ldpc"
+
+    def __init__(self, shift, Z, scale=8.0, a=12, beta=0, max_iter=32, in_mode=_l.VIT_IN_SOFT, skip=0, device=0):
+        head, _alive = _ldpc_shape(shift, Z)
+        self.in_mode, self.skip = int(in_mode), int(skip)
+        self._create(*head, float(scale), int(a), int(beta), int(max_iter), self.in_mode, self.skip, device)
+        self.n, self.k, self.encodable = ldpc_plan(shift, Z, scale, a, beta, max_iter, in_mode, skip)
+        self.k_bytes, self.n_bytes = (self.k + 7) // 8, (self.n + 7) // 8
+        # elements of the mode's type a codeword's row holds at least
+        self.row = self.n if self.in_mode == _l.VIT_IN_SOFT else self.skip + (self.n if self.in_mode == _l.VIT_IN_BPSK else (self.n + 1) // 2)
+
+    def encode_stream(self, d_payload, n_words, d_code, in_stride=None, out_stride=None, stream=None):
+        """d_*: DeviceArray or raw device pointers.  Codeword b reads k_bytes bytes at d_payload + b*in_stride (default k_bytes)
+        and writes n_bytes bytes at d_code + b*out_stride (default n_bytes).  Returns n_words."""
+        k = C.c_size_t(0)
+        check(self._fn("encode_stream")(self._h, self._ptr(d_payload), self.k_bytes if in_stride is None else int(in_stride), int(n_words),
+                                        self._ptr(d_code), self.n_bytes if out_stride is None else int(out_stride), C.byref(k), stream))
+        return k.value
+
+    def process_stream(self, d_in, n_words, d_bits, d_rec=None, d_status=None, d_status_in=None, in_stride=None, out_stride=None, stream=None):
+        """d_*: DeviceArray or raw device pointers.  Codeword b reads its row at d_in + b*in_stride (elements of the input
+        mode's type; default: the row's own length) and, with d_status_in, the int32 at d_status_in + b; it writes k_bytes
+        bytes at d_bits + b*out_stride (bytes; default k_bytes), three words at d_rec + 3b and an int32 at d_status + b.
+        Returns n_words."""
+        k = C.c_size_t(0)
+        check(self._fn("process_stream")(self._h, self._ptr(d_in), self.row if in_stride is None else int(in_stride), self._ptr(d_status_in),
+                                         int(n_words), self._ptr(d_bits), self.k_bytes if out_stride is None else int(out_stride),
+                                         self._ptr(d_rec), self._ptr(d_status), C.byref(k), stream))
+        return k.value
+
+    def reset(self):
+        raise AttributeError("Ldpc has no reset: it carries no state")
+
+    def encode(self, data):
+        """Host convenience, computed on the GPU: data is (n_words, k_bytes) uint8; returns (n_words, n_bytes)."""
+        d = np.asarray(data, dtype=np.uint8)
+        d = np.ascontiguousarray(d.reshape(1, -1) if d.ndim == 1 else d)
+        nw = d.shape[0]
+        held = [DeviceArray.from_bytes(d), DeviceArray(max(1, (nw * self.n_bytes + 3) // 4))]
+        try:
+            if nw:
+                self.encode_stream(held[0], nw, held[1], in_stride=d.shape[1])
+            raw = held[1].to_numpy().view(np.uint8)[:nw * self.n_bytes].reshape(nw, self.n_bytes)
+        finally:
+            for x in held:
+                x.free()
+        return np.ascontiguousarray(raw)
+
+    def decode(self, x, status_in=None):
+        """Host convenience, computed on the GPU: x is (n_words, row) -- float32 soft values, or complex symbols with
+        VIT_IN_BPSK / VIT_IN_QPSK; returns what ldpc_plan returns."""
+        x = _ldpc_rows(x, self.in_mode)
+        nw, kb = x.shape[0], self.k_bytes
+        held = [DeviceArray.from_numpy(x.view(np.float32)), DeviceArray(max(1, (nw * kb + 3) // 4)), DeviceArray(max(1, 3 * nw)), DeviceArray(max(1, nw))]
+        try:
+            d_si = None
+            if status_in is not None:
+                d_si = DeviceArray.from_numpy(np.ascontiguousarray(status_in, dtype=np.int32).reshape(nw).view(np.float32))
+                held.append(d_si)
+            if nw:
+                self.process_stream(held[0], nw, held[1], held[2], held[3], d_si, in_stride=x.shape[1])
+            by = held[1].to_numpy().view(np.uint8)[:nw * kb].reshape(nw, kb)
+            rec = held[2].to_numpy(3 * nw).view(np.uint32).reshape(nw, 3)
+            st = held[3].to_numpy(nw).view(np.int32)
+        finally:
+            for d in held:
+                d.free()
+        return np.ascontiguousarray(by), np.ascontiguousarray(rec), np.ascontiguousarray(st)
+
+
 def rs_plan(state, upsample, n_in, out_len, rate):
     """Host-only replay of one process() call's time law (sfe_dsp_rs_plan).
     state: lib.TimeState (updated in place).  Returns (rel_pos int32[], mu float32[])."""

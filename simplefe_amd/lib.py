@@ -21,6 +21,7 @@ VIT_IN_SOFT, VIT_IN_BPSK, VIT_IN_QPSK = 0, 1, 2      # sfe_dsp_vit_*: what d_in 
 POLAR_FM, POLAR_PM, POLAR_AM = 0, 1, 2               # sfe_dsp_polar_*: the law fixed at create
 OCC_NONFINITE, OCC_TRUNCATED = 1, 2                  # sfe_dsp_occ_*: the bits of a row's status
 REED_OK, REED_UNCORRECTABLE, REED_UPSTREAM = 0, 1, 2 # sfe_dsp_reed_*: a frame's status
+LDPC_OK, LDPC_NOT_FINITE, LDPC_UPSTREAM, LDPC_NOT_CONVERGED = 0, 1, 2, 3     # sfe_dsp_ldpc_*: a codeword's status
 
 
 class TimeState(C.Structure):
@@ -208,6 +209,13 @@ SIGNATURES = {
     "sfe_dsp_reed_encode_stream": (i32, [vp, vp, sz, sz, vp, sz, C.POINTER(sz), vp]),
     "sfe_dsp_reed_process_stream": (i32, [vp, vp, sz, vp, sz, vp, sz, vp, vp, C.POINTER(sz), vp]),
     "sfe_dsp_reed_destroy": (i32, [vp]),
+    "sfe_dsp_ldpc_footprint": (i32, [i32, i32, i32, vp, C.POINTER(sz), C.POINTER(i32)]),
+    "sfe_dsp_ldpc_plan": (i32, [i32, i32, i32, vp, f32, i32, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp, sz, vp, vp, C.POINTER(i32), C.POINTER(i32),
+                                C.POINTER(i32)]),
+    "sfe_dsp_ldpc_create": (i32, [i32, i32, i32, vp, f32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
+    "sfe_dsp_ldpc_process_stream": (i32, [vp, vp, sz, vp, sz, vp, sz, vp, vp, C.POINTER(sz), vp]),
+    "sfe_dsp_ldpc_encode_stream": (i32, [vp, vp, sz, sz, vp, sz, C.POINTER(sz), vp]),
+    "sfe_dsp_ldpc_destroy": (i32, [vp]),
 }
 
 # the diagnostic library only (simplefe_amd/csrc/diag/sfe_dsp_diag.h; scripts/ load it by pointing LIB_PATH at it): bound when present

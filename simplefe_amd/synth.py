@@ -1142,3 +1142,162 @@ def f32_to_u8(x):
     """float32 values requantised to the receive wire format: the byte nearest to 127 x + 128, clipped to [0, 255]."""
     x = np.ascontiguousarray(x).view(np.float32).ravel().astype(np.float64)
     return np.clip(np.rint(x * 127.0 + 128.0), 0, 255).astype(np.uint8)
+
+
+# ---- the quasi-cyclic LDPC code (sfe_dsp_ldpc_*): the law of include/sfe_dsp.h restated on the expanded matrix.  Nothing
+# below knows of circulants or layers: H is a list of rows, each the ascending column indices of its ones.
+def ldpc_expand(shift, Z):
+    """The rows of H, row r Z + i at that index: the ascending columns c Z + (i + shift[r][c]) mod Z of its ones."""
+    s = np.asarray(shift, dtype=np.int64)
+    Z = int(Z)
+    rows = []
+    for r in range(s.shape[0]):
+        cs = np.flatnonzero(s[r] >= 0)
+        for i in range(Z):
+            rows.append(np.sort(cs * Z + (i + s[r, cs]) % Z))
+    return rows
+
+
+def ldpc_dense(rows, n):
+    """H as (m, n) uint8."""
+    H = np.zeros((len(rows), int(n)), np.uint8)
+    for r, cols in enumerate(rows):
+        H[r, cols] = 1
+    return H
+
+
+def gf2_solve(B, S):
+    """X with B X = S over GF(2) -- B (m, m), S (m, w), entries 0 / 1 -- or None where B is singular: Gauss-Jordan on
+    packed rows."""
+    B, S = np.asarray(B, np.uint8), np.asarray(S, np.uint8)
+    m = B.shape[0]
+    M = np.packbits(np.concatenate([B, S], axis=1), axis=1)
+    for p in range(m):
+        byte, mask = p >> 3, 0x80 >> (p & 7)
+        below = np.flatnonzero(M[p:, byte] & mask)
+        if below.size == 0:
+            return None
+        if below[0]:
+            M[[p, p + below[0]]] = M[[p + below[0], p]]
+        col = M[:, byte] & mask
+        col[p] = 0
+        idx = np.flatnonzero(col)
+        if idx.size:
+            M[idx] ^= M[p]
+    return np.unpackbits(M, axis=1)[:, m:m + S.shape[1]]
+
+
+def ldpc_encodable(shift, Z):
+    """Whether the last m columns of H are invertible over GF(2)."""
+    s = np.asarray(shift)
+    rows = ldpc_expand(s, Z)
+    n = s.shape[1] * int(Z)
+    H = ldpc_dense(rows, n)
+    return gf2_solve(H[:, n - len(rows):], np.zeros((len(rows), 0), np.uint8)) is not None
+
+
+def ldpc_encode_reference(shift, Z, data):
+    """data (n_words, >= ceil(k / 8)) uint8, MSB-first: the codewords (n_words, ceil(n / 8)) uint8 with c[0 .. k) the payload
+    and H c = 0, by solving B p = A u for all the words at once.  ValueError where the code is not encodable."""
+    s = np.asarray(shift)
+    rows = ldpc_expand(s, Z)
+    m, n = len(rows), s.shape[1] * int(Z)
+    k = n - m
+    d = np.asarray(data, np.uint8)
+    d = d.reshape(1, -1) if d.ndim == 1 else d
+    u = np.unpackbits(d, axis=1)[:, :k]
+    syn = np.stack([u[:, cols[cols < k]].sum(axis=1) & 1 for cols in rows]).astype(np.uint8)       # (m, n_words)
+    B = ldpc_dense(rows, n)[:, k:]
+    p = gf2_solve(B, syn)
+    if p is None:
+        raise ValueError("ldpc: the parity part of H is singular")
+    return np.packbits(np.concatenate([u, p.T], axis=1), axis=1)
+
+
+def ldpc_quantise(r, scale):
+    """clamp(rint(r * scale), -127, 127) with the product in float32 and ties to even; r finite."""
+    with np.errstate(over="ignore"):
+        p = np.asarray(r, np.float32) * np.float32(scale)
+    return np.clip(np.rint(p), -127, 127).astype(np.int32)
+
+
+def _ldpc_runs(rows, one_at_a_time):
+    """The rows in their order, cut into runs: consecutive rows of one degree that share no variable commute, so a run is
+    updated in one step -- found from the rows themselves.  one_at_a_time: every run is a single row."""
+    runs, cur, seen = [], [], set()
+    for cols in rows:
+        c = set(cols.tolist())
+        if cur and not one_at_a_time and len(cols) == len(cur[0]) and not (c & seen):
+            cur.append(cols)
+            seen |= c
+        else:
+            if cur:
+                runs.append(np.stack(cur))
+            cur, seen = [cols], c
+    runs.append(np.stack(cur))
+    return runs
+
+
+def ldpc_reference(shift, Z, x, scale=8.0, a=12, beta=0, max_iter=32, status_in=None, one_at_a_time=False, with_peak=False):
+    """The decoder's law on x (n_words, n) float32 soft values, row after row of the expanded H in the order r Z + i:
+    returns (bytes (n_words, ceil(k / 8)) uint8, record (n_words, 3) uint32, status (n_words,) int32), and with with_peak
+    the largest |APP| met as a fourth item."""
+    s = np.asarray(shift)
+    rows = ldpc_expand(s, Z)
+    m, n = len(rows), s.shape[1] * int(Z)
+    k = n - m
+    x = np.asarray(x, np.float32)
+    x = x.reshape(1, -1) if x.ndim == 1 else x
+    W = x.shape[0]
+    status = np.zeros(W, np.int32)
+    status[~np.isfinite(x[:, :n]).all(axis=1)] = 1
+    if status_in is not None:
+        status[np.asarray(status_in).ravel() != 0] = 2
+    ok = status == 0
+    L = np.zeros((W, n), np.int32)
+    L[ok] = ldpc_quantise(x[ok, :n], scale)
+    runs = _ldpc_runs(rows, one_at_a_time)
+    app = L.copy()
+    msgs = [np.zeros((W,) + run.shape, np.int32) for run in runs]
+    iters, unsat = np.zeros(W, np.uint32), np.zeros(W, np.uint32)
+    peak = 0
+
+    def unsatisfied(A):
+        neg = A < 0
+        return sum((neg[:, run].sum(axis=2) & 1).sum(axis=1) for run in runs).astype(np.uint32)
+
+    act = np.flatnonzero(ok)
+    unsat[act] = unsatisfied(app[act])
+    act = act[unsat[act] != 0]
+    for it in range(1, int(max_iter) + 1):
+        if act.size == 0:
+            break
+        A = app[act]
+        for run, R in zip(runs, msgs):
+            d = run.shape[1]
+            Q = A[:, run] - R[act]
+            neg = Q < 0
+            mag = np.abs(Q)
+            js = mag.argmin(axis=2)                     # the lowest index among equals
+            first = np.arange(d)[None, None, :] == js[:, :, None]
+            m1 = mag.min(axis=2)
+            m2 = np.where(first, 1 << 20, mag).min(axis=2)
+            M = np.where(first, m2[:, :, None], m1[:, :, None])
+            Mp = np.clip(((M * int(a)) >> 4) - int(beta), 0, 127)
+            S = (neg.sum(axis=2) & 1).astype(bool)
+            Rn = np.where(S[:, :, None] ^ neg, -Mp, Mp)
+            A[:, run] = Q + Rn
+            R[act] = Rn
+        app[act] = A
+        peak = max(peak, int(np.abs(A).max()))
+        iters[act] = it
+        unsat[act] = unsatisfied(A)
+        act = act[unsat[act] != 0]
+    status[ok & (unsat != 0)] = 3
+    hard = (app < 0).astype(np.uint8)
+    by = np.packbits(hard[:, :k], axis=1)
+    flips = ((L != 0) & ((app < 0) != (L < 0))).sum(axis=1).astype(np.uint32)
+    rec = np.stack([iters, unsat, flips], axis=1).astype(np.uint32)
+    by[~ok], rec[~ok] = 0, 0
+    out = (np.ascontiguousarray(by), np.ascontiguousarray(rec), status)
+    return out + (peak,) if with_peak else out
