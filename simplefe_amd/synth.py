@@ -805,6 +805,54 @@ def cov_reference(x, S, M, A, scale):
     return float(scale) * np.einsum("kira,kjra->krij", U, U)
 
 
+def fma32(a, b, c):
+    """fmaf(a, b, c) elementwise on float32 arrays (broadcast), correctly rounded: one rounding, of the exact a b + c.
+    float32(float64(a) float64(b) + float64(c)) rounds twice and is wrong on ties.  Here the product is exact in float64
+    (48 bits), TwoSum gives the float64 sum's rounding error, and a sum that is inexact with an even mantissa is stepped to
+    its neighbour in the error's direction (round to odd): float64 carries more than two bits beyond float32, so the
+    rounding to float32 that follows is the only one that counts."""
+    a, b, c = np.broadcast_arrays(*(np.asarray(v, dtype=np.float32).astype(np.float64) for v in (a, b, c)))
+    with np.errstate(invalid="ignore", over="ignore"):
+        p = a * b
+        s = np.asarray(p + c)
+        t = s - p
+        err = (p - (s - t)) + (c - t)
+        step = np.isfinite(s) & (err != 0.0) & ((s.view(np.int64) & 1) == 0)
+        s = np.where(step, np.nextafter(s, np.where(err > 0.0, np.inf, -np.inf)), s)
+        return s.astype(np.float32)[()]
+
+
+def cov_group(A, T=64):
+    """(T, C) of the covariance estimator's summation order: C the smallest power of two with C C >= A / T."""
+    c = 1
+    while c * c * T < A:
+        c *= 2
+    return T, c
+
+
+def cov_law_reference(x, S, M, A, scale):
+    """The law of sfe_dsp_cov_* in its own arithmetic, as include/sfe_dsp.h states the summation order: the rows that n
+    instants complete, (M, n // A, 2S, 2S) float32, whose bits the device must give.  Per row: chunks of T = 64 instants,
+    each the fma32 chain from +0 in ascending instant order; groups of C chunks (the last may be shorter), each the
+    float32 left fold from 0 of its chunk partials; the row the float32 left fold from 0 of its group sums; then one
+    float32 multiply by float32(scale).  x must hold float32 values.  Uses nothing of the library."""
+    T, C = cov_group(A)
+    U = cov_columns(x, S, M).astype(np.float32)
+    rows, AC = U.shape[2] // A, A // T
+    U = U[:, :, :rows * A].reshape(M, 2 * S, rows, A).transpose(0, 2, 1, 3)     # (M, rows, 2S, A): every row at once
+    zero = np.zeros((M, rows, 2 * S, 2 * S), np.float32)
+    total = zero
+    for g in range(0, AC, C):
+        group = zero
+        for ch in range(g, min(g + C, AC)):
+            part = zero
+            for m in range(ch * T, (ch + 1) * T):
+                part = fma32(U[:, :, :, None, m], U[:, :, None, :, m], part)
+            group = group + part
+        total = total + group
+    return total * np.float32(scale)
+
+
 def cov_from_gram(G):
     """(C, P) complex128 out of real Gram matrices (..., 2S, 2S): C = E[x x^H], the covariance, and P = E[x x^T], the
     pseudo-covariance."""
