@@ -1715,6 +1715,114 @@ int sfe_dsp_ldpc_encode_stream(sfe_ldpc_t h, const void *d_payload, size_t in_st
                                sfe_stream_t stream);
 int sfe_dsp_ldpc_destroy(sfe_ldpc_t h);
 
+/* ------------------------------------------------- OFDM burst receiver
+ * The multicarrier answer to multipath, behind the correlator where sfe_dsp_burst_* stands on a
+ * flat channel: for each burst a reach of T training and Ns data symbols of one stream, whose start
+ * offset lies in device memory where sfe_dsp_corr_* wrote it, becomes Ns rows of Nd equalised
+ * data-bin symbols -- cf32 whose components are the soft values sfe_dsp_vit_* and sfe_dsp_ldpc_*
+ * read -- with a per-bin channel estimate, a record and a status.  Nothing is carried from burst to
+ * burst; no host read or copy lies between the blocks.
+ * Shape, fixed at create: n_fft = N a power of two in [64, 4096]; cp in [0, N]; advance = g in
+ * [0, cp]: the transform window starts g samples before the end of the prefix; n_train = T in
+ * [1, 4]; n_data = Ns in [1, 4096]; (T + Ns)(N + cp) < 2^31; kind [N] uint8 per FFT bin k: 0 null,
+ * 1 data, 2 pilot, with Nd >= 1 data bins, Np >= 0 pilot bins, Nu = Nd + Np used bins; train [N]
+ * cf32, finite, non-zero on every used bin; pilot [N] cf32 (may be NULL with Np = 0), finite,
+ * non-zero on every pilot bin; pilot_sign [Ns] int8 of +-1, or NULL for all +1; cfo_mode 0 (none)
+ * or 1 (from the cyclic prefix; needs cp >= 1); cfo_skip = q in [0, cp), 0 with cfo_mode 0;
+ * out_mode SFE_OFDM_OUT_ZF or SFE_OFDM_OUT_MRC; min_gate finite; n_streams >= 1; anything else is
+ * SFE_EINVAL with a message that starts with "ofdm: ".
+ * Burst b of stream s starts at o = start_base + b*start_step + idx: the index and gate tables are
+ * exactly sfe_dsp_burst_*'s, same layouts, same glue behind a one-template correlator.  Symbol j
+ * in [0, T+Ns) occupies [o + j(N+cp), o + (j+1)(N+cp)); its window is the N samples from
+ * o + j(N+cp) + cp - g.  With x stream s, float32 except where float64 is named:
+ *   0  gate, range   as sfe_dsp_burst_*: status 2 for a gate value not >= min_gate; status 3 for a
+ *                    reach [o, o + (T+Ns)(N+cp)) not inside [0, n_in).  Neither reads a sample.
+ *   1  offset        cfo_mode 1: gamma = sum_{j<T+Ns} sum_{q<=i<cp} x[o+j(N+cp)+i+N]
+ *                    conj(x[o+j(N+cp)+i]); eps = arg(gamma) / (2 pi) in subcarrier spacings,
+ *                    |eps| <= 1/2.  Every sample of the reach is used as
+ *                    x'[n] = x[o+n] exp(-j 2 pi eps n / N): the turn count is formed in float64 from
+ *                    the float32 eps, reduced by rint, and only then taken to float32 (step 4 of
+ *                    sfe_dsp_burst_*).  cfo_mode 0: eps = +0 and x' = x.
+ *   2  transform     Y_j[k] = sum_{n<N} x'_j[n] exp(-j 2 pi k n / N), unscaled, over symbol j's
+ *                    window.
+ *   3  channel       H[k] = sum_{j<T} Y_j[k] c[k] on used bins, c[k] = conj(train[k]) /
+ *                    (T |train[k]|^2) from a table made in float64 at create and rounded once;
+ *                    h2 = (1/Nu) sum_used |H[k]|^2.
+ *   4  common phase  per data symbol j < Ns: P_j = sum over the pilot bins k, increasing, of
+ *                    Y_{T+j}[k] conj(H[k] pilot[k] pilot_sign[j]); phi_j = P_j / |P_j|, and
+ *                    1 + 0j when Np = 0.
+ *   5  output        for the data bins in increasing k, i = 0 .. Nd-1:
+ *                    ZF   Z = Y_{T+j}[k] conj(H[k] phi_j) / |H[k]|^2;
+ *                    MRC  Z = Y_{T+j}[k] conj(H[k] phi_j) / h2, the matched-filter output: a QPSK or
+ *                         BPSK soft value up to one scale per burst, which is what min-sum and
+ *                         Viterbi need;
+ *                    cf32 at d_out + (s*n_bursts + b)*out_stride + j*Nd + i.  With d_chan, H as N
+ *                    cf32 at d_chan + (s*n_bursts + b)*N, unused bins +0.  The record, 8 float32 at
+ *                    d_rec + (s*n_bursts + b)*8: eps; h2; min_used |H|^2 / h2; the pilot error
+ *                    sum_j sum_pilot |Y conj(H phi_j) / |H|^2 - pilot sign|^2 / sum_j sum_pilot
+ *                    |pilot|^2 (+0 with Np = 0); arg(phi_0) / (2 pi); arg(phi_{Ns-1}) / (2 pi); +0;
+ *                    +0.  The status, int32 at d_status + s*status_stride + b: 0.
+ *   6  failure       status 1 for a non-finite sample in the reach, a gamma that is zero or not
+ *                    finite in cfo_mode 1, a used bin whose |H|^2 is zero or not finite, or a P_j
+ *                    that is zero or not finite with Np > 0.  A burst of status 1, 2 or 3 gets Ns Nd
+ *                    symbols of +0, a d_chan row of +0 and a record of quiet NaN whose words 6 and
+ *                    7 are still +0.
+ * Promised: the same call gives the same bits on every run; a burst's output depends on its reach,
+ * the handle and the parameters only -- never on b, s, n_bursts, addresses, strides, whether
+ * windows overlap (they may) or how the kernel splits a burst over workgroups; u8 input gives the
+ * bits of the cf32 path on the converted samples; nothing outside the slots named is written; the
+ * exact case: with cfo_mode 0, Np = 0, T = 1, train all ones and x = 1+0j at every window's first
+ * sample and +0 elsewhere, every Z is exactly 1+0j in both output modes, H is exactly 1+0j on used
+ * bins and h2 is 1.  Not promised: the order of the sums, equal bits between shapes, the bits of
+ * the host plan. */
+#define SFE_OFDM_OUT_ZF 0
+#define SFE_OFDM_OUT_MRC 1
+typedef void *sfe_ofdm_t;   /* opaque: one receiver over n_streams streams */
+/* Host-only (no GPU): validates what create validates (one stream).  With x != NULL -- n_in cf32
+ * samples of ONE stream -- it runs n_bursts bursts by the law in float64 (idx [n_bursts] and gate
+ * [n_bursts] host arrays, either may be NULL), eps, H and phi_j rounded to float32 where the law
+ * hands them on, and rounds once to float32 into symbols [n_bursts][Ns*Nd] cf32 (required then),
+ * chan [n_bursts][N] cf32, record [n_bursts][8] and status [n_bursts] (each may be NULL): the CPU
+ * fallback, and the reference of the device's values (not of its bits).  n_in or n_bursts >= 2^31,
+ * or a start_base + b*start_step beyond +-(2^63 - 2^33) for some burst, is SFE_EINVAL. */
+int sfe_dsp_ofdm_plan(int n_fft, int cp, int advance, int n_train, int n_data, const uint8_t *kind,
+                      const float *train, const float *pilot, const int8_t *pilot_sign,
+                      int cfo_mode, int cfo_skip, int out_mode, float min_gate, const float *x,
+                      size_t n_in, const uint32_t *idx, const float *gate, size_t n_bursts,
+                      int64_t start_base, int64_t start_step, float *symbols, float *chan,
+                      float *record, int *status);
+/*   kind, train, pilot, pilot_sign   copied
+ * Arguments are checked before the device is touched: SFE_EINVAL for a bad one on any machine,
+ * SFE_ENODEV without a GPU. */
+int sfe_dsp_ofdm_create(int n_fft, int cp, int advance, int n_train, int n_data,
+                        const uint8_t *kind, const float *train, const float *pilot,
+                        const int8_t *pilot_sign, int cfo_mode, int cfo_skip, int out_mode,
+                        float min_gate, int n_streams, int device, sfe_ofdm_t *out);
+/* SFE_FMT_F32 (cf32 input, 8-byte aligned) or SFE_FMT_U8 ((I,Q) byte pairs, 2-byte aligned,
+ * converted (b-128)*(1/127) on load exactly as sfe_dsp_rx_u8_to_f32); any other format is
+ * SFE_EINVAL.  A call takes the format by value when it is enqueued. */
+int sfe_dsp_ofdm_set_input_format(sfe_ofdm_t h, int fmt);
+/* n_bursts bursts of every stream: stream s at d_in + s*in_stride (samples of the input format),
+ * n_in samples long; the other layouts as above.  d_idx, d_gate, d_chan, d_rec and d_status may
+ * each be NULL.  *n_out = n_bursts; n_bursts = 0 is a no-op.  out_stride < Ns*Nd, or status_stride
+ * < n_bursts with d_status, is SFE_ERANGE; a null d_in or d_out, misaligned buffers (cf32 8 bytes,
+ * u8 pairs 2, the rest 4), in_stride < n_in with more than one stream, n_in >= 2^31,
+ * n_streams*n_bursts >= 2^31, a start_base + b*start_step beyond +-(2^63 - 2^33) for some burst, a
+ * stride that takes a buffer's byte range to 2^62 and any output byte range that overlaps the
+ * input's, the index table's, the gate table's or another output's are SFE_EINVAL; every refusal
+ * carries a message that starts with "ofdm_process_stream: " and nothing is launched.
+ * Asynchronous on `stream`; one kernel launch and nothing else: allocates nothing, does not
+ * synchronise the host, carries no state (there is no reset).  The handle has no setter apart from
+ * the input format, which the call takes by value, so a call on a stream under graph capture IS
+ * supported. */
+int sfe_dsp_ofdm_process_stream(sfe_ofdm_t h, const void *d_in, size_t n_in, size_t in_stride,
+                                const void *d_idx, size_t idx_stride, const void *d_gate,
+                                size_t gate_stride, size_t n_bursts, int64_t start_base,
+                                int64_t start_step, void *d_out, size_t out_stride, void *d_chan,
+                                void *d_rec, void *d_status, size_t status_stride, size_t *n_out,
+                                sfe_stream_t stream);
+int sfe_dsp_ofdm_destroy(sfe_ofdm_t h);
+
 #ifdef __cplusplus
 }
 #endif

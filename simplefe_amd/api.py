@@ -12,7 +12,8 @@ Two layers, both thin:
     (sfe_dsp_iir_*); `Beam`, the multi-stream beamformer / stream-mixing bank (sfe_dsp_beam_*); `Cov`, the streaming
     spatial covariance estimator (sfe_dsp_cov_*); `Mod`, the burst modulator (sfe_dsp_mod_*); `Polar`, the FM, phase and
     envelope detector (sfe_dsp_polar_*); `Occ`, the spectrum occupancy detector over a Psd's rows (sfe_dsp_occ_*);
-    `Reed`, the interleaved Reed-Solomon outer code behind a Vit and in front of a Mod (sfe_dsp_reed_*).
+    `Reed`, the interleaved Reed-Solomon outer code behind a Vit and in front of a Mod (sfe_dsp_reed_*); `Ofdm`, the OFDM burst
+    receiver behind a Corr (sfe_dsp_ofdm_*).
 
 Everything computes on the GPU through the C ABI; numpy is only the host container.
 """
@@ -1773,6 +1774,132 @@ class Ldpc(_Block):
             for d in held:
                 d.free()
         return np.ascontiguousarray(by), np.ascontiguousarray(rec), np.ascontiguousarray(st)
+
+
+def _ofdm_shape(n_fft, cp, advance, n_train, n_data, kind, train, pilot, pilot_sign, cfo_mode, cfo_skip, out_mode, min_gate):
+    """(the leading arguments of sfe_dsp_ofdm_plan / _create, the arrays they point into, Nd)."""
+    fp = C.POINTER(C.c_float)
+    kind = np.ascontiguousarray(kind, dtype=np.uint8).ravel()
+    train = np.ascontiguousarray(np.asarray(train, dtype=np.complex64).ravel())
+    pilot = None if pilot is None else np.ascontiguousarray(np.asarray(pilot, dtype=np.complex64).ravel())
+    sign = None if pilot_sign is None else np.ascontiguousarray(pilot_sign, dtype=np.int8).ravel()
+    for name, v, n in (("kind", kind, n_fft), ("train", train, n_fft), ("pilot", pilot, n_fft), ("pilot_sign", sign, n_data)):
+        if v is not None and v.size != int(n) and int(n) > 0:
+            raise ValueError("ofdm: %s has %d entries, not %d" % (name, v.size, int(n)))
+    head = (int(n_fft), int(cp), int(advance), int(n_train), int(n_data), kind.ctypes.data, train.view(np.float32).ctypes.data_as(fp),
+            None if pilot is None else pilot.view(np.float32).ctypes.data_as(fp), None if sign is None else sign.ctypes.data,
+            int(cfo_mode), int(cfo_skip), int(out_mode), float(min_gate))
+    return head, (kind, train, pilot, sign), int(np.count_nonzero(kind == 1))
+
+
+def ofdm_plan(n_fft, cp, advance, n_train, n_data, kind, train, pilot=None, pilot_sign=None, cfo_mode=0, cfo_skip=0,
+              out_mode=_l.OFDM_OUT_ZF, min_gate=0.0, x=None, idx=None, gate=None, n_bursts=None, start_base=0, start_step=0):
+    """sfe_dsp_ofdm_plan (host only, no GPU): validates, and with x -- the complex samples of ONE stream -- receives
+    n_bursts bursts by the law in float64: returns (symbols (n_bursts, n_data, Nd) complex64, chan (n_bursts, n_fft)
+    complex64, record (n_bursts, 8) float32, status (n_bursts,) int32), or None without x.  idx (uint32) and gate
+    (float32) are host arrays of n_bursts entries or None; n_bursts defaults to len(idx), else 1.  Raises SfeError on
+    arguments the block refuses."""
+    head, keep, Nd = _ofdm_shape(n_fft, cp, advance, n_train, n_data, kind, train, pilot, pilot_sign, cfo_mode, cfo_skip, out_mode, min_gate)
+    fp, L = C.POINTER(C.c_float), _l.load()
+    if x is None:
+        check(L.sfe_dsp_ofdm_plan(*head, None, 0, None, None, 0, 0, 0, None, None, None, None))
+        return None
+    x = np.ascontiguousarray(np.asarray(x, dtype=np.complex64).ravel())
+    if idx is not None:
+        idx = np.ascontiguousarray(idx, dtype=np.uint32).ravel()
+    nb = int(n_bursts) if n_bursts is not None else (idx.size if idx is not None else 1)
+    if gate is not None:
+        gate = np.ascontiguousarray(gate, dtype=np.float32).ravel()
+    for name, v in (("idx", idx), ("gate", gate)):
+        if v is not None and v.size != nb:
+            raise ValueError("ofdm_plan: %s has %d entries for %d bursts" % (name, v.size, nb))
+    Ns, N = max(int(n_data), 0), max(int(n_fft), 0)
+    sym, ch = np.empty((nb, Ns, Nd), np.complex64), np.empty((nb, N), np.complex64)
+    rec, st = np.empty((nb, 8), np.float32), np.empty(nb, np.int32)
+    check(L.sfe_dsp_ofdm_plan(*head, x.view(np.float32).ctypes.data_as(fp), x.size,
+                              None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_uint32)),
+                              None if gate is None else gate.ctypes.data_as(fp), nb, int(start_base), int(start_step),
+                              sym.view(np.float32).ctypes.data_as(fp), ch.view(np.float32).ctypes.data_as(fp), rec.ctypes.data_as(fp),
+                              st.ctypes.data_as(C.POINTER(C.c_int))))
+    return sym, ch, rec, st
+
+
+class Ofdm(_Block):
+    """OFDM burst receiver (sfe_dsp_ofdm_*): per burst, a reach of n_train training and n_data data symbols that starts
+    where the correlator's peak says becomes n_data rows of Nd equalised data-bin symbols -- frequency offset from the
+    cyclic prefix, a per-bin channel estimate from the training symbols, the common phase from the pilots, zero-forcing or
+    matched-filter output -- with the channel estimate, a record (eps, h2, min |H|^2 / h2, pilot error, arg phi_0,
+    arg phi_last, 0, 0) and a status."""
+    _prefix = "ofdm"
+
+    def __init__(self, n_fft, cp, advance, n_train, n_data, kind, train, pilot=None, pilot_sign=None, cfo_mode=0, cfo_skip=0,
+                 out_mode=_l.OFDM_OUT_ZF, min_gate=0.0, n_streams=1, device=0):
+        head, _keep, self.n_data_bins = _ofdm_shape(n_fft, cp, advance, n_train, n_data, kind, train, pilot, pilot_sign, cfo_mode, cfo_skip,
+                                                    out_mode, min_gate)
+        self.n_fft, self.cp, self.advance, self.n_train, self.n_data = int(n_fft), int(cp), int(advance), int(n_train), int(n_data)
+        self.n_sym = self.n_data * self.n_data_bins         # cf32 symbols a burst writes
+        self.n_streams = int(n_streams)
+        self.in_u8 = False
+        self._create(*head, self.n_streams, device)
+
+    def set_input_format(self, fmt):
+        """lib.FMT_F32 (cf32) or lib.FMT_U8 ((I,Q) byte pairs, converted on load)."""
+        self._set_input_format(fmt)
+
+    def process_stream(self, d_in, n_in, n_bursts, d_out, d_idx=None, d_gate=None, d_chan=None, d_rec=None, d_status=None, start_base=0,
+                       start_step=0, in_stride=None, idx_stride=None, gate_stride=None, out_stride=None, status_stride=None, stream=None):
+        """d_*: DeviceArray or raw device pointers.  Burst b of stream s starts at start_base + b*start_step + the uint32
+        at d_idx + s*idx_stride + b (0 without d_idx) of the n_in samples at d_in + s*in_stride, is gated by the float32 at
+        d_gate + s*gate_stride + b, and writes n_data*Nd cf32 symbols at d_out + (s*n_bursts + b)*out_stride, n_fft cf32 at
+        d_chan + (s*n_bursts + b)*n_fft, 8 float32 at d_rec + (s*n_bursts + b)*8 and an int32 at
+        d_status + s*status_stride + b.  in_stride defaults to n_in, out_stride to n_data*Nd and the other strides to
+        n_bursts.  Returns n_bursts."""
+        nb = int(n_bursts)
+        k = C.c_size_t(0)
+        check(self._fn("process_stream")(
+            self._h, self._ptr(d_in), int(n_in), int(n_in) if in_stride is None else int(in_stride),
+            self._ptr(d_idx), nb if idx_stride is None else int(idx_stride), self._ptr(d_gate), nb if gate_stride is None else int(gate_stride),
+            nb, int(start_base), int(start_step), self._ptr(d_out), self.n_sym if out_stride is None else int(out_stride),
+            self._ptr(d_chan), self._ptr(d_rec), self._ptr(d_status), nb if status_stride is None else int(status_stride), C.byref(k), stream))
+        return k.value
+
+    def reset(self):
+        raise AttributeError("Ofdm has no reset: it carries no state")
+
+    def receive(self, x, idx=None, gate=None, n_bursts=None, start_base=0, start_step=0):
+        """Host convenience, computed on the GPU: x is (n_streams, n) complex -- or, with FMT_U8, (n_streams, 2n) uint8
+        (I,Q) pairs -- idx (uint32) and gate (float32) are (n_streams, n_bursts) or None; returns (symbols (n_streams,
+        n_bursts, n_data, Nd) complex64, chan (n_streams, n_bursts, n_fft) complex64, record (n_streams, n_bursts, 8)
+        float32, status (n_streams, n_bursts) int32)."""
+        S, M, N = self.n_streams, self.n_sym, self.n_fft
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(S, -1)
+        if gate is not None:
+            gate = np.ascontiguousarray(gate, dtype=np.float32).reshape(S, -1)
+        nb = int(n_bursts) if n_bursts is not None else (idx.shape[1] if idx is not None else (gate.shape[1] if gate is not None else 1))
+        d_in, n = self._upload_input(x)
+        held = [d_in]
+        try:
+            d_idx = d_gate = None
+            if idx is not None:
+                d_idx = DeviceArray.from_numpy(idx.view(np.float32).ravel())
+                held.append(d_idx)
+            if gate is not None:
+                d_gate = DeviceArray.from_numpy(gate.ravel())
+                held.append(d_gate)
+            d_out, d_ch = DeviceArray(max(1, S * nb * M * 2)), DeviceArray(max(1, S * nb * N * 2))
+            d_rec, d_st = DeviceArray(max(1, S * nb * 8)), DeviceArray(max(1, S * nb))
+            held += [d_out, d_ch, d_rec, d_st]
+            if nb:
+                self.process_stream(d_in, n, nb, d_out, d_idx, d_gate, d_ch, d_rec, d_st, start_base, start_step)
+            sym = d_out.to_numpy(S * nb * M * 2).view(np.complex64).reshape(S, nb, self.n_data, self.n_data_bins)
+            ch = d_ch.to_numpy(S * nb * N * 2).view(np.complex64).reshape(S, nb, N)
+            rec = d_rec.to_numpy(S * nb * 8).reshape(S, nb, 8)
+            st = d_st.to_numpy(S * nb).view(np.int32).reshape(S, nb)
+        finally:
+            for d in held:
+                d.free()
+        return np.ascontiguousarray(sym), np.ascontiguousarray(ch), np.ascontiguousarray(rec), np.ascontiguousarray(st)
 
 
 def rs_plan(state, upsample, n_in, out_len, rate):

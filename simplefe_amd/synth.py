@@ -1349,3 +1349,103 @@ def ldpc_reference(shift, Z, x, scale=8.0, a=12, beta=0, max_iter=32, status_in=
     by[~ok], rec[~ok] = 0, 0
     out = (np.ascontiguousarray(by), np.ascontiguousarray(rec), status)
     return out + (peak,) if with_peak else out
+
+
+# ---- the OFDM burst receiver (sfe_dsp_ofdm_*): a burst waveform made on the host, and the law restated in numpy
+def ofdm_bins(kind):
+    """(data bins, pilot bins) of a kind table, each in increasing k."""
+    kind = np.asarray(kind, dtype=np.uint8).ravel()
+    return np.flatnonzero(kind == 1), np.flatnonzero(kind == 2)
+
+
+def ofdm_signal(n_fft, cp, n_train, kind, train, n, start, symbols=None, bits=None, pilot=None, pilot_sign=None, taps=(1.0,), eps=0.0,
+                noise=0.0, seed=SEED):
+    """n complex64 samples holding one OFDM burst from sample `start` on: n_train training symbols (train on the used
+    bins) and the data symbols -- `symbols`, (n_data, Nd) complex on the data bins in increasing k, or `bits`, 2 n_data Nd
+    coded bits as mod_symbols' Gray QPSK of unit modulus -- with pilot * pilot_sign[j] on the pilot bins, each an inverse
+    transform with its cyclic prefix of cp samples; then the FIR channel `taps`, a frequency offset of eps subcarrier
+    spacings counted from `start`, and complex Gaussian noise of standard deviation `noise` per component.  The transmit
+    transform is scaled 1/N, so that H of the law is the channel's frequency response."""
+    N = int(n_fft)
+    data, pil = ofdm_bins(kind)
+    if symbols is None:
+        symbols = mod_symbols(bits, 4, 1.0).reshape(-1, data.size)
+    symbols = np.asarray(symbols, dtype=np.complex128).reshape(-1, data.size)
+    Ns = symbols.shape[0]
+    sign = np.ones(Ns) if pilot_sign is None else np.asarray(pilot_sign, dtype=np.float64).ravel()
+    train = np.asarray(train, dtype=np.complex128).ravel()
+    X = np.zeros((n_train + Ns, N), np.complex128)
+    used = np.concatenate([data, pil])
+    X[:n_train, used] = train[used]
+    X[n_train:, data] = symbols
+    if pil.size and Ns:
+        X[n_train:, pil] = np.asarray(pilot, dtype=np.complex128).ravel()[pil][None, :] * sign[:, None]
+    t = np.fft.ifft(X, axis=1)
+    frame = np.concatenate([t[:, N - cp:], t], axis=1).ravel()
+    y = np.convolve(frame, np.asarray(taps, dtype=np.complex128))
+    y = y * np.exp(2j * np.pi * float(eps) * np.arange(y.size) / N)
+    out = np.zeros(int(n), np.complex128)
+    hi = min(int(n), int(start) + y.size)
+    out[int(start):hi] = y[:hi - int(start)]
+    if noise:
+        rng = np.random.default_rng(seed)
+        out = out + float(noise) * (rng.standard_normal(out.size) + 1j * rng.standard_normal(out.size))
+    return out.astype(np.complex64)
+
+
+def ofdm_reference(x, o, n_fft, cp, advance, n_train, n_data, kind, train, pilot=None, pilot_sign=None, cfo_mode=0, cfo_skip=0, out_mode=0):
+    """The law of sfe_dsp_ofdm_* on the burst that starts at sample o of the complex64 stream x, in float64 on np.fft,
+    with the law's three hand-overs in float32 (eps, H, phi_j) and the table c rounded once: returns (symbols (n_data, Nd)
+    complex64, chan (n_fft,) complex64, record (8,) float32, status).  Statuses 1 and 3 carry the law's bits; there is
+    no gate here."""
+    N, L, T, Ns = int(n_fft), int(n_fft) + int(cp), int(n_train), int(n_data)
+    data, pil = ofdm_bins(kind)
+    used = np.concatenate([data, pil])
+    x = np.asarray(x, dtype=np.complex64).ravel()
+
+    def failed(st):
+        rec = np.full(8, np.nan, np.float32)
+        rec[6:] = 0.0
+        return np.zeros((Ns, data.size), np.complex64), np.zeros(N, np.complex64), rec, st
+
+    if o < 0 or o + (T + Ns) * L > x.size:
+        return failed(3)
+    r = x[o:o + (T + Ns) * L].astype(np.complex128).reshape(T + Ns, L)
+    if not (np.isfinite(r.real).all() and np.isfinite(r.imag).all()):
+        return failed(1)
+    eps = np.float32(0.0)
+    if cfo_mode:
+        gamma = np.sum(r[:, cfo_skip + N:cp + N] * np.conj(r[:, cfo_skip:cp]))
+        if gamma == 0 or not np.isfinite(gamma):
+            return failed(1)
+        eps = np.float32(np.angle(gamma) / (2.0 * np.pi))
+        nn = np.arange((T + Ns) * L, dtype=np.float64).reshape(T + Ns, L)
+        turn = np.float64(eps) * nn / N
+        r = r * np.exp(-2j * np.pi * (turn - np.rint(turn)))
+    Y = np.fft.fft(r[:, cp - advance:cp - advance + N], axis=1)
+    tr = np.asarray(train, dtype=np.complex64).ravel().astype(np.complex128)[used]
+    c = (np.conj(tr) / (T * np.abs(tr) ** 2)).astype(np.complex64).astype(np.complex128)
+    H = np.zeros(N, np.complex128)
+    H[used] = (Y[:T, used].sum(axis=0) * c).astype(np.complex64)
+    p = np.abs(H[used]) ** 2
+    p32 = p.astype(np.float32)
+    if not (np.all(p32 > 0) and np.isfinite(p32).all()):
+        return failed(1)
+    h2 = p.mean()
+    sign = np.ones(Ns) if pilot_sign is None else np.asarray(pilot_sign, dtype=np.float64).ravel()
+    phi = np.ones(Ns, np.complex128)
+    D = Y[T:]
+    perr = 0.0
+    if pil.size and Ns:
+        pl = np.asarray(pilot, dtype=np.complex64).ravel().astype(np.complex128)[pil]
+        want = pl[None, :] * sign[:, None]
+        P = np.sum(D[:, pil] * np.conj(H[pil][None, :] * want), axis=1)
+        if np.any(P == 0) or not np.isfinite(P).all():
+            return failed(1)
+        phi = (P / np.abs(P)).astype(np.complex64).astype(np.complex128)
+        zp = D[:, pil] * np.conj(H[pil][None, :] * phi[:, None]) / np.abs(H[pil][None, :]) ** 2
+        perr = np.sum(np.abs(zp - want) ** 2) / (Ns * np.sum(np.abs(pl) ** 2))
+    Z = D[:, data] * np.conj(H[data][None, :] * phi[:, None])
+    Z = Z / (h2 if out_mode == 1 else np.abs(H[data][None, :]) ** 2)
+    rec = np.array([eps, h2, p.min() / h2, perr, np.angle(phi[0]) / (2 * np.pi), np.angle(phi[-1]) / (2 * np.pi), 0.0, 0.0], np.float32)
+    return Z.astype(np.complex64), H.astype(np.complex64), rec, 0
