@@ -1393,11 +1393,14 @@ def ofdm_signal(n_fft, cp, n_train, kind, train, n, start, symbols=None, bits=No
     return out.astype(np.complex64)
 
 
-def ofdm_reference(x, o, n_fft, cp, advance, n_train, n_data, kind, train, pilot=None, pilot_sign=None, cfo_mode=0, cfo_skip=0, out_mode=0):
+def ofdm_reference(x, o, n_fft, cp, advance, n_train, n_data, kind, train, pilot=None, pilot_sign=None, cfo_mode=0, cfo_skip=0, out_mode=0,
+                   eps=None):
     """The law of sfe_dsp_ofdm_* on the burst that starts at sample o of the complex64 stream x, in float64 on np.fft,
     with the law's three hand-overs in float32 (eps, H, phi_j) and the table c rounded once: returns (symbols (n_data, Nd)
     complex64, chan (n_fft,) complex64, record (8,) float32, status).  Statuses 1 and 3 carry the law's bits; there is
-    no gate here."""
+    no gate here.  `eps`, where given with cfo_mode 1, is the float32 hand-over itself -- an implementation's own estimate,
+    say -- and takes the place of angle(gamma) / 2 pi; everything behind the hand-over is the law's."""
+    eps_in = eps
     N, L, T, Ns = int(n_fft), int(n_fft) + int(cp), int(n_train), int(n_data)
     data, pil = ofdm_bins(kind)
     used = np.concatenate([data, pil])
@@ -1418,7 +1421,7 @@ def ofdm_reference(x, o, n_fft, cp, advance, n_train, n_data, kind, train, pilot
         gamma = np.sum(r[:, cfo_skip + N:cp + N] * np.conj(r[:, cfo_skip:cp]))
         if gamma == 0 or not np.isfinite(gamma):
             return failed(1)
-        eps = np.float32(np.angle(gamma) / (2.0 * np.pi))
+        eps = np.float32(np.angle(gamma) / (2.0 * np.pi)) if eps_in is None else np.float32(eps_in)
         nn = np.arange((T + Ns) * L, dtype=np.float64).reshape(T + Ns, L)
         turn = np.float64(eps) * nn / N
         r = r * np.exp(-2j * np.pi * (turn - np.rint(turn)))

@@ -1,4 +1,5 @@
-"""The shapes, channels and waveforms the OFDM-receiver tests share (tests/test_ofdm_host.py, tests/test_gpu_ofdm.py).
+"""The shapes, channels and waveforms the OFDM-receiver tests share (tests/test_ofdm_host.py, tests/test_gpu_ofdm.py,
+tests/test_gpu_ofdm_grid.py).
 Host only: numpy and simplefe_amd.synth; nothing here touches the library or a GPU."""
 import numpy as np
 
@@ -23,6 +24,45 @@ SHAPES = {
                   taps={0: 1.0, 3: 0.4 * np.exp(2.5j), 11: 0.2 * np.exp(-0.8j)}, eps=-0.31),
 }
 NAMES = list(SHAPES)
+
+# One shape per kernel size, log2 N = 6 .. 12, with EVERY bin used -- DC and N / 2 included -- so that the whole of every
+# transform's output is compared: data_k None is "all bins that are no pilot", pilot_k the pilot bins themselves.  The window
+# starts four samples before the prefix ends and the 3-tap channel, its first tap dominant, ends inside those four.  Between
+# them: T = 1 .. 4; cfo_skip = 0 and cp - 1 (one product per symbol); cp odd and smaller than the workgroup, N + cp no
+# multiple of it; cfo_mode 0; no pilots, one, two, and more pilots than lanes; and one data bin alone (Nd = 1, bin N - 1).
+def _grid(n_fft, cp, advance, n_train, n_data, spacing, cfo_skip, eps, cfo_mode=1, data_k=None, turn=0.0):
+    pilot_k = () if spacing is None else tuple(range(spacing // 2, n_fft, spacing))
+    return dict(n_fft=n_fft, cp=cp, advance=advance, n_train=n_train, n_data=n_data, cfo_mode=cfo_mode, cfo_skip=cfo_skip, data_k=data_k,
+                pilot_k=pilot_k, taps={0: np.exp(1j * turn), 1: 0.3 * np.exp(1j * (1.0 + turn)), 3: 0.15 * np.exp(1j * (turn - 2.0))}, eps=eps)
+
+
+GRID = {
+    "g64": _grid(64, 16, 12, 2, 3, 8, 15, 0.21),                        # 8 pilots; cfo_skip = cp - 1
+    "g128": _grid(128, 9, 5, 4, 2, 16, 0, -0.08, turn=0.5),             # T = 4; cp odd, below the 64 lanes
+    "g256": _grid(256, 7, 3, 3, 2, 16, 6, 0.33, turn=-1.1),             # T = 3; four butterflies per lane in one wave
+    "g512": _grid(512, 40, 36, 1, 2, None, 0, -0.27, turn=2.0),         # no pilots
+    "g1024": _grid(1024, 100, 96, 2, 2, 64, 99, 0.11, turn=0.9),        # four waves; cfo_skip = cp - 1
+    "g2048": _grid(2048, 33, 29, 1, 1, 1024, 32, -0.19, turn=-0.4),     # two pilots; a radix-2 pass before multi-element radix-4 passes
+    "g4096": _grid(4096, 24, 20, 1, 1, 3, 0, 0.0, cfo_mode=0, turn=1.7),            # 1366 pilots on 256 lanes; cfo_mode 0
+    "g2048one": _grid(2048, 33, 29, 2, 3, None, 0, 0.26, data_k=(2047,), turn=0.3),            # Nd = 1, no pilots
+    "g128p1": _grid(128, 9, 5, 1, 2, 128, 8, 0.45, turn=-2.3),          # Np = 1: the one pilot is bin N / 2; eps near the half
+}
+GRID_NAMES = list(GRID)
+
+# The long burst: the n64 shape's bins, pilots and channel with 1024 data symbols -- 82 080 samples, and with eps near a half
+# the turn count eps n / N passes 500: formed in float32 it is rounded to some 3e-5 of a turn before it is reduced, formed in
+# float64 and reduced first, as the law says, to 1e-13.
+LONG = {name: dict(SHAPES["n64"], n_data=1024, eps=eps) for name, eps in (("long+", 0.4), ("long-", -0.47))}
+LONG_NAMES = list(LONG)
+
+
+def shape(name):
+    return SHAPES[name] if name in SHAPES else GRID[name] if name in GRID else LONG[name]
+
+
+def bursts(name):
+    """Bursts in a shape's stream: three, one of the long burst."""
+    return 1 if name in LONG else 3
 RATIO_BAR = 1.0 / 16.0          # min_used |H|^2 / h2 of every equalised case
 
 # The worst error vector |Z - sent| of the float64 plan over each shape's noiseless bursts (zero-forcing output), as
@@ -32,15 +72,20 @@ WORST = {"n64": 1.885e-7, "n128": 1.898e-2, "n512": 1.027e-2, "n4096": 2.149e-7}
 
 def tables(name):
     """kind uint8 [N], train complex64 [N], pilot complex64 [N] or None, pilot_sign int8 [Ns] or None."""
-    sh = SHAPES[name]
+    sh = shape(name)
     N, Ns = sh["n_fft"], sh["n_data"]
     k = np.arange(N)
     f = np.where(k < N // 2, k, k - N)                  # the bin's signed frequency
-    kind = np.where((np.abs(f) <= sh["used"]) & (f != 0), 1, 0).astype(np.uint8)
-    kind[np.isin(np.abs(f), sh["pilots"])] = 2
+    if "pilot_k" in sh:                                 # a GRID shape: the bins themselves
+        kind = np.ones(N, np.uint8) if sh["data_k"] is None else np.isin(k, sh["data_k"]).astype(np.uint8)
+        kind[list(sh["pilot_k"])] = 2
+    else:
+        kind = np.where((np.abs(f) <= sh["used"]) & (f != 0), 1, 0).astype(np.uint8)
+        kind[np.isin(np.abs(f), sh["pilots"])] = 2
+    has_pilots = bool((kind == 2).any())
     seed = synth.SEED + N
     train = (synth.psk_symbols(N, 4, seed=seed) * (1.0 + 0.25 * np.cos(0.37 * k))).astype(np.complex64)
-    if not sh["pilots"]:
+    if not has_pilots:
         return kind, train, None, None
     pilot = (synth.psk_symbols(N, 2, seed=seed + 1) * 1.25).astype(np.complex64)
     sign = np.where(synth.vit_bits(Ns, seed=seed + 2) == 1, -1, 1).astype(np.int8)
@@ -49,7 +94,7 @@ def tables(name):
 
 def shape_args(name, out_mode=0, min_gate=0.0):
     """The keyword arguments of api.ofdm_plan / api.Ofdm for a shape."""
-    sh = SHAPES[name]
+    sh = shape(name)
     kind, train, pilot, sign = tables(name)
     return dict(n_fft=sh["n_fft"], cp=sh["cp"], advance=sh["advance"], n_train=sh["n_train"], n_data=sh["n_data"], kind=kind, train=train,
                 pilot=pilot, pilot_sign=sign, cfo_mode=sh["cfo_mode"], cfo_skip=sh["cfo_skip"], out_mode=out_mode, min_gate=min_gate)
@@ -62,7 +107,7 @@ def reference_args(name, out_mode=0):
 
 
 def reach(name):
-    sh = SHAPES[name]
+    sh = shape(name)
     return (sh["n_train"] + sh["n_data"]) * (sh["n_fft"] + sh["cp"])
 
 
@@ -71,7 +116,7 @@ def n_data_bins(name):
 
 
 def channel(name):
-    taps = SHAPES[name]["taps"]
+    taps = shape(name)["taps"]
     h = np.zeros(max(taps) + 1, np.complex128)
     for d, v in taps.items():
         h[d] = v
@@ -80,7 +125,7 @@ def channel(name):
 
 def sent_symbols(name, b, seed=0):
     """The (n_data, Nd) unit QPSK symbols burst b carries, complex64."""
-    sh = SHAPES[name]
+    sh = shape(name)
     Nd = n_data_bins(name)
     bits = synth.vit_bits(2 * sh["n_data"] * Nd, seed=synth.SEED + 1000 * seed + 17 * b + sh["n_fft"])
     return synth.mod_symbols(bits, 4, 1.0).reshape(sh["n_data"], Nd)
@@ -89,13 +134,14 @@ def sent_symbols(name, b, seed=0):
 _streams = {}
 
 
-def stream(name, n_bursts=3, noise=0.0, gain=1.0, seed=0):
+def stream(name, n_bursts=None, noise=0.0, gain=1.0, seed=0):
     """One stream of n_bursts bursts of a shape through its channel and offset: (x complex64, starts int64 [n_bursts], the
     sent symbols (n_bursts, n_data, Nd)).  Burst b starts 11 + 3 b samples into its slot of reach + 40 samples.  Cached:
     callers must not write into what they get."""
+    n_bursts = bursts(name) if n_bursts is None else n_bursts
     key = (name, n_bursts, noise, gain, seed)
     if key not in _streams:
-        sh = SHAPES[name]
+        sh = shape(name)
         kind, train, pilot, sign = tables(name)
         slot = reach(name) + 40
         starts = np.array([b * slot + 11 + 3 * b for b in range(n_bursts)], np.int64)
@@ -116,9 +162,10 @@ def stream(name, n_bursts=3, noise=0.0, gain=1.0, seed=0):
 _refs = {}
 
 
-def reference(name, out_mode=0, n_bursts=3):
+def reference(name, out_mode=0, n_bursts=None):
     """synth.ofdm_reference over stream(name, n_bursts): (symbols (n_bursts, n_data, Nd), chan (n_bursts, N), record
     (n_bursts, 8), status (n_bursts,)).  Cached."""
+    n_bursts = bursts(name) if n_bursts is None else n_bursts
     key = (name, out_mode, n_bursts)
     if key not in _refs:
         x, starts, _ = stream(name, n_bursts)
@@ -130,7 +177,7 @@ def reference(name, out_mode=0, n_bursts=3):
 def exact_case(name, n_bursts=2):
     """The exact case on a shape's sizes: cfo_mode 0, no pilots, T = 1, train all ones, and x = 1+0j at every window's first
     sample and +0 elsewhere: (keyword arguments without out_mode, x, starts)."""
-    sh = SHAPES[name]
+    sh = shape(name)
     N, cp, g, Ns = sh["n_fft"], sh["cp"], sh["advance"], sh["n_data"]
     kind = (tables(name)[0] != 0).astype(np.uint8)
     args = dict(n_fft=N, cp=cp, advance=g, n_train=1, n_data=Ns, kind=kind, train=np.ones(N, np.complex64), pilot=None, pilot_sign=None,
@@ -149,7 +196,7 @@ def rel_rms(got, want):
 
 
 # the condition on the inputs: every equalised case keeps its weakest used bin within 12 dB of the mean
-for _name in NAMES:
+for _name in NAMES + GRID_NAMES + LONG_NAMES:
     _rec, _st = reference(_name)[2:]
     assert not _st.any() and (_rec[:, 2] >= RATIO_BAR).all(), (_name, _rec[:, 2])
 

@@ -8,11 +8,10 @@ import numpy as np
 import pytest
 
 from simplefe_amd import synth
+from vit_cases import SENT, rows_of, run, same
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
-SENT = np.float32(-7654.25)         # around records and statuses
-SENT_BYTE = 0xA5                    # around the payload bytes
 QNAN = 0x7fc00000
 CODES = [(3, (7, 5)), (7, (0o171, 0o133)), (7, (0o133, 0o171, 0o165)), (8, (0o247, 0o371)), (9, (0o561, 0o753))]
 CODE_IDS = ["K3", "K7", "K7n3", "K8", "K9"]
@@ -29,64 +28,6 @@ def api():
 def L():
     from simplefe_amd import lib
     return lib
-
-
-def rows_of(api, K, gen, n_info, keep, terminated, n_bursts, seed):
-    """n_bursts rows of soft values: noisy BPSK at 2 dB of different payloads, and, as rows 1 and 2 (where there are that
-    many), integer-valued values -- most steps tie -- and all zeros."""
-    rng = np.random.default_rng(seed)
-    rows = []
-    for b in range(n_bursts):
-        coded = api.vit_encode(K, gen, synth.vit_bits(n_info, seed + 10 * b), keep, terminated)
-        if b == 1:
-            rows.append(rng.integers(-2, 3, size=coded.size).astype(F32))
-        elif b == 2:
-            rows.append(np.zeros(coded.size, F32))
-        else:
-            rows.append(synth.vit_soft(coded, 2.0, 1.0 / len(gen), seed + 10 * b + 1))
-    return np.stack(rows)
-
-
-def run(api, h, x, in_pad=0, out_pad=0, lead=0, status_in=None, call=None):
-    """One call through guarded buffers: the rows `lead` elements into their buffer and in_pad elements apart, the bytes
-    out_pad apart, a sentinel everywhere else; returns (bytes, record, status) with the guard bands checked.  `call`
-    replaces the plain process_stream (a captured one, say): it gets the same arguments."""
-    soft = h.in_mode == 0
-    x = np.ascontiguousarray(x, F32 if soft else np.complex64)
-    nb, w = x.shape[0], 1 if soft else 2
-    stride = x.shape[1] + in_pad
-    buf = np.full((lead + nb * stride + 3) * w, np.nan, F32)
-    for b in range(nb):
-        buf[(lead + b * stride) * w:][:x.shape[1] * w] = x[b].view(F32)
-    d_in = api.DeviceArray.from_numpy(buf)
-    ostride, front = h.n_bytes + out_pad, 5
-    raw_by = np.full(front + nb * ostride + 7, SENT_BYTE, np.uint8)
-    d_by = api.DeviceArray.from_bytes(raw_by)
-    d_rec, d_st = api.DeviceArray.from_numpy(np.full(3 + 2 * nb + 5, SENT, F32)), api.DeviceArray.from_numpy(np.full(5 + nb + 3, SENT, F32))
-    held = [d_in, d_by, d_rec, d_st]
-    d_si = None
-    if status_in is not None:
-        d_si = api.DeviceArray.from_numpy(np.ascontiguousarray(status_in, np.int32).view(F32))
-        held.append(d_si)
-    try:
-        args = (d_in.ptr + 4 * w * lead, nb, d_by.ptr + front, d_rec.ptr + 12, d_st.ptr + 20, d_si)
-        k = (call or h.process_stream)(*args, in_stride=stride, out_stride=ostride)
-        api.sync()
-        assert k == nb
-        by, rec, st = d_by.to_numpy().view(np.uint8)[:raw_by.size], d_rec.to_numpy(), d_st.to_numpy()
-    finally:
-        for d in held:
-            d.free()
-    sent = np.array([SENT]).view(np.uint32)[0]
-    body = by[front:front + nb * ostride].reshape(nb, ostride)
-    assert (by[:front] == SENT_BYTE).all() and (by[front + nb * ostride:] == SENT_BYTE).all() and (body[:, h.n_bytes:] == SENT_BYTE).all()
-    assert (rec[:3].view(np.uint32) == sent).all() and (rec[3 + 2 * nb:].view(np.uint32) == sent).all()
-    assert (st[:5].view(np.uint32) == sent).all() and (st[5 + nb:].view(np.uint32) == sent).all()
-    return np.ascontiguousarray(body[:, :h.n_bytes]), rec[3:3 + 2 * nb].view(np.uint32).reshape(nb, 2), st[5:5 + nb].view(np.int32)
-
-
-def same(got, want):
-    return all(np.array_equal(u, v) for u, v in zip(got, want))
 
 
 @pytest.mark.parametrize("code", CODES, ids=CODE_IDS)

@@ -9,7 +9,9 @@ import re
 import numpy as np
 import pytest
 
+import vit_cases as vc
 from simplefe_amd import synth
+from vit_cases import encode_np, law_np, soft_inputs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = os.path.join(ROOT, "include", "sfe_dsp.h")
@@ -35,84 +37,6 @@ def L():
 def api():
     from simplefe_amd import api as a
     return a
-
-
-# ---- the law, restated: nothing below calls the library
-def parity(v):
-    v = np.asarray(v, np.uint32).copy()
-    for sh in (16, 8, 4, 2, 1):
-        v ^= v >> sh
-    return (v & 1).astype(np.uint8)
-
-
-def encode_np(K, gen, bits, keep=None, terminated=True):
-    """(the kept coded bits, every coded bit as (T, n), the (T, n) mask of kept positions)."""
-    n = len(gen)
-    word = list(bits) + [0] * (K - 1 if terminated else 0)
-    keep = np.ones((1, n), np.uint8) if keep is None else np.asarray(keep, np.uint8)
-    s, full = 0, np.zeros((len(word), n), np.uint8)
-    for t, u in enumerate(word):
-        reg = ((s << 1) | int(u)) % (1 << K)
-        for j, g in enumerate(gen):
-            full[t, j] = bin(reg & g).count("1") & 1
-        s = reg % (1 << (K - 1))
-    mask = np.array([keep[t % len(keep)] for t in range(len(word))], bool)
-    return full[mask], full, mask
-
-
-def law_np(K, gen, n_info, soft, keep=None, terminated=True):
-    """One burst by the law of include/sfe_dsp.h in numpy float32: (bytes uint8, metric word uint32, count, status)."""
-    n, S = len(gen), 1 << (K - 1)
-    T = n_info + (K - 1 if terminated else 0)
-    soft = np.asarray(soft, F32)
-    nbytes = (n_info + 7) // 8
-    if not np.isfinite(soft).all():
-        return np.zeros(nbytes, np.uint8), 0x7fc00000, 0, 1
-    keep = np.ones((1, n), np.uint8) if keep is None else np.asarray(keep, np.uint8)
-    r = np.zeros((T, n), F32)                   # punctured positions: +0
-    i = 0
-    for t in range(T):
-        for j in range(n):
-            if keep[t % len(keep), j]:
-                r[t, j] = soft[i]
-                i += 1
-    assert i == soft.size
-    s = np.arange(S)
-    p0, p1 = s >> 1, (s >> 1) | (S >> 1)
-    u = s & 1
-    regs = [(p << 1 | u) % (1 << K) for p in (p0, p1)]
-    neg = [[parity(reg & g).astype(bool) for g in gen] for reg in regs]      # [branch][j][state]
-    pm = np.full(S, -np.inf, F32)
-    pm[0] = F32(0.0)
-    dec = np.zeros((T, S), np.uint8)
-    for t in range(T):
-        cand = []
-        for br, p in enumerate((p0, p1)):
-            bm = np.where(neg[br][0], -r[t, 0], r[t, 0]).astype(F32)
-            for j in range(1, n):
-                bm = (bm + np.where(neg[br][j], -r[t, j], r[t, j]).astype(F32)).astype(F32)
-            cand.append((pm[p] + bm).astype(F32))
-        dec[t] = cand[1] > cand[0]
-        pm = np.where(dec[t].astype(bool), cand[1], cand[0]).astype(F32)
-    end = 0 if terminated else int(np.argmax(pm))           # the first of the largest
-    word, st = np.zeros(T, np.uint8), end
-    for t in range(T - 1, -1, -1):
-        word[t] = st & 1
-        st = (st >> 1) | (int(dec[t, st]) << (K - 2))
-    bits = word[:n_info]
-    _, full, mask = encode_np(K, gen, bits, keep, terminated)
-    count = int((((full == 1) & (r > 0)) | ((full == 0) & (r < 0)))[mask].sum())
-    return np.packbits(bits), int(pm[end:end + 1].view(np.uint32)[0]), count, 0
-
-
-def soft_inputs(K, gen, n_info, keep, terminated, seed):
-    """Three rows of a shape: noisy BPSK at 2 dB, integer-valued values (most steps tie), all zeros."""
-    bits = synth.vit_bits(n_info, seed)
-    coded = encode_np(K, gen, bits, keep, terminated)[0]
-    rng = np.random.default_rng(seed + 1)
-    noisy = synth.vit_soft(coded, 2.0, 1.0 / len(gen), seed + 2)
-    ints = rng.integers(-2, 3, size=coded.size).astype(F32)
-    return np.stack([noisy, ints, np.zeros(coded.size, F32)])
 
 
 # ---- the ABI
@@ -160,6 +84,25 @@ def test_plan_equals_the_numpy_restatement(api, code, terminated, n_info):
             wby, wm, wc, wst = law_np(K, gen, n_info, x[b], keep, terminated)
             assert np.array_equal(by[b], wby) and int(rec[b, 0]) == wm and int(rec[b, 1]) == wc and st[b] == wst, (keep, b)
         # all zeros: all-zero bits, metric +0, nothing disagrees
+        assert not by[2].any() and rec[2].tolist() == [0, 0] and st[2] == 0
+
+
+@pytest.mark.parametrize("code", vc.GRID_CODES, ids=vc.GRID_CODE_IDS)
+def test_plan_and_encoder_equal_the_restatement_over_the_grid(api, code):
+    """vit_cases' grid -- K = 3 .. 9 with 2, 3 and 4 generators, no puncturing and periods 3, 17 and 32 (the last two reach
+    into the second word of the keep mask), both endings, n_info 1, 40 and 131 -- on noisy, integer-valued and all-zero
+    rows: the plan is the numpy restatement bit for bit, the encoder is encode_np and n_soft is its length."""
+    K, gen = code
+    for name, keep, terminated, n_info, seed in vc.grid_cases(K, gen):
+        bits = synth.vit_bits(n_info, seed)
+        coded = encode_np(K, gen, bits, keep, terminated)[0]
+        assert np.array_equal(api.vit_encode(K, gen, bits, keep, terminated), coded), (name, terminated, n_info)
+        assert api.vit_plan(K, gen, n_info, keep, terminated) == coded.size
+        x = soft_inputs(K, gen, n_info, keep, terminated, seed)
+        by, rec, st = api.vit_plan(K, gen, n_info, keep, terminated, x=x)
+        for b in range(x.shape[0]):
+            wby, wm, wc, wst = law_np(K, gen, n_info, x[b], keep, terminated)
+            assert np.array_equal(by[b], wby) and int(rec[b, 0]) == wm and int(rec[b, 1]) == wc and st[b] == wst, (name, terminated, n_info, b)
         assert not by[2].any() and rec[2].tolist() == [0, 0] and st[2] == 0
 
 
