@@ -1823,6 +1823,108 @@ int sfe_dsp_ofdm_process_stream(sfe_ofdm_t h, const void *d_in, size_t n_in, siz
                                 sfe_stream_t stream);
 int sfe_dsp_ofdm_destroy(sfe_ofdm_t h);
 
+/* ------------------------------------------------- OFDM burst modulator
+ * The transmit mirror of the OFDM burst receiver: per burst, a row of coded bits -- what
+ * sfe_dsp_ldpc_encode_stream, sfe_dsp_vit_* or sfe_dsp_reed_* wrote -- or of cf32 symbols -- a row
+ * of sfe_dsp_ofdm_*'s d_out -- on the device becomes one frame of T training and Ns data symbols,
+ * each N samples behind its cyclic prefix, at a stated place of an output stream, cf32 or the
+ * transmit wire format.  Bursts and symbols are independent; nothing is carried.  No NCO: frequency
+ * placement is sfe_dsp_combine_*'s.
+ * Shape, fixed at create: n_fft = N, cp, n_train = T, n_data = Ns, kind [N], train [N], pilot [N]
+ * and pilot_sign [Ns] mean what they mean for sfe_dsp_ofdm_* and are validated the same way: N a
+ * power of two in [64, 4096]; cp in [0, N]; T in [1, 4]; Ns in [1, 4096]; (T + Ns)(N + cp) < 2^31;
+ * Nd >= 1 data bins; train finite, and non-zero on every used bin; pilot (may be NULL with Np = 0)
+ * finite, and non-zero on every pilot bin; pilot_sign of +-1, or NULL for all +1.  There is no
+ * advance, cfo or out_mode.  amp is finite and > 0; order is 2 or 4; in_mode is
+ * SFE_OFDMMOD_IN_BITS or SFE_OFDMMOD_IN_SYMBOLS; out_fmt is SFE_FMT_F32 or SFE_FMT_TX10, under
+ * which cp must be even.  There is no setter.  Anything else is SFE_EINVAL with a message that
+ * starts with "ofdmmod: ".
+ * Bins: two tables are made at create, ta = amp train and pa = amp pilot, one float32 product per
+ * component.  For symbol j < T + Ns and bin k: a null bin is +0; a training symbol (j < T) carries
+ * ta[k] on every used bin; a data symbol carries pa[k] pilot_sign[j-T], one product per component,
+ * on a pilot bin, and on data bin i of Nd, in increasing k:
+ *   BITS, order 2      (amp (1 - 2c), +0)
+ *   BITS, order 4      (a4 (1 - 2 c_0), a4 (1 - 2 c_1)), a4 = float32(amp / sqrt 2), formed in
+ *                      float64 and rounded once: sfe_dsp_mod_*'s Gray QPSK, which SFE_VIT_IN_QPSK
+ *                      undoes
+ *                      coded bit t = ((j-T) Nd + i) bps + c, bps = 1 or 2, is bit 7 - (t mod 8) of
+ *                      byte floor(t / 8) at d_in + b*in_stride (bytes): MSB-first, the layout
+ *                      sfe_dsp_ldpc_encode_stream, sfe_dsp_vit_* and sfe_dsp_reed_* write.  A burst
+ *                      reads ceil(Ns Nd bps / 8) bytes.
+ *   SYMBOLS            the cf32 at d_in + b*in_stride + (j-T) Nd + i (in_stride in cf32) times amp,
+ *                      one product per component; order is ignored.  Exactly the layout of
+ *                      sfe_dsp_ofdm_*'s d_out rows; a burst reads Ns Nd cf32.
+ * Transform: x_j[n] = (1/N) sum_k X_j[k] exp(+j 2 pi k n / N), so that the receiver's H is the
+ * channel's response.  simplefe_amd/csrc/ofdmmod_law.h states it operation by operation, and both
+ * the kernel and the host plan compile that header: one radix-2 pass when log2 N is odd, then
+ * radix-4 Stockham passes; twiddles from a table exp(+j 2 pi q / N) made in float64 and rounded
+ * once; the complex product two explicit fmaf over one rounded product each; every output of a
+ * pass a fixed expression of its inputs; last the product with the exact power of two 1/N.  Passes
+ * are data-parallel, so no order of lanes can matter.
+ * Frame: symbol j is cp + N samples, x_j[N-cp .. N) then x_j[0 .. N); F = (T + Ns)(N + cp).
+ * Placement: sfe_dsp_mod_*'s, word for word.  A call defines EVERY sample of the output stream
+ * [0, n_out).  Burst b's frame occupies [o_b, o_b + F), o_b = start_base + b*start_step; every
+ * sample in no frame is +0.  SFE_EINVAL, nothing launched: start_base < 0; start_step < F with
+ * more than one burst (start_step is ignored with one); o_(n_bursts-1) + F > n_out; n_out or
+ * n_bursts >= 2^31; an odd n_out under TX10.  n_bursts = 0 writes n_out zeros.
+ * TX10: the bytes are exactly sfe_dsp_tx_f32_to_10bit's of the F32 output -- two complex samples in
+ * 5 bytes, the groups aligned to the stream; (n_out / 2) * 5 bytes are written.  In addition cp
+ * (at create), start_base and start_step (at the call; start_step with more than one burst) must
+ * be even, so that no group straddles a symbol or a frame: an odd one is SFE_EINVAL.  A call whose
+ * workgroups -- one per symbol, one per 4096 samples in no frame -- number 2^31 or more is
+ * SFE_EINVAL.
+ * Promised: the same call gives the same bits on every run; a frame depends on its input row and
+ * the handle only -- never on b, n_bursts, addresses, strides or offsets; the device's F32 words
+ * and TX10 bytes EQUAL sfe_dsp_ofdmmod_plan's, for every input whose intermediate values are zero
+ * or normal numbers (nothing is promised otherwise); nothing outside the n_out samples is written;
+ * samples i and i + N of a symbol are bit-equal for i < cp; the exact case: with every bin a data
+ * bin, order 2, amp 1 and all bits 0, a data symbol is exactly 1+0j at its sample cp and zero at
+ * every other sample (compare with ==: the sign of a zero is not promised; with cp = N the prefix
+ * is the whole symbol, so sample 0 is the copy of sample cp), and with train all ones so is a
+ * training symbol -- the input of sfe_dsp_ofdm_*'s own exact case with advance 0.
+ * There is no status output: bytes are always valid, and a non-finite symbol in SYMBOLS mode
+ * propagates (nothing is promised for it). */
+#define SFE_OFDMMOD_IN_BITS 0
+#define SFE_OFDMMOD_IN_SYMBOLS 1
+typedef void *sfe_ofdmmod_t;  /* opaque: one modulator; it owns its tables on the device and nothing in it changes after create */
+/* Host-only: the lanes of the workgroup that makes one symbol of n_fft bins, the samples in no
+ * frame one workgroup writes, and the LDS a symbol's workgroup uses (each pointer may be NULL). */
+int sfe_dsp_ofdmmod_footprint(int n_fft, int *threads, int *zero_tile_samples, size_t *lds_bytes);
+/* Host-only (no GPU): validates what create validates and reports Nd, F and what a burst reads --
+ * bytes in BITS mode, cf32 symbols in SYMBOLS mode (each pointer may be NULL); then the placement
+ * as process_stream does; then, with out != NULL, writes the stream by the law above, exactly as
+ * stated -- n_out cf32 samples, or (n_out / 2) * 5 bytes under SFE_FMT_TX10 -- from in (host
+ * memory laid out as d_in; required with n_bursts > 0): the reference of the device's bits.
+ * in_stride below what a burst reads is SFE_ERANGE. */
+int sfe_dsp_ofdmmod_plan(int n_fft, int cp, int n_train, int n_data, const uint8_t *kind,
+                         const float *train, const float *pilot, const int8_t *pilot_sign,
+                         float amp, int order, int in_mode, int out_fmt, const void *in,
+                         size_t in_stride, size_t n_bursts, int64_t start_base, int64_t start_step,
+                         size_t n_out, void *out, int *n_data_bins, int *frame_len, size_t *n_in);
+/*   kind, train, pilot, pilot_sign   copied
+ * Arguments are checked before the device is touched: SFE_EINVAL for a bad one on any machine,
+ * SFE_ENODEV without a GPU. */
+int sfe_dsp_ofdmmod_create(int n_fft, int cp, int n_train, int n_data, const uint8_t *kind,
+                           const float *train, const float *pilot, const int8_t *pilot_sign,
+                           float amp, int order, int in_mode, int out_fmt, int device,
+                           sfe_ofdmmod_t *out);
+/* One stream of n_out samples holding n_bursts frames.  *n_written = n_out.  The placement
+ * refusals above; in_stride below what a burst reads is SFE_ERANGE; a null d_out, a null d_in with
+ * bursts, a cf32 d_out or a cf32 d_in (SYMBOLS mode) that is not 8-byte aligned (TX10 output and
+ * coded bytes need no alignment), an in_stride that takes the input's byte range to 2^62 and an
+ * output byte range that overlaps the input's are SFE_EINVAL; every refusal carries a message that
+ * starts with "ofdmmod_process_stream: " and nothing is launched.  n_out = 0 is a no-op.
+ * Asynchronous on `stream`; one kernel launch and nothing else: allocates nothing, does not
+ * synchronise the host, carries no state (there is no reset).  A handle has no setter, so a call
+ * on a stream under graph capture IS supported.  Behind sfe_dsp_ldpc_encode_stream its d_out and
+ * out_stride, behind sfe_dsp_ofdm_* its d_out and out_stride (a non-regenerative relay), are the
+ * whole glue. */
+int sfe_dsp_ofdmmod_process_stream(sfe_ofdmmod_t h, const void *d_in, size_t in_stride,
+                                   size_t n_bursts, int64_t start_base, int64_t start_step,
+                                   void *d_out, size_t n_out, size_t *n_written,
+                                   sfe_stream_t stream);
+int sfe_dsp_ofdmmod_destroy(sfe_ofdmmod_t h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,7 @@ Two layers, both thin:
     spatial covariance estimator (sfe_dsp_cov_*); `Mod`, the burst modulator (sfe_dsp_mod_*); `Polar`, the FM, phase and
     envelope detector (sfe_dsp_polar_*); `Occ`, the spectrum occupancy detector over a Psd's rows (sfe_dsp_occ_*);
     `Reed`, the interleaved Reed-Solomon outer code behind a Vit and in front of a Mod (sfe_dsp_reed_*); `Ofdm`, the OFDM burst
-    receiver behind a Corr (sfe_dsp_ofdm_*).
+    receiver behind a Corr (sfe_dsp_ofdm_*); `OfdmMod`, its transmit side, the OFDM burst modulator (sfe_dsp_ofdmmod_*).
 
 Everything computes on the GPU through the C ABI; numpy is only the host container.
 """
@@ -1900,6 +1900,97 @@ class Ofdm(_Block):
             for d in held:
                 d.free()
         return np.ascontiguousarray(sym), np.ascontiguousarray(ch), np.ascontiguousarray(rec), np.ascontiguousarray(st)
+
+
+def _ofdmmod_shape(n_fft, cp, n_train, n_data, kind, train, pilot, pilot_sign, amp, order, in_mode, out_fmt):
+    """(the leading arguments of sfe_dsp_ofdmmod_plan / _create, the arrays they point into)."""
+    head, keep, _nd = _ofdm_shape(n_fft, cp, 0, n_train, n_data, kind, train, pilot, pilot_sign, 0, 0, 0, 0.0)
+    return (head[0], head[1], *head[3:9], float(amp), int(order), int(in_mode), int(out_fmt)), keep
+
+
+def _ofdmmod_rows(data, symbols):
+    """The input of a call as (n_bursts, stride) rows: complex64 in SYMBOLS mode, uint8 in BITS mode."""
+    d = np.asarray(data, dtype=np.complex64 if symbols else np.uint8)
+    return np.ascontiguousarray(d.reshape(1, -1) if d.ndim == 1 else d)
+
+
+def ofdmmod_footprint(n_fft):
+    """sfe_dsp_ofdmmod_footprint (host only): (lanes of a symbol's workgroup, samples in no frame one workgroup writes, the
+    LDS bytes of a symbol's workgroup)."""
+    nt, zt, by = C.c_int(0), C.c_int(0), C.c_size_t(0)
+    check(_l.load().sfe_dsp_ofdmmod_footprint(int(n_fft), C.byref(nt), C.byref(zt), C.byref(by)))
+    return nt.value, zt.value, by.value
+
+
+def ofdmmod_plan(n_fft, cp, n_train, n_data, kind, train, pilot=None, pilot_sign=None, amp=1.0, order=4, in_mode=_l.OFDMMOD_IN_BITS,
+                 out_fmt=_l.FMT_F32, data=None, n_out=0, start_base=0, start_step=0, n_bursts=None):
+    """sfe_dsp_ofdmmod_plan (host only, no GPU): validates and, without data, returns (Nd data bins, F samples per frame, the
+    bytes -- BITS mode -- or cf32 symbols -- SYMBOLS mode -- a burst reads), after checking the placement too where n_out or
+    n_bursts is given.  With data -- (n_bursts, stride) uint8 coded bytes, MSB-first, or complex64 symbols -- it writes the
+    stream of n_out samples by the law: returns complex64 (n_out,), or the (n_out / 2) * 5 uint8 bytes of the transmit wire
+    format with FMT_TX10.  These are the device's bits.  Raises SfeError on arguments the block refuses."""
+    head, _alive = _ofdmmod_shape(n_fft, cp, n_train, n_data, kind, train, pilot, pilot_sign, amp, order, in_mode, out_fmt)
+    L, Nd, F, ni = _l.load(), C.c_int(0), C.c_int(0), C.c_size_t(0)
+    tail = (C.byref(Nd), C.byref(F), C.byref(ni))
+    if data is None:
+        check(L.sfe_dsp_ofdmmod_plan(*head, None, 0, int(n_bursts or 0), int(start_base), int(start_step), int(n_out), None, *tail))
+        return Nd.value, F.value, ni.value
+    d = _ofdmmod_rows(data, in_mode == _l.OFDMMOD_IN_SYMBOLS)
+    nb = d.shape[0] if n_bursts is None else int(n_bursts)
+    n_out = max(int(n_out), 0)
+    out = np.empty(n_out // 2 * 5, np.uint8) if out_fmt == _l.FMT_TX10 else np.empty(n_out, np.complex64)
+    check(L.sfe_dsp_ofdmmod_plan(*head, d.ctypes.data if d.size else None, d.shape[1] if d.size else 0, nb, int(start_base), int(start_step), n_out,
+                                 out.ctypes.data if out.size else None, *tail))
+    return out
+
+
+class OfdmMod(_Block):
+    """OFDM burst modulator (sfe_dsp_ofdmmod_*), the transmit side of Ofdm: per burst, a row of coded bytes on the device --
+    what Ldpc.encode_stream wrote, say -- or of cf32 symbols -- a row of Ofdm's output -- is mapped to the data bins of
+    n_data symbols behind n_train training symbols, transformed, given its cyclic prefixes and written as one frame of an
+    output stream, cf32 or (out_fmt FMT_TX10) the transmit wire format; every other sample of the stream is written as
+    zero.  The device's bits are ofdmmod_plan's."""
+    _prefix = "ofdmmod"
+
+    def __init__(self, n_fft, cp, n_train, n_data, kind, train, pilot=None, pilot_sign=None, amp=1.0, order=4, in_mode=_l.OFDMMOD_IN_BITS,
+                 out_fmt=_l.FMT_F32, device=0):
+        head, _alive = _ofdmmod_shape(n_fft, cp, n_train, n_data, kind, train, pilot, pilot_sign, amp, order, in_mode, out_fmt)
+        self.n_fft, self.cp, self.n_train, self.n_data = int(n_fft), int(cp), int(n_train), int(n_data)
+        self.order, self.in_mode, self.out_fmt = int(order), int(in_mode), int(out_fmt)
+        self._create(*head, device)
+        self.n_data_bins, self.frame_len, self.n_in = ofdmmod_plan(n_fft, cp, n_train, n_data, kind, train, pilot, pilot_sign, amp, order,
+                                                                   in_mode, out_fmt)
+        self.n_sym = self.n_data * self.n_data_bins         # data symbols of a burst
+        self.n_bytes = (self.n_sym * (2 if self.order == 4 else 1) + 7) // 8       # coded bytes of a burst in BITS mode
+
+    def process_stream(self, d_in, n_bursts, d_out, n_out, start_base=0, start_step=0, in_stride=None, stream=None):
+        """d_*: DeviceArray or raw device pointers.  Burst b reads n_bytes bytes (BITS mode) or n_sym cf32 (SYMBOLS mode) at
+        d_in + b*in_stride (bytes or cf32; default: what a burst reads) and its frame_len samples start at sample
+        start_base + b*start_step of the n_out samples at d_out (cf32, or 5-byte groups of two samples with FMT_TX10); the
+        call writes all n_out samples.  Returns n_out."""
+        k = C.c_size_t(0)
+        check(self._fn("process_stream")(self._h, self._ptr(d_in), self.n_in if in_stride is None else int(in_stride), int(n_bursts),
+                                         int(start_base), int(start_step), self._ptr(d_out), int(n_out), C.byref(k), stream))
+        return k.value
+
+    def reset(self):
+        raise AttributeError("OfdmMod has no reset: it carries no state")
+
+    def modulate(self, data, n_out, start_base=0, start_step=0):
+        """Host convenience, computed on the GPU: data is (n_bursts, stride) uint8 coded bytes or complex64 symbols; returns
+        what ofdmmod_plan returns."""
+        symbols = self.in_mode == _l.OFDMMOD_IN_SYMBOLS
+        d = _ofdmmod_rows(data, symbols)
+        tx10 = self.out_fmt == _l.FMT_TX10
+        nbytes = int(n_out) // 2 * 5 if tx10 else 8 * int(n_out)
+        held = [DeviceArray.from_numpy(d.view(np.float32).ravel()) if symbols else DeviceArray.from_bytes(d), DeviceArray(max(1, (nbytes + 3) // 4))]
+        try:
+            self.process_stream(held[0], d.shape[0], held[1], n_out, start_base, start_step, in_stride=d.shape[1])
+            raw = held[1].to_numpy().view(np.uint8)[:nbytes]
+        finally:
+            for x in held:
+                x.free()
+        return np.ascontiguousarray(raw) if tx10 else np.ascontiguousarray(raw).view(np.complex64)
 
 
 def rs_plan(state, upsample, n_in, out_len, rate):

@@ -24,6 +24,7 @@ REED_OK, REED_UNCORRECTABLE, REED_UPSTREAM = 0, 1, 2 # sfe_dsp_reed_*: a frame's
 LDPC_OK, LDPC_NOT_FINITE, LDPC_UPSTREAM, LDPC_NOT_CONVERGED = 0, 1, 2, 3     # sfe_dsp_ldpc_*: a codeword's status
 OFDM_OUT_ZF, OFDM_OUT_MRC = 0, 1                     # sfe_dsp_ofdm_*: out_mode
 OFDM_OK, OFDM_NO_ESTIMATE, OFDM_GATED, OFDM_OUT_OF_RANGE = 0, 1, 2, 3        # sfe_dsp_ofdm_*: a burst's status
+OFDMMOD_IN_BITS, OFDMMOD_IN_SYMBOLS = 0, 1           # sfe_dsp_ofdmmod_*: in_mode
 
 
 class TimeState(C.Structure):
@@ -224,6 +225,12 @@ SIGNATURES = {
     "sfe_dsp_ofdm_set_input_format": (i32, [vp, i32]),
     "sfe_dsp_ofdm_process_stream": (i32, [vp, vp, sz, sz, vp, sz, vp, sz, sz, C.c_int64, C.c_int64, vp, sz, vp, vp, vp, sz, C.POINTER(sz), vp]),
     "sfe_dsp_ofdm_destroy": (i32, [vp]),
+    "sfe_dsp_ofdmmod_footprint": (i32, [i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(sz)]),
+    "sfe_dsp_ofdmmod_plan": (i32, [i32, i32, i32, i32, vp, fp, fp, vp, f32, i32, i32, i32, vp, sz, sz, C.c_int64, C.c_int64, sz, vp,
+                                   C.POINTER(i32), C.POINTER(i32), C.POINTER(sz)]),
+    "sfe_dsp_ofdmmod_create": (i32, [i32, i32, i32, i32, vp, fp, fp, vp, f32, i32, i32, i32, i32, C.POINTER(vp)]),
+    "sfe_dsp_ofdmmod_process_stream": (i32, [vp, vp, sz, sz, C.c_int64, C.c_int64, vp, sz, C.POINTER(sz), vp]),
+    "sfe_dsp_ofdmmod_destroy": (i32, [vp]),
 }
 
 # the diagnostic library only (simplefe_amd/csrc/diag/sfe_dsp_diag.h; scripts/ load it by pointing LIB_PATH at it): bound when present
