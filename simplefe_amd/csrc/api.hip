@@ -34,13 +34,6 @@ int device_cu_count()
     return c;
 }
 
-// [a, a + an) and [b, b + bn) share a byte
-bool ranges_overlap(const void *a, size_t an, const void *b, size_t bn)
-{
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return an && bn && pa < pb + bn && pb < pa + an;
-}
-
 int use_device(int device)
 {
     int n = 0;

@@ -142,13 +142,7 @@ int sfe_dsp_beam_create(const float *weights, const float *weights_conj, int n_i
 
 int sfe_dsp_beam_set_input_format(sfe_beam_t h, int fmt)
 {
-    Beam *p = as_beam(h);
-    if (!p || (fmt != SFE_FMT_F32 && fmt != SFE_FMT_U8)) {
-        set_error("beam_set_input_format: null handle or a format other than SFE_FMT_F32 / SFE_FMT_U8");
-        return SFE_EINVAL;
-    }
-    p->in_u8 = fmt == SFE_FMT_U8;
-    return SFE_OK;
+    return set_format(as_beam(h), "beam_set_input_format", fmt, SFE_FMT_U8, "SFE_FMT_U8", &Beam::in_u8);
 }
 
 int sfe_dsp_beam_set_weights(sfe_beam_t h, const float *weights, const float *weights_conj)

@@ -80,19 +80,6 @@ int burst_check(const float *pre, int Lp, int sps, int N, int lag, int timing_mo
     return SFE_OK;
 }
 
-// o = start_base + b start_step + idx, then o - sps, must not leave int64 for any b < n_bursts and any uint32 idx: the sum is
-// linear in b, so its two ends decide.  `who` is the message prefix.
-int burst_check_starts(const char *who, int64_t start_base, int64_t start_step, size_t n_bursts)
-{
-    const __int128 room = ((__int128)1 << 63) - ((__int128)1 << 33);
-    const __int128 last = (__int128)start_base + (__int128)(n_bursts - 1) * start_step;
-    if (start_base < -room || start_base > room || last < -room || last > room) {
-        set_error("%s: start_base + b * start_step must stay within +-(2^63 - 2^33) for every burst", who);
-        return SFE_EINVAL;
-    }
-    return SFE_OK;
-}
-
 bool usable(double re, double im) { return std::isfinite(re) && std::isfinite(im) && (re != 0.0 || im != 0.0); }
 
 void unturn(double t, double *c, double *s)     // exp(-j 2 pi t) as (c, s)
@@ -223,7 +210,7 @@ int sfe_dsp_burst_plan(const float *preamble, int n_pre, int sps, int n_sym, int
         set_error("burst: n_bursts = %zu must be below 2^31", n_bursts);
         return SFE_EINVAL;
     }
-    const int rs = burst_check_starts("burst", start_base, start_step, n_bursts);
+    const int rs = check_starts("burst", start_base, start_step, n_bursts);
     if (rs != SFE_OK) return rs;
     const long long reach = ((long long)n_sym + 2) * sps;
     for (size_t b = 0; b < n_bursts; b++) {
@@ -280,13 +267,7 @@ int sfe_dsp_burst_create(const float *preamble, int n_pre, int sps, int n_sym, i
 
 int sfe_dsp_burst_set_input_format(sfe_burst_t h, int fmt)
 {
-    Burst *p = as_burst(h);
-    if (!p || (fmt != SFE_FMT_F32 && fmt != SFE_FMT_U8)) {
-        set_error("burst_set_input_format: null handle or a format other than SFE_FMT_F32 / SFE_FMT_U8");
-        return SFE_EINVAL;
-    }
-    p->in_u8 = fmt == SFE_FMT_U8;
-    return SFE_OK;
+    return set_format(as_burst(h), "burst_set_input_format", fmt, SFE_FMT_U8, "SFE_FMT_U8", &Burst::in_u8);
 }
 
 int sfe_dsp_burst_set_gate(sfe_burst_t h, float min_gate)
@@ -306,44 +287,11 @@ int sfe_dsp_burst_process_stream(sfe_burst_t h, const void *d_in, size_t n_in, s
     static const char who[] = "burst_process_stream";
     Burst *p = stream_handle(as_burst(h), who, n_out);
     if (!p) return SFE_EINVAL;
-    int rc = refuse_2_31(who, n_in);
-    if (rc != SFE_OK) return rc;
-    const size_t S = (size_t)p->n_streams, N = (size_t)p->N;
-    if (n_bursts >= ((size_t)1 << 31) / S) {
-        set_error("burst_process_stream: n_streams * n_bursts = %zu * %zu must be below 2^31 per call", S, n_bursts);
-        return SFE_EINVAL;
-    }
-    if (n_bursts == 0) return SFE_OK;
-    if ((rc = refuse_null(who, {d_in, d_out})) != SFE_OK) return rc;
-    if (out_stride < N || (d_status && status_stride < n_bursts)) {
-        set_error("burst_process_stream: out_stride %zu < n_sym = %zu or status_stride %zu < n_bursts = %zu", out_stride, N, status_stride,
-                  n_bursts);
-        return SFE_ERANGE;
-    }
-    if (S > 1 && in_stride < n_in) {
-        set_error("burst_process_stream: in_stride %zu < n_in %zu with %d streams", in_stride, n_in, p->n_streams);
-        return SFE_EINVAL;
-    }
-    if ((rc = burst_check_starts(who, start_base, start_step, n_bursts)) != SFE_OK) return rc;
-    const size_t isz = p->in_u8 ? 2 : 8, rows = S * n_bursts;
-    size_t in_b = 0, ix_b = 0, ga_b = 0, ou_b = 0, st_b = 0;
-    if (!span_bytes(S - 1, in_stride, n_in, isz, &in_b) || (d_idx && !span_bytes(S - 1, idx_stride, n_bursts, 4, &ix_b)) ||
-        (d_gate && !span_bytes(S - 1, gate_stride, n_bursts, 4, &ga_b)) || !span_bytes(rows - 1, out_stride, N, 8, &ou_b) ||
-        (d_status && !span_bytes(S - 1, status_stride, n_bursts, 4, &st_b))) {
-        set_error("burst_process_stream: a stride is so large that its buffer's byte range reaches 2^62");
-        return SFE_EINVAL;
-    }
-    const Span in{d_in, in_b, isz}, ix{d_idx, ix_b, 4}, ga{d_gate, ga_b, 4}, ou{d_out, ou_b, 8};
-    const Span re{d_rec, d_rec ? rows * BURST_REC * 4 : 0, 4}, st{d_status, st_b, 4};
-    if ((rc = refuse_misaligned(who, "cf32 8 B, u8 (I,Q) pairs 2 B, indices, gates, records and statuses 4 B", {in, ix, ga, ou, re, st})) != SFE_OK ||
-        (rc = refuse_overlap(who, in, {ou, re, st})) != SFE_OK || (rc = refuse_overlap(who, ix, {ou, re, st})) != SFE_OK ||
-        (rc = refuse_overlap(who, ga, {ou, re, st})) != SFE_OK)
-        return rc;
-    if (ranges_overlap(ou.p, ou.bytes, re.p, re.bytes) || ranges_overlap(ou.p, ou.bytes, st.p, st.bytes) ||
-        ranges_overlap(re.p, re.bytes, st.p, st.bytes)) {
-        set_error("burst_process_stream: the output ranges overlap one another");
-        return SFE_EINVAL;
-    }
+    bool go;
+    int rc = check_windows(who, "n_sym", (size_t)p->n_streams, p->in_u8 ? 2 : 8, d_in, n_in, in_stride, d_idx, idx_stride, d_gate, gate_stride,
+                           n_bursts, start_base, start_step, d_out, out_stride, (size_t)p->N, nullptr, 0, d_rec, BURST_REC, d_status,
+                           status_stride, &go);
+    if (rc != SFE_OK || !go) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (stream_is_capturing(s)) {       // set_gate may change what a captured call would have pinned
         set_error("burst_process_stream: graph capture is not supported (set_gate may change the gate a captured call would have pinned)");

@@ -101,13 +101,7 @@ int sfe_dsp_chan_create(const float *taps, int n_taps, int n_chans, int decim, i
 
 int sfe_dsp_chan_set_input_format(sfe_chan_t h, int fmt)
 {
-    Chan *c = as_chan(h);
-    if (!c || (fmt != SFE_FMT_F32 && fmt != SFE_FMT_U8)) {
-        set_error("chan_set_input_format: null handle or a format other than SFE_FMT_F32 / SFE_FMT_U8");
-        return SFE_EINVAL;
-    }
-    c->in_u8 = fmt == SFE_FMT_U8;
-    return SFE_OK;
+    return set_format(as_chan(h), "chan_set_input_format", fmt, SFE_FMT_U8, "SFE_FMT_U8", &Chan::in_u8);
 }
 
 int sfe_dsp_chan_process_stream(sfe_chan_t h, const void *d_in, size_t n_in, size_t in_stride, void *d_out, size_t out_stride,

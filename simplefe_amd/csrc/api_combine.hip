@@ -106,13 +106,7 @@ int sfe_dsp_combine_create(const float *taps, int n_taps, int n_chans, int inter
 
 int sfe_dsp_combine_set_output_format(sfe_combine_t h, int fmt)
 {
-    Combiner *c = as_combiner(h);
-    if (!c || (fmt != SFE_FMT_F32 && fmt != SFE_FMT_TX10)) {
-        set_error("combine_set_output_format: null handle or a format other than SFE_FMT_F32 / SFE_FMT_TX10");
-        return SFE_EINVAL;
-    }
-    c->out_tx10 = fmt == SFE_FMT_TX10;
-    return SFE_OK;
+    return set_format(as_combiner(h), "combine_set_output_format", fmt, SFE_FMT_TX10, "SFE_FMT_TX10", &Combiner::out_tx10);
 }
 
 int sfe_dsp_combine_process_stream(sfe_combine_t h, const void *d_in, size_t n_in, size_t in_stride, void *d_out, size_t out_stride,

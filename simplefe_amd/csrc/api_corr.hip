@@ -156,13 +156,7 @@ int sfe_dsp_corr_create(const float *templates, int len, int n_templates, int bl
 
 int sfe_dsp_corr_set_input_format(sfe_corr_t h, int fmt)
 {
-    Corr *p = as_corr(h);
-    if (!p || (fmt != SFE_FMT_F32 && fmt != SFE_FMT_U8)) {
-        set_error("corr_set_input_format: null handle or a format other than SFE_FMT_F32 / SFE_FMT_U8");
-        return SFE_EINVAL;
-    }
-    p->in_u8 = fmt == SFE_FMT_U8;
-    return SFE_OK;
+    return set_format(as_corr(h), "corr_set_input_format", fmt, SFE_FMT_U8, "SFE_FMT_U8", &Corr::in_u8);
 }
 
 int sfe_dsp_corr_process_stream(sfe_corr_t h, const void *d_in, size_t n_in, size_t in_stride, void *d_peak_val, void *d_peak_idx,
@@ -199,13 +193,8 @@ int sfe_dsp_corr_process_stream(sfe_corr_t h, const void *d_in, size_t n_in, siz
     const size_t met_b = d_metric ? ((rows - 1) * metric_stride + n_in) * 4 : 0;
     const Span in{d_in, in_b, isz}, val{d_peak_val, peak_b, 4}, idx{d_peak_idx, peak_b, 4}, met{d_metric, met_b, 4};
     if ((rc = refuse_misaligned(who, "cf32 8 B, u8 (I,Q) pairs 2 B, outputs 4 B", {in, val, idx, met})) != SFE_OK ||
-        (rc = refuse_overlap(who, in, {val, idx, met})) != SFE_OK)
+        (rc = refuse_overlap(who, in, {val, idx, met})) != SFE_OK || (rc = refuse_outputs_overlap(who, {val, idx, met})) != SFE_OK)
         return rc;
-    if (ranges_overlap(d_peak_val, peak_b, d_peak_idx, peak_b) ||
-        (met_b && (ranges_overlap(d_metric, met_b, d_peak_val, peak_b) || ranges_overlap(d_metric, met_b, d_peak_idx, peak_b)))) {
-        set_error("corr_process_stream: the output ranges overlap one another");
-        return SFE_EINVAL;
-    }
     hipStream_t s = (hipStream_t)stream;
     rc = refuse_capture(who, "sample", s);
     if (rc != SFE_OK) return rc;

@@ -91,13 +91,7 @@ int sfe_dsp_cov_create(int n_in_streams, int n_bands, int n_avg, float scale, in
 
 int sfe_dsp_cov_set_input_format(sfe_cov_t h, int fmt)
 {
-    Cov *p = as_cov(h);
-    if (!p || (fmt != SFE_FMT_F32 && fmt != SFE_FMT_U8)) {
-        set_error("cov_set_input_format: null handle or a format other than SFE_FMT_F32 / SFE_FMT_U8");
-        return SFE_EINVAL;
-    }
-    p->in_u8 = fmt == SFE_FMT_U8;
-    return SFE_OK;
+    return set_format(as_cov(h), "cov_set_input_format", fmt, SFE_FMT_U8, "SFE_FMT_U8", &Cov::in_u8);
 }
 
 int sfe_dsp_cov_process_stream(sfe_cov_t h, const void *d_in, size_t n_in, size_t in_stride, void *d_out, size_t out_stride,

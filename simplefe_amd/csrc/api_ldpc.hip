@@ -103,43 +103,9 @@ LdpcArgs ldpc_args(const Ldpc &p)
     return a;
 }
 
-// The checks the two stream calls share: `in_row` elements of `esz` bytes are read and `out_row` bytes written per codeword.
-// SFE_OK with *go = false: nothing to do.
-int ldpc_stream_checks(const char *who, size_t n_words, const void *d_in, size_t in_stride, size_t in_row, size_t esz, const void *d_status_in,
-                       void *d_out, size_t out_stride, size_t out_row, void *d_rec, void *d_status, bool *go)
-{
-    *go = false;
-    if (n_words >= ((size_t)1 << 31)) {
-        set_error("%s: n_words = %zu must be below 2^31 per call", who, n_words);
-        return SFE_EINVAL;
-    }
-    if (n_words == 0) return SFE_OK;
-    int rc = refuse_null(who, {d_in, d_out});
-    if (rc != SFE_OK) return rc;
-    if (in_stride < in_row || out_stride < out_row) {
-        set_error("%s: in_stride %zu < the %zu elements read per codeword, or out_stride %zu < the %zu bytes written per codeword", who, in_stride,
-                  in_row, out_stride, out_row);
-        return SFE_ERANGE;
-    }
-    size_t in_b = 0, ou_b = 0;
-    if (!span_bytes(n_words - 1, in_stride, in_row, esz, &in_b) || !span_bytes(n_words - 1, out_stride, out_row, 1, &ou_b)) {
-        set_error("%s: a stride is so large that its buffer's byte range reaches 2^62", who);
-        return SFE_EINVAL;
-    }
-    const Span in{d_in, in_b, esz}, si{d_status_in, d_status_in ? n_words * 4 : 0, 4}, ou{d_out, ou_b, 1};
-    const Span re{d_rec, d_rec ? n_words * 12 : 0, 4}, st{d_status, d_status ? n_words * 4 : 0, 4};
-    if ((rc = refuse_misaligned(who, "soft values 4 B, symbols 8 B, records and statuses 4 B; payloads and codewords need none", {in, si, re, st})) !=
-            SFE_OK ||
-        (rc = refuse_overlap(who, in, {ou, re, st})) != SFE_OK || (rc = refuse_overlap(who, si, {ou, re, st})) != SFE_OK)
-        return rc;
-    if (ranges_overlap(ou.p, ou.bytes, re.p, re.bytes) || ranges_overlap(ou.p, ou.bytes, st.p, st.bytes) ||
-        ranges_overlap(re.p, re.bytes, st.p, st.bytes)) {
-        set_error("%s: the output ranges overlap one another", who);
-        return SFE_EINVAL;
-    }
-    *go = true;
-    return SFE_OK;
-}
+// the stream calls' words for check_rows (call_checks.h); a record is 12 bytes
+constexpr RowNouns LDPC_NOUNS{"n_words", "elements read per codeword", "the ", " bytes written per codeword",
+                              "soft values 4 B, symbols 8 B, records and statuses 4 B; payloads and codewords need none", 12};
 
 }  // namespace
 }  // namespace sfe
@@ -255,8 +221,8 @@ int sfe_dsp_ldpc_encode_stream(sfe_ldpc_t h, const void *d_payload, size_t in_st
         return SFE_ESTATE;
     }
     bool go;
-    int rc = ldpc_stream_checks(who, n_words, d_payload, in_stride, (size_t)p->code->k_bytes(), 1, nullptr, d_code, out_stride,
-                                (size_t)p->code->n_bytes(), nullptr, nullptr, &go);
+    int rc = check_rows(who, LDPC_NOUNS, n_words, d_payload, in_stride, (size_t)p->code->k_bytes(), 1, nullptr, d_code, out_stride,
+                        (size_t)p->code->n_bytes(), nullptr, nullptr, &go);
     if (rc != SFE_OK || !go) return rc;
     SFE_ON_DEVICE(p->device);
     LdpcArgs a = ldpc_args(*p);
@@ -276,8 +242,8 @@ int sfe_dsp_ldpc_process_stream(sfe_ldpc_t h, const void *d_in, size_t in_stride
     if (!p) return SFE_EINVAL;
     const LdpcParams &par = p->par;
     bool go;
-    int rc = ldpc_stream_checks(who, n_words, d_in, in_stride, par.row_elems(p->code->n), 4 * (size_t)par.elem_floats(), d_status_in, d_bits,
-                                out_stride, (size_t)p->code->k_bytes(), d_rec, d_status, &go);
+    int rc = check_rows(who, LDPC_NOUNS, n_words, d_in, in_stride, par.row_elems(p->code->n), 4 * (size_t)par.elem_floats(), d_status_in, d_bits,
+                        out_stride, (size_t)p->code->k_bytes(), d_rec, d_status, &go);
     if (rc != SFE_OK || !go) return rc;
     SFE_ON_DEVICE(p->device);
     LdpcArgs a = ldpc_args(*p);

@@ -2,13 +2,13 @@
 // kernel is in mod.hip.  Here: the checks, and the host twin of the kernel's law (sfe_dsp_mod_plan: the reference of the
 // device's bits -- a sequential encoder, the symbol map, and the same fmaf chains in the same order, every skipped term
 // skipped literally).
-#include <climits>
 #include <cmath>
 #include <cstring>
 
 #include "host.h"
 #include "block.h"
 #include "mod.h"
+#include "ofdmmod_law.h"
 #include "vit_code.h"
 
 namespace sfe {
@@ -91,34 +91,6 @@ int mod_check(int K, int n_gen, const uint32_t *gen, const uint8_t *keep, int P,
     return SFE_OK;
 }
 
-// where the frames lie in the stream
-int mod_check_place(const char *who, const ModShape &m, size_t n_bursts, int64_t start_base, int64_t start_step, size_t n_out)
-{
-    if (n_out >= ((size_t)1 << 31) || n_bursts >= ((size_t)1 << 31)) {
-        set_error("%s: n_out = %zu and n_bursts = %zu must be below 2^31", who, n_out, n_bursts);
-        return SFE_EINVAL;
-    }
-    if (m.tx10 && (n_out & 1)) {
-        set_error("%s: n_out = %zu must be even with SFE_FMT_TX10 (whole 5-byte groups)", who, n_out);
-        return SFE_EINVAL;
-    }
-    if (n_bursts == 0) return SFE_OK;
-    if (start_base < 0) {
-        set_error("%s: start_base = %lld must not be negative", who, (long long)start_base);
-        return SFE_EINVAL;
-    }
-    if (n_bursts > 1 && start_step < m.F) {
-        set_error("%s: start_step = %lld is below the frame's F = %d samples (frames must not overlap)", who, (long long)start_step, m.F);
-        return SFE_EINVAL;
-    }
-    const __int128 end = (__int128)start_base + (__int128)(n_bursts - 1) * (n_bursts > 1 ? start_step : 0) + m.F;
-    if (end > (__int128)n_out) {
-        set_error("%s: the last frame ends behind the stream's n_out = %zu samples", who, n_out);
-        return SFE_EINVAL;
-    }
-    return SFE_OK;
-}
-
 // the symbols of one burst by the law: a sequential encoder, then the map
 void mod_symbols_host(const ModShape &m, const uint8_t *row, std::vector<v2f> &s)
 {
@@ -159,18 +131,6 @@ void mod_frame_host(const ModShape &m, const std::vector<v2f> &s, v2f *y)
             }
             y[(size_t)k * m.sps + r] = v2f{ax, ay};
         }
-}
-
-// the quantiser of sfe_dsp_tx_f32_to_10bit, with the device's saturating conversion
-unsigned mod_q10_host(float x)
-{
-    const float p = x * 511.0f;
-    int v;
-    if (p != p) v = 0;
-    else if (p >= 2147483648.0f) v = INT_MAX;
-    else if (p <= -2147483648.0f) v = INT_MIN;
-    else v = (int)p;
-    return (unsigned)((int)(short)v + 512) & 0x3FFu;
 }
 
 struct Mod {
@@ -214,7 +174,7 @@ int sfe_dsp_mod_plan(int K, int n_gen, const uint32_t *gen, const uint8_t *keep,
     if (n_sym) *n_sym = m.N;
     if (frame_len) *frame_len = m.F;
     if (n_soft) *n_soft = (size_t)m.code.n_soft;
-    if ((rc = mod_check_place("mod", m, n_bursts, start_base, start_step, n_out)) != SFE_OK) return rc;
+    if ((rc = check_place("mod", m.F, m.tx10, false, n_bursts, start_base, start_step, n_out)) != SFE_OK) return rc;
     if (n_bursts > 0) {
         if (!bytes) {
             set_error("mod: null bytes with bursts to modulate");
@@ -237,15 +197,9 @@ int sfe_dsp_mod_plan(int K, int n_gen, const uint32_t *gen, const uint8_t *keep,
         mod_symbols_host(m, bytes + b * in_stride, s);
         mod_frame_host(m, s, y + start_base + (int64_t)b * (n_bursts > 1 ? start_step : 0));
     }
-    if (m.tx10) {
-        uint8_t *o = static_cast<uint8_t *>(out);
-        for (size_t g = 0; g < n_out / 2; g++, o += 5) {
-            const unsigned u0 = mod_q10_host(y[2 * g].x), u1 = mod_q10_host(y[2 * g].y), u2 = mod_q10_host(y[2 * g + 1].x),
-                           u3 = mod_q10_host(y[2 * g + 1].y);
-            o[0] = (uint8_t)((u0 >> 8) | ((u1 >> 8) << 2) | ((u2 >> 8) << 4) | ((u3 >> 8) << 6));
-            o[1] = (uint8_t)u0, o[2] = (uint8_t)u1, o[3] = (uint8_t)u2, o[4] = (uint8_t)u3;
-        }
-    }
+    // the wire format's law is ofdmmod_law.h's: the same quantiser, the same groups; omc is v2f's layout
+    static_assert(sizeof(omc) == sizeof(v2f) && alignof(omc) == alignof(v2f), "om_tx10_host reads v2f samples");
+    if (m.tx10) om_tx10_host(reinterpret_cast<const omc *>(y), n_out, static_cast<uint8_t *>(out));
     return SFE_OK;
 }
 
@@ -276,23 +230,10 @@ int sfe_dsp_mod_process_stream(sfe_mod_t h, const void *d_bytes, size_t in_strid
     Mod *p = stream_handle(as_mod(h), who, n_written, "n_written");
     if (!p) return SFE_EINVAL;
     const ModShape &m = p->shape;
-    int rc = mod_check_place(who, m, n_bursts, start_base, start_step, n_out);
-    if (rc != SFE_OK) return rc;
-    if (n_out == 0) return SFE_OK;
-    if ((rc = refuse_null(who, {d_out})) != SFE_OK || (n_bursts && (rc = refuse_null(who, {d_bytes})) != SFE_OK)) return rc;
-    if (n_bursts && in_stride < m.nbytes()) {
-        set_error("mod_process_stream: in_stride %zu < ceil(n_info / 8) = %zu", in_stride, m.nbytes());
-        return SFE_ERANGE;
-    }
-    size_t in_b = 0;
-    if (n_bursts && !span_bytes(n_bursts - 1, in_stride, m.nbytes(), 1, &in_b)) {
-        set_error("mod_process_stream: in_stride is so large that the payloads' byte range reaches 2^62");
-        return SFE_EINVAL;
-    }
-    const Span in{d_bytes, in_b, 1}, ou{d_out, m.tx10 ? n_out / 2 * 5 : n_out * sizeof(v2f), m.tx10 ? (size_t)1 : sizeof(v2f)};
-    if ((rc = refuse_misaligned(who, "cf32 output 8 B; TX10 output and payload bytes need none", {ou})) != SFE_OK ||
-        (rc = refuse_overlap(who, in, {ou})) != SFE_OK)
-        return rc;
+    static const FrameNouns nouns{"ceil(n_info / 8) = ", "", "payloads'", "cf32 output 8 B; TX10 output and payload bytes need none"};
+    bool go;
+    int rc = check_frames(who, nouns, m.F, m.tx10, false, d_bytes, in_stride, m.nbytes(), 1, n_bursts, start_base, start_step, d_out, n_out, &go);
+    if (rc != SFE_OK || !go) return rc;
     const long long nb = (long long)n_bursts;
     const long long last_end = nb ? start_base + (nb - 1) * (nb > 1 ? start_step : 0) + m.F : 0;
     ModArgs a{};

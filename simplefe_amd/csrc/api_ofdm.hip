@@ -104,19 +104,6 @@ int ofdm_check(int n_fft, int cp, int advance, int n_train, int n_data, const ui
     return SFE_OK;
 }
 
-// o = start_base + b start_step + idx must not leave int64 for any b < n_bursts and any uint32 idx: the sum is linear in
-// b, so its two ends decide.  `who` is the message prefix.
-int ofdm_check_starts(const char *who, int64_t start_base, int64_t start_step, size_t n_bursts)
-{
-    const __int128 room = ((__int128)1 << 63) - ((__int128)1 << 33);
-    const __int128 last = (__int128)start_base + (__int128)(n_bursts - 1) * start_step;
-    if (start_base < -room || start_base > room || last < -room || last > room) {
-        set_error("%s: start_base + b * start_step must stay within +-(2^63 - 2^33) for every burst", who);
-        return SFE_EINVAL;
-    }
-    return SFE_OK;
-}
-
 bool usable(double re, double im) { return std::isfinite(re) && std::isfinite(im) && (re != 0.0 || im != 0.0); }
 
 // in-place radix-2 transform of N = 2^logn points, exp(-j 2 pi k n / N), every twiddle from cos and sin in float64
@@ -268,7 +255,7 @@ int sfe_dsp_ofdm_plan(int n_fft, int cp, int advance, int n_train, int n_data, c
     if (!symbols) OFDM_REFUSE("ofdm: null symbols with samples to receive");
     if (n_in >= ((size_t)1 << 31)) OFDM_REFUSE("ofdm: n_in = %zu must be below 2^31", n_in);
     if (n_bursts >= ((size_t)1 << 31)) OFDM_REFUSE("ofdm: n_bursts = %zu must be below 2^31", n_bursts);
-    const int rs = ofdm_check_starts("ofdm", start_base, start_step, n_bursts);
+    const int rs = check_starts("ofdm", start_base, start_step, n_bursts);
     if (rs != SFE_OK) return rs;
     const int N = sh.N;
     std::vector<double> wr(N / 2), wi(N / 2);
@@ -314,13 +301,8 @@ int sfe_dsp_ofdm_create(int n_fft, int cp, int advance, int n_train, int n_data,
 
 int sfe_dsp_ofdm_set_input_format(sfe_ofdm_t h, int fmt)
 {
-    Ofdm *p = as_ofdm(h);
-    if (!p || (fmt != SFE_FMT_F32 && fmt != SFE_FMT_U8)) {
-        set_error("ofdm_set_input_format: null handle or a format other than SFE_FMT_F32 / SFE_FMT_U8");
-        return SFE_EINVAL;
-    }
-    p->in_u8 = fmt == SFE_FMT_U8;       // a call takes it by value when it is enqueued
-    return SFE_OK;
+    // a call takes it by value when it is enqueued
+    return set_format(as_ofdm(h), "ofdm_set_input_format", fmt, SFE_FMT_U8, "SFE_FMT_U8", &Ofdm::in_u8);
 }
 
 int sfe_dsp_ofdm_process_stream(sfe_ofdm_t h, const void *d_in, size_t n_in, size_t in_stride, const void *d_idx, size_t idx_stride,
@@ -331,47 +313,12 @@ int sfe_dsp_ofdm_process_stream(sfe_ofdm_t h, const void *d_in, size_t n_in, siz
     static const char who[] = "ofdm_process_stream";
     Ofdm *p = stream_handle(as_ofdm(h), who, n_out);
     if (!p) return SFE_EINVAL;
-    int rc = refuse_2_31(who, n_in);
-    if (rc != SFE_OK) return rc;
     const OfdmShape &sh = p->sh;
-    const size_t S = (size_t)p->n_streams, N = (size_t)sh.N, row = (size_t)sh.Ns * sh.Nd;
-    if (n_bursts >= ((size_t)1 << 31) / S) {
-        set_error("ofdm_process_stream: n_streams * n_bursts = %zu * %zu must be below 2^31 per call", S, n_bursts);
-        return SFE_EINVAL;
-    }
-    if (n_bursts == 0) return SFE_OK;
-    if ((rc = refuse_null(who, {d_in, d_out})) != SFE_OK) return rc;
-    if (out_stride < row || (d_status && status_stride < n_bursts)) {
-        set_error("ofdm_process_stream: out_stride %zu < n_data * Nd = %zu or status_stride %zu < n_bursts = %zu", out_stride, row,
-                  status_stride, n_bursts);
-        return SFE_ERANGE;
-    }
-    if (S > 1 && in_stride < n_in) {
-        set_error("ofdm_process_stream: in_stride %zu < n_in %zu with %d streams", in_stride, n_in, p->n_streams);
-        return SFE_EINVAL;
-    }
-    if ((rc = ofdm_check_starts(who, start_base, start_step, n_bursts)) != SFE_OK) return rc;
-    const size_t isz = p->in_u8 ? 2 : 8, rows = S * n_bursts;
-    size_t in_b = 0, ix_b = 0, ga_b = 0, ou_b = 0, st_b = 0;
-    if (!span_bytes(S - 1, in_stride, n_in, isz, &in_b) || (d_idx && !span_bytes(S - 1, idx_stride, n_bursts, 4, &ix_b)) ||
-        (d_gate && !span_bytes(S - 1, gate_stride, n_bursts, 4, &ga_b)) || !span_bytes(rows - 1, out_stride, row, 8, &ou_b) ||
-        (d_status && !span_bytes(S - 1, status_stride, n_bursts, 4, &st_b))) {
-        set_error("ofdm_process_stream: a stride is so large that its buffer's byte range reaches 2^62");
-        return SFE_EINVAL;
-    }
-    const Span in{d_in, in_b, isz}, ix{d_idx, ix_b, 4}, ga{d_gate, ga_b, 4}, ou{d_out, ou_b, 8}, ch{d_chan, d_chan ? rows * N * 8 : 0, 8};
-    const Span re{d_rec, d_rec ? rows * OFDM_REC * 4 : 0, 4}, st{d_status, st_b, 4};
-    if ((rc = refuse_misaligned(who, "cf32 8 B, u8 (I,Q) pairs 2 B, indices, gates, records and statuses 4 B", {in, ix, ga, ou, ch, re, st})) != SFE_OK ||
-        (rc = refuse_overlap(who, in, {ou, ch, re, st})) != SFE_OK || (rc = refuse_overlap(who, ix, {ou, ch, re, st})) != SFE_OK ||
-        (rc = refuse_overlap(who, ga, {ou, ch, re, st})) != SFE_OK)
-        return rc;
-    const Span outs[4] = {ou, ch, re, st};
-    for (int i = 0; i < 4; i++)
-        for (int j = i + 1; j < 4; j++)
-            if (ranges_overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes)) {
-                set_error("ofdm_process_stream: the output ranges overlap one another");
-                return SFE_EINVAL;
-            }
+    bool go;
+    int rc = check_windows(who, "n_data * Nd", (size_t)p->n_streams, p->in_u8 ? 2 : 8, d_in, n_in, in_stride, d_idx, idx_stride, d_gate,
+                           gate_stride, n_bursts, start_base, start_step, d_out, out_stride, (size_t)sh.Ns * sh.Nd, d_chan, (size_t)sh.N, d_rec,
+                           OFDM_REC, d_status, status_stride, &go);
+    if (rc != SFE_OK || !go) return rc;
     SFE_ON_DEVICE(p->device);
     const OfdmArgs a{d_in, static_cast<const unsigned *>(d_idx), static_cast<const float *>(d_gate), p->d_tw, p->d_c, p->d_pilot, p->d_sign,
                      p->d_bins, static_cast<v2f *>(d_out), static_cast<v2f *>(d_chan), static_cast<float *>(d_rec), static_cast<int *>(d_status),

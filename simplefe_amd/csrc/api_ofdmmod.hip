@@ -89,39 +89,6 @@ int omod_check(int n_fft, int cp, int n_train, int n_data, const uint8_t *kind, 
     return SFE_OK;
 }
 
-// where the frames lie in the stream: mod's rules, and whole groups under TX10
-int omod_check_place(const char *who, const OmodShape &m, size_t n_bursts, int64_t start_base, int64_t start_step, size_t n_out)
-{
-    if (n_out >= ((size_t)1 << 31) || n_bursts >= ((size_t)1 << 31)) {
-        set_error("%s: n_out = %zu and n_bursts = %zu must be below 2^31", who, n_out, n_bursts);
-        return SFE_EINVAL;
-    }
-    if (m.tx10 && (n_out & 1)) {
-        set_error("%s: n_out = %zu must be even with SFE_FMT_TX10 (whole 5-byte groups)", who, n_out);
-        return SFE_EINVAL;
-    }
-    if (n_bursts == 0) return SFE_OK;
-    if (start_base < 0) {
-        set_error("%s: start_base = %lld must not be negative", who, (long long)start_base);
-        return SFE_EINVAL;
-    }
-    if (n_bursts > 1 && start_step < m.F) {
-        set_error("%s: start_step = %lld is below the frame's F = %d samples (frames must not overlap)", who, (long long)start_step, m.F);
-        return SFE_EINVAL;
-    }
-    if (m.tx10 && ((start_base & 1) || (n_bursts > 1 && (start_step & 1)))) {
-        set_error("%s: start_base = %lld and start_step = %lld must be even with SFE_FMT_TX10 (a frame starts on a 5-byte group)", who,
-                  (long long)start_base, (long long)start_step);
-        return SFE_EINVAL;
-    }
-    const __int128 end = (__int128)start_base + (__int128)(n_bursts - 1) * (n_bursts > 1 ? start_step : 0) + m.F;
-    if (end > (__int128)n_out) {
-        set_error("%s: the last frame ends behind the stream's n_out = %zu samples", who, n_out);
-        return SFE_EINVAL;
-    }
-    return SFE_OK;
-}
-
 struct Ofdmmod {
     static constexpr uint32_t MAGIC = 0x4f464d31u;   // 'OFM1'
     uint32_t magic = MAGIC;
@@ -169,7 +136,7 @@ int sfe_dsp_ofdmmod_plan(int n_fft, int cp, int n_train, int n_data, const uint8
     if (n_data_bins) *n_data_bins = m.Nd;
     if (frame_len) *frame_len = m.F;
     if (n_in) *n_in = m.n_in();
-    if ((rc = omod_check_place("ofdmmod", m, n_bursts, start_base, start_step, n_out)) != SFE_OK) return rc;
+    if ((rc = check_place("ofdmmod", m.F, m.tx10, m.tx10, n_bursts, start_base, start_step, n_out)) != SFE_OK) return rc;
     if (n_bursts > 0) {
         if (!in) OMOD_REFUSE("ofdmmod: null input with bursts to modulate");
         if (in_stride < m.n_in()) {
@@ -221,24 +188,12 @@ int sfe_dsp_ofdmmod_process_stream(sfe_ofdmmod_t h, const void *d_in, size_t in_
     Ofdmmod *p = stream_handle(as_ofdmmod(h), who, n_written, "n_written");
     if (!p) return SFE_EINVAL;
     const OmodShape &m = p->sh;
-    int rc = omod_check_place(who, m, n_bursts, start_base, start_step, n_out);
-    if (rc != SFE_OK) return rc;
-    if (n_out == 0) return SFE_OK;
-    if ((rc = refuse_null(who, {d_out})) != SFE_OK || (n_bursts && (rc = refuse_null(who, {d_in})) != SFE_OK)) return rc;
-    if (n_bursts && in_stride < m.n_in()) {
-        set_error("ofdmmod_process_stream: in_stride %zu < the %zu %s a burst reads", in_stride, m.n_in(), m.symbols ? "cf32 symbols" : "bytes");
-        return SFE_ERANGE;
-    }
-    const size_t ie = m.symbols ? sizeof(omc) : 1;
-    size_t in_b = 0;
-    if (n_bursts && !span_bytes(n_bursts - 1, in_stride, m.n_in(), ie, &in_b)) {
-        set_error("ofdmmod_process_stream: in_stride is so large that the input's byte range reaches 2^62");
-        return SFE_EINVAL;
-    }
-    const Span in{d_in, in_b, ie}, ou{d_out, m.tx10 ? n_out / 2 * 5 : n_out * sizeof(omc), m.tx10 ? (size_t)1 : sizeof(omc)};
-    if ((rc = refuse_misaligned(who, "cf32 input and output 8 B; TX10 output and coded bytes need none", {in, ou})) != SFE_OK ||
-        (rc = refuse_overlap(who, in, {ou})) != SFE_OK)
-        return rc;
+    const FrameNouns nouns{"the ", m.symbols ? " cf32 symbols a burst reads" : " bytes a burst reads", "input's",
+                           "cf32 input and output 8 B; TX10 output and coded bytes need none"};
+    bool go;
+    int rc = check_frames(who, nouns, m.F, m.tx10, m.tx10, d_in, in_stride, m.n_in(), m.symbols ? sizeof(omc) : 1, n_bursts, start_base,
+                          start_step, d_out, n_out, &go);
+    if (rc != SFE_OK || !go) return rc;
     const long long nb = (long long)n_bursts, step = nb > 1 ? start_step : 0;
     const long long last_end = nb ? start_base + (nb - 1) * step + m.F : 0;
     OfdmmodArgs a{};

@@ -107,13 +107,7 @@ int sfe_dsp_psd_create(const float *window, int n_fft, int hop, int n_avg, float
 
 int sfe_dsp_psd_set_input_format(sfe_psd_t h, int fmt)
 {
-    Psd *p = as_psd(h);
-    if (!p || (fmt != SFE_FMT_F32 && fmt != SFE_FMT_U8)) {
-        set_error("psd_set_input_format: null handle or a format other than SFE_FMT_F32 / SFE_FMT_U8");
-        return SFE_EINVAL;
-    }
-    p->in_u8 = fmt == SFE_FMT_U8;
-    return SFE_OK;
+    return set_format(as_psd(h), "psd_set_input_format", fmt, SFE_FMT_U8, "SFE_FMT_U8", &Psd::in_u8);
 }
 
 int sfe_dsp_psd_process_stream(sfe_psd_t h, const void *d_in, size_t n_in, size_t in_stride, void *d_out, size_t out_stride,

@@ -44,42 +44,9 @@ ReedArgs reed_args(const Reed &r)
     return a;
 }
 
-// The checks the two stream calls share: `in_row` bytes are read and `out_row` written per frame.  SFE_OK with *go = false:
-// nothing to do.
-int reed_stream_checks(const char *who, size_t n_frames, const void *d_in, size_t in_stride, size_t in_row, const void *d_status_in, void *d_out,
-                       size_t out_stride, size_t out_row, void *d_rec, void *d_status, bool *go)
-{
-    *go = false;
-    if (n_frames >= ((size_t)1 << 31)) {
-        set_error("%s: n_frames = %zu must be below 2^31 per call", who, n_frames);
-        return SFE_EINVAL;
-    }
-    if (n_frames == 0) return SFE_OK;
-    int rc = refuse_null(who, {d_in, d_out});
-    if (rc != SFE_OK) return rc;
-    if (in_stride < in_row || out_stride < out_row) {
-        set_error("%s: in_stride %zu < the %zu bytes read per frame, or out_stride %zu < the %zu bytes written per frame", who, in_stride, in_row,
-                  out_stride, out_row);
-        return SFE_ERANGE;
-    }
-    size_t in_b = 0, ou_b = 0;
-    if (!span_bytes(n_frames - 1, in_stride, in_row, 1, &in_b) || !span_bytes(n_frames - 1, out_stride, out_row, 1, &ou_b)) {
-        set_error("%s: a stride is so large that its buffer's byte range reaches 2^62", who);
-        return SFE_EINVAL;
-    }
-    const Span in{d_in, in_b, 1}, si{d_status_in, d_status_in ? n_frames * 4 : 0, 4}, ou{d_out, ou_b, 1};
-    const Span re{d_rec, d_rec ? n_frames * 8 : 0, 4}, st{d_status, d_status ? n_frames * 4 : 0, 4};
-    if ((rc = refuse_misaligned(who, "records and statuses 4 B; payloads and frames need none", {si, re, st})) != SFE_OK ||
-        (rc = refuse_overlap(who, in, {ou, re, st})) != SFE_OK || (rc = refuse_overlap(who, si, {ou, re, st})) != SFE_OK)
-        return rc;
-    if (ranges_overlap(ou.p, ou.bytes, re.p, re.bytes) || ranges_overlap(ou.p, ou.bytes, st.p, st.bytes) ||
-        ranges_overlap(re.p, re.bytes, st.p, st.bytes)) {
-        set_error("%s: the output ranges overlap one another", who);
-        return SFE_EINVAL;
-    }
-    *go = true;
-    return SFE_OK;
-}
+// the stream calls' words for check_rows (call_checks.h); a record is 8 bytes
+constexpr RowNouns REED_NOUNS{"n_frames", "bytes read per frame", "the ", " bytes written per frame",
+                              "records and statuses 4 B; payloads and frames need none", 8};
 
 }  // namespace
 }  // namespace sfe
@@ -162,8 +129,8 @@ int sfe_dsp_reed_encode_stream(sfe_reed_t h, const void *d_payload, size_t in_st
     Reed *p = stream_handle(as_reed(h), who, n_out);
     if (!p) return SFE_EINVAL;
     bool go;
-    int rc = reed_stream_checks(who, n_frames, d_payload, in_stride, (size_t)p->code.payload_bytes(), nullptr, d_frame, out_stride,
-                                (size_t)p->code.frame_bytes(), nullptr, nullptr, &go);
+    int rc = check_rows(who, REED_NOUNS, n_frames, d_payload, in_stride, (size_t)p->code.payload_bytes(), 1, nullptr, d_frame, out_stride,
+                        (size_t)p->code.frame_bytes(), nullptr, nullptr, &go);
     if (rc != SFE_OK || !go) return rc;
     SFE_ON_DEVICE(p->device);
     ReedArgs a = reed_args(*p);
@@ -182,8 +149,8 @@ int sfe_dsp_reed_process_stream(sfe_reed_t h, const void *d_frame, size_t in_str
     Reed *p = stream_handle(as_reed(h), who, n_out);
     if (!p) return SFE_EINVAL;
     bool go;
-    int rc = reed_stream_checks(who, n_frames, d_frame, in_stride, (size_t)p->code.frame_bytes(), d_status_in, d_out, out_stride,
-                                (size_t)p->code.payload_bytes(), d_rec, d_status, &go);
+    int rc = check_rows(who, REED_NOUNS, n_frames, d_frame, in_stride, (size_t)p->code.frame_bytes(), 1, d_status_in, d_out, out_stride,
+                        (size_t)p->code.payload_bytes(), d_rec, d_status, &go);
     if (rc != SFE_OK || !go) return rc;
     SFE_ON_DEVICE(p->device);
     ReedArgs a = reed_args(*p);

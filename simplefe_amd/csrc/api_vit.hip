@@ -81,6 +81,8 @@ int vit_check_code(const char *who, int K, int n_gen, const uint32_t *gen, const
 namespace {
 
 constexpr int VIT_MAX_SKIP = 1 << 24;
+// vit_process_stream's words for check_rows (call_checks.h); a record is 8 bytes
+constexpr RowNouns VIT_NOUNS{"n_bursts", "elements of a burst's row", "ceil(n_info / 8) = ", "", "soft values 4 B, symbols 8 B, records and statuses 4 B", 8};
 
 // what plan and create validate
 int vit_check(int K, int n_gen, const uint32_t *gen, const uint8_t *keep, int P, int terminated, int n_info, int in_mode, int skip, VitCode *c)
@@ -318,34 +320,10 @@ int sfe_dsp_vit_process_stream(sfe_vit_t h, const void *d_in, size_t in_stride, 
     Vit *p = stream_handle(as_vit(h), who, n_out);
     if (!p) return SFE_EINVAL;
     const VitCode &c = p->code;
-    if (n_bursts >= ((size_t)1 << 31)) {
-        set_error("vit_process_stream: n_bursts = %zu must be below 2^31 per call", n_bursts);
-        return SFE_EINVAL;
-    }
-    if (n_bursts == 0) return SFE_OK;
-    int rc = refuse_null(who, {d_in, d_bits});
-    if (rc != SFE_OK) return rc;
-    const size_t nbytes = ((size_t)c.n_info + 7) / 8, esz = 4 * (size_t)c.elem_floats();
-    if (in_stride < c.row_elems() || out_stride < nbytes) {
-        set_error("vit_process_stream: in_stride %zu < the %zu elements of a burst's row, or out_stride %zu < ceil(n_info / 8) = %zu", in_stride,
-                  c.row_elems(), out_stride, nbytes);
-        return SFE_ERANGE;
-    }
-    size_t in_b = 0, ou_b = 0;
-    if (!span_bytes(n_bursts - 1, in_stride, c.row_elems(), esz, &in_b) || !span_bytes(n_bursts - 1, out_stride, nbytes, 1, &ou_b)) {
-        set_error("vit_process_stream: a stride is so large that its buffer's byte range reaches 2^62");
-        return SFE_EINVAL;
-    }
-    const Span in{d_in, in_b, esz}, si{d_status_in, d_status_in ? n_bursts * 4 : 0, 4}, ou{d_bits, ou_b, 1};
-    const Span re{d_rec, d_rec ? n_bursts * 8 : 0, 4}, st{d_status, d_status ? n_bursts * 4 : 0, 4};
-    if ((rc = refuse_misaligned(who, "soft values 4 B, symbols 8 B, records and statuses 4 B", {in, si, ou, re, st})) != SFE_OK ||
-        (rc = refuse_overlap(who, in, {ou, re, st})) != SFE_OK || (rc = refuse_overlap(who, si, {ou, re, st})) != SFE_OK)
-        return rc;
-    if (ranges_overlap(ou.p, ou.bytes, re.p, re.bytes) || ranges_overlap(ou.p, ou.bytes, st.p, st.bytes) ||
-        ranges_overlap(re.p, re.bytes, st.p, st.bytes)) {
-        set_error("vit_process_stream: the output ranges overlap one another");
-        return SFE_EINVAL;
-    }
+    bool go;
+    int rc = check_rows(who, VIT_NOUNS, n_bursts, d_in, in_stride, c.row_elems(), 4 * (size_t)c.elem_floats(), d_status_in, d_bits, out_stride,
+                        ((size_t)c.n_info + 7) / 8, d_rec, d_status, &go);
+    if (rc != SFE_OK || !go) return rc;
     SFE_ON_DEVICE(p->device);
     VitArgs a = vit_args(*p);
     a.in = static_cast<const float *>(d_in);

@@ -1,8 +1,11 @@
 // block.h -- what every handle of libsfe_dsp.so is built from: owners of its device memory, pinned host memory, streams and
-// events, the carried pair, the device scope of a create, the handle cast, the table of the unit circle, and the checks
-// every process_stream of a streaming block opens with.  The FIR, resampler and pipe handles (host.h, api_pipe.hip) and the
-// streaming blocks' (api_chan.hip ... api_mod.hip) all use it.  HOST CODE ONLY; host.h includes it.  A handle's struct names
-// its magic as `static constexpr uint32_t MAGIC` and carries `magic` and `device`.
+// events, the carried pair, the device scope of a create, the handle cast, the table of the unit circle, the opening of
+// every process_stream and the format setter.  The checks of a call's buffers need no HIP and live in call_checks.h, which
+// this includes: the pieces (Span, span_bytes, refuse_*) and the one check each of the burst chain's three families --
+// rows (api_vit.hip, api_reed.hip, api_ldpc.hip), windows (api_burst.hip, api_ofdm.hip), frames (api_mod.hip,
+// api_ofdmmod.hip).  The FIR, resampler and pipe handles (host.h, api_pipe.hip) and every block's api_*.hip use it.  HOST CODE
+// ONLY; host.h includes it.  A handle's struct names its magic as `static constexpr uint32_t MAGIC` and carries `magic` and
+// `device`.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -12,6 +15,7 @@
 #include <utility>
 #include <vector>
 
+#include "call_checks.h"
 #include "common.h"
 
 namespace sfe {
@@ -24,7 +28,6 @@ namespace sfe {
         return SFE_EHIP;                                     \
     }
 
-bool ranges_overlap(const void *a, size_t an, const void *b, size_t bn);      // [a, a + an) and [b, b + bn) share a byte
 int use_device(int device);                                                    // hipSetDevice with the range / no-GPU checks
 bool stream_is_capturing(hipStream_t s);
 
@@ -237,58 +240,19 @@ T *stream_handle(T *p, const char *who, size_t *n_out, const char *n_name = "n_o
     }
     return p;
 }
+// the checks of the buffers that follow: call_checks.h
 
-inline int refuse_2_31(const char *who, size_t n_in)       // the kernels index a stream's samples in 32 bits
+// sfe_dsp_<block>_set_input_format / _set_output_format where the format is all there is to check: SFE_FMT_F32 clears
+// the handle's flag, `other` (SFE_FMT_U8 or SFE_FMT_TX10; `other_name` for the message) sets it.  p: as_handle's result
+template <class T>
+int set_format(T *p, const char *who, int fmt, int other, const char *other_name, int T::*flag)
 {
-    if (n_in < ((size_t)1 << 31)) return SFE_OK;
-    set_error("%s: n_in = %zu must be below 2^31 per call", who, n_in);
-    return SFE_EINVAL;
-}
-
-inline int refuse_null(const char *who, std::initializer_list<const void *> bufs)
-{
-    for (const void *b : bufs)
-        if (!b) {
-            set_error("%s: null buffer", who);
-            return SFE_EINVAL;
-        }
+    if (!p || (fmt != SFE_FMT_F32 && fmt != other)) {
+        set_error("%s: null handle or a format other than SFE_FMT_F32 / %s", who, other_name);
+        return SFE_EINVAL;
+    }
+    p->*flag = fmt == other;
     return SFE_OK;
-}
-
-// a buffer of `bytes` bytes whose element is `align` bytes (a power of two)
-struct Span {
-    const void *p;
-    size_t bytes, align;
-};
-inline int refuse_misaligned(const char *who, const char *elements, std::initializer_list<Span> bufs)   // `elements`: for the message
-{
-    for (const Span &b : bufs)
-        if (reinterpret_cast<uintptr_t>(b.p) & (b.align - 1)) {
-            set_error("%s: buffers must be aligned to their element (%s)", who, elements);
-            return SFE_EINVAL;
-        }
-    return SFE_OK;
-}
-// an output of no bytes (a null optional one, a call that completes no row) overlaps nothing
-inline int refuse_overlap(const char *who, Span in, std::initializer_list<Span> outs)
-{
-    for (const Span &o : outs)
-        if (ranges_overlap(in.p, in.bytes, o.p, o.bytes)) {
-            set_error("%s: input and output ranges overlap (in-place operation is not supported)", who);
-            return SFE_EINVAL;
-        }
-    return SFE_OK;
-}
-
-// bytes = (rows_less_1 * stride + tail) * elem, false where that is not below 2^62
-inline bool span_bytes(size_t rows_less_1, size_t stride, size_t tail, size_t elem, size_t *bytes)
-{
-    size_t v;
-    if (__builtin_mul_overflow(rows_less_1, stride, &v) || __builtin_add_overflow(v, tail, &v) || __builtin_mul_overflow(v, elem, &v) ||
-        v >= ((size_t)1 << 62))
-        return false;
-    *bytes = v;
-    return true;
 }
 
 // the counter named advances on the host with the carried pair, so a captured call could not be replayed

@@ -1,0 +1,610 @@
+// test_call_checks.cpp -- csrc/call_checks.h alone, built by a plain host compiler under -fsanitize=address,undefined
+// (tests/test_call_checks_host.py): the return code and the whole message of every check, at the boundary values.  The
+// header is the only library file included -- it needs no HIP -- and set_error is this program's own.  Pointers are made-up
+// integers: nothing is dereferenced.  Every expected message is written out here as the entry point worded it before the
+// checks were shared; none is composed from the code under test.
+#include <stdarg.h>
+#include <stdio.h>
+#include <string.h>
+
+#include "../../simplefe_amd/csrc/call_checks.h"
+
+static char g_msg[512];
+namespace sfe {
+void set_error(const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_msg, sizeof g_msg, fmt, ap);
+    va_end(ap);
+}
+}  // namespace sfe
+using namespace sfe;
+
+static int g_fails = 0, g_checks = 0;
+static void expect(int line, int rc, int code, const char *text)
+{
+    g_checks++;
+    if (rc == code && strcmp(g_msg, text) == 0) return;
+    g_fails++;
+    printf("line %d: rc %d, message \"%s\"\n         want %d, \"%s\"\n", line, rc, g_msg, code, text);
+}
+static void expect_true(int line, bool ok)
+{
+    g_checks++;
+    if (ok) return;
+    g_fails++;
+    printf("line %d: false\n", line);
+}
+// the message is cleared first: an accepted call must leave it alone ("")
+#define CHECK(call, code, text)                 \
+    do {                                        \
+        g_msg[0] = 0;                           \
+        const int rc__ = (call);                \
+        expect(__LINE__, rc__, code, text);     \
+    } while (0)
+#define TRUE(x) expect_true(__LINE__, (x))
+
+static const void *P(uintptr_t a) { return reinterpret_cast<const void *>(a); }
+static const size_t T31 = (size_t)1 << 31, T62 = (size_t)1 << 62, T63 = (size_t)1 << 63;
+
+static void test_span_bytes()
+{
+    size_t b = 77;
+    TRUE(!span_bytes(T63, 2, 0, 1, &b) && b == 77);             // rows * stride overflows
+    TRUE(!span_bytes(1, SIZE_MAX, 1, 1, &b) && b == 77);        // + tail overflows
+    TRUE(!span_bytes(0, 0, T63, 2, &b) && b == 77);             // * elem overflows
+    TRUE(span_bytes(0, 0, T62 - 1, 1, &b) && b == T62 - 1);
+    TRUE(!span_bytes(0, 0, T62, 1, &b) && b == T62 - 1);
+    TRUE(!span_bytes(0, 0, T62 / 2, 2, &b));                    // 2^62 by the last product, no overflow
+    TRUE(span_bytes(1, T62 / 2, T62 / 2 - 1, 1, &b) && b == T62 - 1);
+    TRUE(span_bytes(2, 100, 7, 8, &b) && b == 207 * 8);
+}
+
+static void test_overlap()
+{
+    TRUE(!ranges_overlap(P(1000), 100, P(1100), 100) && !ranges_overlap(P(1100), 100, P(1000), 100));      // adjacent
+    TRUE(ranges_overlap(P(1000), 100, P(1099), 100) && ranges_overlap(P(1099), 100, P(1000), 100));        // one shared byte
+    TRUE(!ranges_overlap(P(1000), 100, P(1050), 0) && !ranges_overlap(P(1050), 0, P(1000), 100));          // no bytes, inside
+    TRUE(!ranges_overlap(P(0), 0, P(0), 100) && !ranges_overlap(P(1000), 100, nullptr, 0));
+    const Span in{P(1000), 100, 1};
+    const char *text = "w: input and output ranges overlap (in-place operation is not supported)";
+    CHECK(refuse_overlap("w", in, {Span{P(1100), 100, 1}, Span{P(900), 100, 1}}), SFE_OK, "");
+    CHECK(refuse_overlap("w", in, {Span{P(1100), 100, 1}, Span{P(1099), 100, 1}}), SFE_EINVAL, text);
+    CHECK(refuse_overlap("w", in, {Span{P(901), 100, 1}}), SFE_EINVAL, text);
+    CHECK(refuse_overlap("w", in, {Span{P(1050), 0, 4}, Span{nullptr, 0, 4}}), SFE_OK, "");
+    CHECK(refuse_overlap("w", Span{P(1050), 0, 1}, {Span{P(1000), 100, 1}}), SFE_OK, "");
+    CHECK(refuse_null("w", {P(8), P(16)}), SFE_OK, "");
+    CHECK(refuse_null("w", {P(8), nullptr}), SFE_EINVAL, "w: null buffer");
+    CHECK(refuse_2_31("w", T31 - 1), SFE_OK, "");
+    CHECK(refuse_2_31("w", T31), SFE_EINVAL, "w: n_in = 2147483648 must be below 2^31 per call");
+    CHECK(refuse_misaligned("w", "x 8 B", {Span{P(0x1008), 0, 8}, Span{nullptr, 0, 8}, Span{P(0x1001), 0, 1}}), SFE_OK, "");
+    CHECK(refuse_misaligned("w", "x 8 B", {Span{P(0x1008), 0, 8}, Span{P(0x1004), 0, 8}}), SFE_EINVAL,
+          "w: buffers must be aligned to their element (x 8 B)");
+}
+
+static void test_outputs_overlap()
+{
+    const uintptr_t at[4] = {0x1000, 0x2000, 0x3000, 0x4000};
+    auto run = [&](const uintptr_t *a) {
+        return refuse_outputs_overlap("w", {Span{P(a[0]), 0x100, 1}, Span{P(a[1]), 0x100, 1}, Span{P(a[2]), 0x100, 1}, Span{P(a[3]), 0x100, 1}});
+    };
+    CHECK(run(at), SFE_OK, "");
+    for (int i = 0; i < 4; i++)
+        for (int j = i + 1; j < 4; j++) {
+            uintptr_t a[4] = {at[0], at[1], at[2], at[3]};
+            a[j] = at[i] + 0xff;            // the last byte of i, and of nothing else
+            CHECK(run(a), SFE_EINVAL, "w: the output ranges overlap one another");
+            a[j] = at[i] + 0x100;           // adjacent
+            CHECK(run(a), SFE_OK, "");
+        }
+    CHECK(refuse_outputs_overlap("w", {Span{P(0x1000), 0x100, 1}, Span{nullptr, 0, 4}, Span{P(0x1010), 0, 4}}), SFE_OK, "");
+    CHECK(refuse_outputs_overlap("w", {}), SFE_OK, "");
+}
+
+static void test_check_starts()
+{
+    const int64_t R = INT64_MAX - ((int64_t)1 << 33) + 1;       // 2^63 - 2^33
+    const char *text = "burst: start_base + b * start_step must stay within +-(2^63 - 2^33) for every burst";
+    CHECK(check_starts("burst", R, 0, 1), SFE_OK, "");
+    CHECK(check_starts("burst", R + 1, 0, 1), SFE_EINVAL, text);
+    CHECK(check_starts("burst", -R, 0, 1), SFE_OK, "");
+    CHECK(check_starts("burst", -R - 1, 0, 1), SFE_EINVAL, text);
+    CHECK(check_starts("burst", INT64_MIN, 0, 1), SFE_EINVAL, text);
+    CHECK(check_starts("burst", INT64_MAX, 0, 1), SFE_EINVAL, text);
+    CHECK(check_starts("burst", R, INT64_MAX, 1), SFE_OK, "");          // one burst: the step moves nothing
+    CHECK(check_starts("burst", 0, R / 2, 3), SFE_OK, "");              // the last burst at R
+    CHECK(check_starts("burst", 1, R / 2, 3), SFE_EINVAL, text);        // and one past it
+    CHECK(check_starts("burst", 0, -(R / 2), 3), SFE_OK, "");
+    CHECK(check_starts("burst", -1, -(R / 2), 3), SFE_EINVAL, text);
+    CHECK(check_starts("burst", 0, INT64_MAX, T31 - 1), SFE_EINVAL, text);      // far outside int64: no wrap back into range
+    CHECK(check_starts("ofdm", R + 1, 0, 1), SFE_EINVAL, "ofdm: start_base + b * start_step must stay within +-(2^63 - 2^33) for every burst");
+}
+
+static void test_check_place()
+{
+    const int F = 8;
+    // the rules in their order
+    CHECK(check_place("mod", F, false, false, 1, 0, 0, T31), SFE_EINVAL, "mod: n_out = 2147483648 and n_bursts = 1 must be below 2^31");
+    CHECK(check_place("mod", F, false, false, T31, 0, 0, 10), SFE_EINVAL, "mod: n_out = 10 and n_bursts = 2147483648 must be below 2^31");
+    CHECK(check_place("mod", F, true, false, T31, 0, 0, 11), SFE_EINVAL, "mod: n_out = 11 and n_bursts = 2147483648 must be below 2^31");
+    CHECK(check_place("mod", F, true, false, 1, -1, 0, 11), SFE_EINVAL, "mod: n_out = 11 must be even with SFE_FMT_TX10 (whole 5-byte groups)");
+    CHECK(check_place("mod", F, true, false, 0, 0, 0, 11), SFE_EINVAL, "mod: n_out = 11 must be even with SFE_FMT_TX10 (whole 5-byte groups)");
+    CHECK(check_place("mod", F, false, false, 0, 0, 0, 11), SFE_OK, "");
+    CHECK(check_place("mod", F, true, true, 0, -5, -3, 10), SFE_OK, "");            // no burst: whatever the starts
+    CHECK(check_place("mod", F, false, false, 0, INT64_MIN, INT64_MIN, 0), SFE_OK, "");
+    CHECK(check_place("mod", F, false, false, 2, -1, 7, 100), SFE_EINVAL, "mod: start_base = -1 must not be negative");
+    CHECK(check_place("mod", F, true, true, 2, 1, 7, 100), SFE_EINVAL,
+          "mod: start_step = 7 is below the frame's F = 8 samples (frames must not overlap)");
+    CHECK(check_place("mod", F, false, false, 2, 0, F - 1, 100), SFE_EINVAL,
+          "mod: start_step = 7 is below the frame's F = 8 samples (frames must not overlap)");
+    CHECK(check_place("mod", F, false, false, 2, 0, F, 100), SFE_OK, "");
+    CHECK(check_place("mod", F, false, false, 1, 0, F - 1, 100), SFE_OK, "");       // one burst: any step
+    CHECK(check_place("mod", F, false, false, 1, 92, -1000, 100), SFE_OK, "");
+    CHECK(check_place("mod", F, false, false, 1, 92, INT64_MIN, 100), SFE_OK, "");
+    CHECK(check_place("mod", F, false, false, 2, 0, F, 16), SFE_OK, "");            // the last frame ends at n_out
+    CHECK(check_place("mod", F, false, false, 2, 0, F, 15), SFE_EINVAL, "mod: the last frame ends behind the stream's n_out = 15 samples");
+    CHECK(check_place("mod", F, false, false, 1, 92, 0, 100), SFE_OK, "");
+    CHECK(check_place("mod", F, false, false, 1, 93, 0, 100), SFE_EINVAL, "mod: the last frame ends behind the stream's n_out = 100 samples");
+    CHECK(check_place("mod", F, false, false, 3, 5, INT64_MAX, 100), SFE_EINVAL, "mod: the last frame ends behind the stream's n_out = 100 samples");
+    CHECK(check_place("mod", F, false, false, T31 - 1, INT64_MAX, INT64_MAX, T31 - 1), SFE_EINVAL,
+          "mod: the last frame ends behind the stream's n_out = 2147483647 samples");
+    // whole groups under TX10: ofdmmod's rule, ahead of the frame's end
+    CHECK(check_place("ofdmmod", F, true, true, 1, 1, 0, 100), SFE_EINVAL,
+          "ofdmmod: start_base = 1 and start_step = 0 must be even with SFE_FMT_TX10 (a frame starts on a 5-byte group)");
+    CHECK(check_place("ofdmmod", F, true, true, 2, 0, 9, 100), SFE_EINVAL,
+          "ofdmmod: start_base = 0 and start_step = 9 must be even with SFE_FMT_TX10 (a frame starts on a 5-byte group)");
+    CHECK(check_place("ofdmmod", F, true, true, 2, 99, 9, 100), SFE_EINVAL,
+          "ofdmmod: start_base = 99 and start_step = 9 must be even with SFE_FMT_TX10 (a frame starts on a 5-byte group)");
+    CHECK(check_place("ofdmmod", F, true, true, 1, 0, 9, 100), SFE_OK, "");         // one burst: the step is not looked at
+    CHECK(check_place("ofdmmod", F, true, true, 2, 2, 10, 100), SFE_OK, "");
+    CHECK(check_place("ofdmmod", F, true, false, 1, 1, 0, 100), SFE_OK, "");        // mod: odd starts are its own business
+    CHECK(check_place("ofdmmod", F, true, false, 2, 0, 9, 100), SFE_OK, "");
+    CHECK(check_place("ofdmmod", F, false, false, 2, 1, 9, 100), SFE_OK, "");
+    CHECK(check_place("ofdmmod", F, true, false, 2, 99, 9, 100), SFE_EINVAL, "ofdmmod: the last frame ends behind the stream's n_out = 100 samples");
+}
+
+// ---- rows.  The words each block hands over, and what its entry point said before the checks were shared.
+static const RowNouns VIT{"n_bursts", "elements of a burst's row", "ceil(n_info / 8) = ", "", "soft values 4 B, symbols 8 B, records and statuses 4 B", 8};
+static const RowNouns REED{"n_frames", "bytes read per frame", "the ", " bytes written per frame",
+                           "records and statuses 4 B; payloads and frames need none", 8};
+static const RowNouns LDPC{"n_words", "elements read per codeword", "the ", " bytes written per codeword",
+                           "soft values 4 B, symbols 8 B, records and statuses 4 B; payloads and codewords need none", 12};
+
+struct RowCase {
+    const char *who;
+    const RowNouns *nn;
+    size_t in_row, esz, out_row;
+    bool decode;            // status in, record and status out
+    const char *count, *null, *short_in, *short_out, *huge, *misaligned, *in_out, *out_out;
+};
+
+static void test_rows(const RowCase &c)
+{
+    const size_t n = 3, in_b = (2 * c.in_row + c.in_row) * c.esz, out_b = 3 * c.out_row, rec_b = n * c.nn->rec_bytes;
+    const uintptr_t IN = 0x10000, OUT = 0x20000, SI = 0x30000, REC = 0x40000, ST = 0x50000;
+    bool go;
+    auto call = [&](size_t n_, uintptr_t in, size_t is, uintptr_t si, uintptr_t out, size_t os, uintptr_t rec, uintptr_t st) {
+        go = true;
+        if (!c.decode) si = rec = st = 0;
+        return check_rows(c.who, *c.nn, n_, P(in), is, c.in_row, c.esz, P(si), P(out), os, c.out_row, P(rec), P(st), &go);
+    };
+    const size_t is = c.in_row, os = c.out_row;
+    CHECK(call(n, IN, is, SI, OUT, os, REC, ST), SFE_OK, "");
+    TRUE(go);
+    CHECK(call(n, IN, is, 0, OUT, os, 0, 0), SFE_OK, "");           // every optional buffer left out
+    TRUE(go);
+    CHECK(call(0, 0, 0, 0, 0, 0, 0, 0), SFE_OK, "");
+    TRUE(!go);
+    CHECK(call(T31, 0, 0, SI, 0, 0, REC, ST), SFE_EINVAL, c.count);
+    TRUE(!go);
+    CHECK(call(T31 - 1, 0, 0, SI, OUT, 0, REC, ST), SFE_EINVAL, c.null);        // the count passes, the next rule speaks
+    CHECK(call(n, 0, is - 1, SI, OUT, os, REC, ST), SFE_EINVAL, c.null);
+    CHECK(call(n, IN, is, SI, 0, os - 1, REC, ST), SFE_EINVAL, c.null);
+    CHECK(call(n, IN, is - 1, SI, OUT, os, REC, ST), SFE_ERANGE, c.short_in);
+    CHECK(call(n, IN, is, SI, OUT, os - 1, REC, ST), SFE_ERANGE, c.short_out);
+    CHECK(call(n, IN + 1, T62, SI, OUT, os, REC, ST), SFE_EINVAL, c.huge);
+    CHECK(call(n, IN, is, SI, IN, T62, REC, ST), SFE_EINVAL, c.huge);
+    CHECK(call(n, IN, SIZE_MAX, SI, OUT, os, REC, ST), SFE_EINVAL, c.huge);
+    CHECK(call(1, IN, T62, SI, OUT, T62, REC, ST), SFE_OK, "");     // one row: the strides move nothing
+    TRUE(go);
+    if (c.esz > 1) {
+        CHECK(call(n, IN + c.esz / 2, is, SI, IN, os, REC, ST), SFE_EINVAL, c.misaligned);
+        CHECK(call(n, IN + 1, is, SI, OUT, os, REC, ST), SFE_EINVAL, c.misaligned);
+    } else {
+        CHECK(call(n, IN + 1, is, SI, OUT + 1, os, REC, ST), SFE_OK, "");
+    }
+    CHECK(call(n, IN, is, SI, OUT + 3, os, REC, ST), SFE_OK, "");   // bytes out: no alignment
+    if (c.decode) {
+        CHECK(call(n, IN, is, SI + 2, OUT, os, REC, ST), SFE_EINVAL, c.misaligned);
+        CHECK(call(n, IN, is, SI, OUT, os, REC + 2, ST), SFE_EINVAL, c.misaligned);
+        CHECK(call(n, IN, is, SI, OUT, os, REC, ST + 2), SFE_EINVAL, c.misaligned);
+        CHECK(call(n, IN, is, SI, OUT, os, IN, ST + 1), SFE_EINVAL, c.misaligned);
+    }
+    CHECK(call(n, IN, is, SI, IN + in_b - 1, os, REC, REC), SFE_EINVAL, c.in_out);
+    CHECK(call(n, IN, is, SI, IN + in_b, os, REC, ST), SFE_OK, "");
+    CHECK(call(n, IN, is, SI, IN - out_b, os, REC, ST), SFE_OK, "");
+    CHECK(call(n, IN, is, SI, IN - out_b + 1, os, REC, ST), SFE_EINVAL, c.in_out);
+    CHECK(call(n, IN, 2 * is, SI, IN + (5 * is) * c.esz - 1, os, REC, ST), SFE_EINVAL, c.in_out);      // the stride counts
+    CHECK(call(n, IN, 2 * is, SI, IN + (5 * is) * c.esz, os, REC, ST), SFE_OK, "");
+    if (c.decode) {
+        CHECK(call(n, IN, is, SI, OUT, os, IN, ST), SFE_EINVAL, c.in_out);
+        CHECK(call(n, IN, is, SI, OUT, os, REC, IN), SFE_EINVAL, c.in_out);
+        CHECK(call(n, IN, is, SI, SI + 4 * n - 1, os, REC, ST), SFE_EINVAL, c.in_out);
+        CHECK(call(n, IN, is, SI, SI + 4 * n, os, REC, ST), SFE_OK, "");
+        CHECK(call(n, IN, is, SI, OUT, os, SI + 8, ST), SFE_EINVAL, c.in_out);
+        CHECK(call(n, IN, is, SI, OUT, os, REC, SI), SFE_EINVAL, c.in_out);
+        CHECK(call(n, IN, is, SI, OUT, os, OUT, ST), SFE_EINVAL, c.out_out);
+        CHECK(call(n, IN, is, SI, OUT, os, REC, OUT), SFE_EINVAL, c.out_out);
+        CHECK(call(n, IN, is, SI, OUT, os, REC, REC + rec_b - 4), SFE_EINVAL, c.out_out);         // the record's own width
+        CHECK(call(n, IN, is, SI, OUT, os, REC, REC + rec_b), SFE_OK, "");
+        CHECK(call(n, IN, is, SI, OUT, os, ST + 4 * n - 4, ST), SFE_EINVAL, c.out_out);
+        CHECK(call(n, IN, is, SI, OUT, os, ST + 4 * n, ST), SFE_OK, "");
+        CHECK(call(n, IN, is, 0, OUT, os, 0, OUT), SFE_EINVAL, c.out_out);
+        CHECK(call(n, IN, is, SI, OUT, 2 * os, REC, (OUT + 5 * os - 1) & ~(uintptr_t)3), SFE_EINVAL, c.out_out);     // the stride counts
+        CHECK(call(n, IN, is, SI, OUT, 2 * os, REC, (OUT + 5 * os + 3) & ~(uintptr_t)3), SFE_OK, "");
+    }
+    TRUE(go);
+}
+
+static void test_rows_all()
+{
+    test_rows(RowCase{"vit_process_stream", &VIT, 40, 4, 5, true, "vit_process_stream: n_bursts = 2147483648 must be below 2^31 per call",
+                      "vit_process_stream: null buffer",
+                      "vit_process_stream: in_stride 39 < the 40 elements of a burst's row, or out_stride 5 < ceil(n_info / 8) = 5",
+                      "vit_process_stream: in_stride 40 < the 40 elements of a burst's row, or out_stride 4 < ceil(n_info / 8) = 5",
+                      "vit_process_stream: a stride is so large that its buffer's byte range reaches 2^62",
+                      "vit_process_stream: buffers must be aligned to their element (soft values 4 B, symbols 8 B, records and statuses 4 B)",
+                      "vit_process_stream: input and output ranges overlap (in-place operation is not supported)",
+                      "vit_process_stream: the output ranges overlap one another"});
+    test_rows(RowCase{"vit_process_stream", &VIT, 23, 8, 5, true, "vit_process_stream: n_bursts = 2147483648 must be below 2^31 per call",
+                      "vit_process_stream: null buffer",
+                      "vit_process_stream: in_stride 22 < the 23 elements of a burst's row, or out_stride 5 < ceil(n_info / 8) = 5",
+                      "vit_process_stream: in_stride 23 < the 23 elements of a burst's row, or out_stride 4 < ceil(n_info / 8) = 5",
+                      "vit_process_stream: a stride is so large that its buffer's byte range reaches 2^62",
+                      "vit_process_stream: buffers must be aligned to their element (soft values 4 B, symbols 8 B, records and statuses 4 B)",
+                      "vit_process_stream: input and output ranges overlap (in-place operation is not supported)",
+                      "vit_process_stream: the output ranges overlap one another"});
+    test_rows(RowCase{"reed_encode_stream", &REED, 96, 1, 120, false, "reed_encode_stream: n_frames = 2147483648 must be below 2^31 per call",
+                      "reed_encode_stream: null buffer",
+                      "reed_encode_stream: in_stride 95 < the 96 bytes read per frame, or out_stride 120 < the 120 bytes written per frame",
+                      "reed_encode_stream: in_stride 96 < the 96 bytes read per frame, or out_stride 119 < the 120 bytes written per frame",
+                      "reed_encode_stream: a stride is so large that its buffer's byte range reaches 2^62", "",
+                      "reed_encode_stream: input and output ranges overlap (in-place operation is not supported)", ""});
+    test_rows(RowCase{"reed_process_stream", &REED, 120, 1, 96, true, "reed_process_stream: n_frames = 2147483648 must be below 2^31 per call",
+                      "reed_process_stream: null buffer",
+                      "reed_process_stream: in_stride 119 < the 120 bytes read per frame, or out_stride 96 < the 96 bytes written per frame",
+                      "reed_process_stream: in_stride 120 < the 120 bytes read per frame, or out_stride 95 < the 96 bytes written per frame",
+                      "reed_process_stream: a stride is so large that its buffer's byte range reaches 2^62",
+                      "reed_process_stream: buffers must be aligned to their element (records and statuses 4 B; payloads and frames need none)",
+                      "reed_process_stream: input and output ranges overlap (in-place operation is not supported)",
+                      "reed_process_stream: the output ranges overlap one another"});
+    test_rows(RowCase{"ldpc_encode_stream", &LDPC, 12, 1, 24, false, "ldpc_encode_stream: n_words = 2147483648 must be below 2^31 per call",
+                      "ldpc_encode_stream: null buffer",
+                      "ldpc_encode_stream: in_stride 11 < the 12 elements read per codeword, or out_stride 24 < the 24 bytes written per codeword",
+                      "ldpc_encode_stream: in_stride 12 < the 12 elements read per codeword, or out_stride 23 < the 24 bytes written per codeword",
+                      "ldpc_encode_stream: a stride is so large that its buffer's byte range reaches 2^62", "",
+                      "ldpc_encode_stream: input and output ranges overlap (in-place operation is not supported)", ""});
+    const char *ldpc_al = "ldpc_process_stream: buffers must be aligned to their element (soft values 4 B, symbols 8 B, records and statuses 4 B; "
+                          "payloads and codewords need none)";
+    test_rows(RowCase{"ldpc_process_stream", &LDPC, 192, 4, 12, true, "ldpc_process_stream: n_words = 2147483648 must be below 2^31 per call",
+                      "ldpc_process_stream: null buffer",
+                      "ldpc_process_stream: in_stride 191 < the 192 elements read per codeword, or out_stride 12 < the 12 bytes written per codeword",
+                      "ldpc_process_stream: in_stride 192 < the 192 elements read per codeword, or out_stride 11 < the 12 bytes written per codeword",
+                      "ldpc_process_stream: a stride is so large that its buffer's byte range reaches 2^62", ldpc_al,
+                      "ldpc_process_stream: input and output ranges overlap (in-place operation is not supported)",
+                      "ldpc_process_stream: the output ranges overlap one another"});
+    test_rows(RowCase{"ldpc_process_stream", &LDPC, 99, 8, 12, true, "ldpc_process_stream: n_words = 2147483648 must be below 2^31 per call",
+                      "ldpc_process_stream: null buffer",
+                      "ldpc_process_stream: in_stride 98 < the 99 elements read per codeword, or out_stride 12 < the 12 bytes written per codeword",
+                      "ldpc_process_stream: in_stride 99 < the 99 elements read per codeword, or out_stride 11 < the 12 bytes written per codeword",
+                      "ldpc_process_stream: a stride is so large that its buffer's byte range reaches 2^62", ldpc_al,
+                      "ldpc_process_stream: input and output ranges overlap (in-place operation is not supported)",
+                      "ldpc_process_stream: the output ranges overlap one another"});
+}
+
+// ---- windows
+struct WindowCase {
+    const char *who, *row_name;
+    size_t row, chan_row;       // chan_row 0: the block has no channel output
+    const char *n_in, *count, *null, *short_out, *short_status, *short_in, *starts, *huge, *misaligned, *in_out, *out_out;
+};
+
+static void test_windows(const WindowCase &c, size_t isz)
+{
+    const size_t S = 2, n_in = 1000, nb = 3, rows = S * nb, REC = 8;
+    const size_t in_b = (n_in + n_in) * isz, ou_b = rows * c.row * 8, ch_b = rows * c.chan_row * 8, re_b = rows * REC * 4, st_b = (nb + nb) * 4;
+    struct A {
+        size_t S, n_in, in_stride;
+        uintptr_t in, idx;
+        size_t idx_stride;
+        uintptr_t gate;
+        size_t gate_stride, nb;
+        int64_t base, step;
+        uintptr_t out;
+        size_t out_stride;
+        uintptr_t chan, rec, st;
+        size_t st_stride;
+    };
+    const A good{S, n_in, n_in, 0x100000, 0x200000, nb, 0x300000, nb, nb, 5, 7, 0x400000, c.row, c.chan_row ? (uintptr_t)0x500000 : 0, 0x600000, 0x700000, nb};
+    bool go;
+    auto call = [&](const A &a) {
+        go = true;
+        return check_windows(c.who, c.row_name, a.S, isz, P(a.in), a.n_in, a.in_stride, P(a.idx), a.idx_stride, P(a.gate), a.gate_stride, a.nb,
+                             a.base, a.step, P(a.out), a.out_stride, c.row, P(a.chan), c.chan_row, P(a.rec), REC, P(a.st), a.st_stride, &go);
+    };
+    A a = good;
+    CHECK(call(a), SFE_OK, "");
+    TRUE(go);
+    a = good, a.idx = a.gate = a.chan = a.rec = a.st = 0, a.idx_stride = a.gate_stride = a.st_stride = 0;
+    CHECK(call(a), SFE_OK, "");         // every optional buffer left out, and its stride with it
+    TRUE(go);
+    a = good, a.nb = 0, a.in = a.out = 0, a.out_stride = 0;
+    CHECK(call(a), SFE_OK, "");
+    TRUE(!go);
+    a = good, a.n_in = T31, a.nb = T31;
+    CHECK(call(a), SFE_EINVAL, c.n_in);
+    TRUE(!go);
+    a = good, a.nb = T31 / 2, a.in = 0;
+    CHECK(call(a), SFE_EINVAL, c.count);
+    a = good, a.nb = T31 / 2 - 1, a.n_in = T31 - 1, a.in = 0;
+    CHECK(call(a), SFE_EINVAL, c.null);
+    a = good, a.in = 0, a.out_stride = c.row - 1;
+    CHECK(call(a), SFE_EINVAL, c.null);
+    a = good, a.out = 0, a.out_stride = c.row - 1;
+    CHECK(call(a), SFE_EINVAL, c.null);
+    a = good, a.out_stride = c.row - 1, a.in_stride = n_in - 1;
+    CHECK(call(a), SFE_ERANGE, c.short_out);
+    a = good, a.st_stride = nb - 1, a.in_stride = n_in - 1;
+    CHECK(call(a), SFE_ERANGE, c.short_status);
+    a = good, a.st_stride = nb - 1, a.st = 0;
+    CHECK(call(a), SFE_OK, "");
+    a = good, a.in_stride = n_in - 1, a.base = INT64_MIN;
+    CHECK(call(a), SFE_EINVAL, c.short_in);
+    a = good, a.S = 1, a.in_stride = 0;
+    CHECK(call(a), SFE_OK, "");         // one stream: its stride moves nothing
+    a = good, a.base = INT64_MAX - ((int64_t)1 << 33) + 2, a.step = 0, a.in_stride = T62;
+    CHECK(call(a), SFE_EINVAL, c.starts);
+    a = good, a.base = INT64_MAX - ((int64_t)1 << 33) + 1 - 14, a.in += 1;
+    CHECK(call(a), SFE_EINVAL, c.misaligned);           // the last burst at the bound: the starts pass, a later rule speaks
+    a.step = 8;
+    CHECK(call(a), SFE_EINVAL, c.starts);
+    // each stride at 2^62; an absent buffer's stride is not looked at
+    a = good, a.in_stride = T62 / isz - n_in + 1, a.in += 1;
+    CHECK(call(a), SFE_EINVAL, c.huge);
+    a = good, a.idx_stride = T62, a.in += 1;
+    CHECK(call(a), SFE_EINVAL, c.huge);
+    a.idx = 0, a.in = good.in;
+    CHECK(call(a), SFE_OK, "");
+    a = good, a.gate_stride = T62;
+    CHECK(call(a), SFE_EINVAL, c.huge);
+    a.gate = 0;
+    CHECK(call(a), SFE_OK, "");
+    a = good, a.out_stride = T62;
+    CHECK(call(a), SFE_EINVAL, c.huge);
+    a = good, a.st_stride = SIZE_MAX;
+    CHECK(call(a), SFE_EINVAL, c.huge);
+    a.st = 0;
+    CHECK(call(a), SFE_OK, "");
+    // each buffer off its element's alignment, ahead of any overlap
+    a = good, a.in += isz / 2, a.out = a.in;
+    CHECK(call(a), SFE_EINVAL, c.misaligned);
+    a = good, a.idx += 2, a.out = good.in;
+    CHECK(call(a), SFE_EINVAL, c.misaligned);
+    a = good, a.gate += 2;
+    CHECK(call(a), SFE_EINVAL, c.misaligned);
+    a = good, a.out += 4;
+    CHECK(call(a), SFE_EINVAL, c.misaligned);
+    a = good, a.rec += 2;
+    CHECK(call(a), SFE_EINVAL, c.misaligned);
+    a = good, a.st += 1;
+    CHECK(call(a), SFE_EINVAL, c.misaligned);
+    if (c.chan_row) {
+        a = good, a.chan += 4;
+        CHECK(call(a), SFE_EINVAL, c.misaligned);
+    }
+    if (isz == 2) {
+        a = good, a.in += 2;
+        CHECK(call(a), SFE_OK, "");
+    }
+    // an input against an output, ahead of output against output
+    a = good, a.out = good.in + in_b - 8, a.rec = a.st;
+    CHECK(call(a), SFE_EINVAL, c.in_out);
+    a = good, a.out = good.in + in_b;
+    CHECK(call(a), SFE_OK, "");
+    a = good, a.out = good.in - ou_b;
+    CHECK(call(a), SFE_OK, "");
+    a = good, a.out = good.in - ou_b + 8;
+    CHECK(call(a), SFE_EINVAL, c.in_out);
+    a = good, a.rec = good.idx + (nb + nb) * 4 - 4;
+    CHECK(call(a), SFE_EINVAL, c.in_out);
+    a = good, a.rec = good.idx + (nb + nb) * 4;
+    CHECK(call(a), SFE_OK, "");
+    a = good, a.st = good.gate + (nb + nb) * 4 - 4;
+    CHECK(call(a), SFE_EINVAL, c.in_out);
+    a = good, a.st = good.gate + (nb + nb) * 4;
+    CHECK(call(a), SFE_OK, "");
+    a = good, a.st = good.in;
+    CHECK(call(a), SFE_EINVAL, c.in_out);
+    if (c.chan_row) {
+        a = good, a.chan = good.in + in_b - 8;
+        CHECK(call(a), SFE_EINVAL, c.in_out);
+        a = good, a.chan = good.gate - ch_b + 8;
+        CHECK(call(a), SFE_EINVAL, c.in_out);
+        a = good, a.chan = good.gate - ch_b;
+        CHECK(call(a), SFE_OK, "");
+    }
+    // every pair of outputs; each buffer's extent from its own width
+    a = good, a.rec = good.out + ou_b - 4;
+    CHECK(call(a), SFE_EINVAL, c.out_out);
+    a = good, a.rec = good.out + ou_b;
+    CHECK(call(a), SFE_OK, "");
+    a = good, a.st = good.out - st_b + 4;
+    CHECK(call(a), SFE_EINVAL, c.out_out);
+    a = good, a.st = good.out - st_b;
+    CHECK(call(a), SFE_OK, "");
+    a = good, a.st = good.rec + re_b - 4;
+    CHECK(call(a), SFE_EINVAL, c.out_out);
+    a = good, a.st = good.rec + re_b;
+    CHECK(call(a), SFE_OK, "");
+    if (c.chan_row) {
+        a = good, a.chan = good.out + ou_b - 8;
+        CHECK(call(a), SFE_EINVAL, c.out_out);
+        a = good, a.chan = good.out + ou_b;
+        CHECK(call(a), SFE_OK, "");
+        a = good, a.rec = good.chan + ch_b - 4;
+        CHECK(call(a), SFE_EINVAL, c.out_out);
+        a = good, a.rec = good.chan + ch_b;
+        CHECK(call(a), SFE_OK, "");
+        a = good, a.st = good.chan + ch_b - 4;
+        CHECK(call(a), SFE_EINVAL, c.out_out);
+        a = good, a.chan = good.st - ch_b;
+        CHECK(call(a), SFE_OK, "");
+    }
+    TRUE(go);
+}
+
+static void test_windows_all()
+{
+    const WindowCase burst{"burst_process_stream", "n_sym", 16, 0, "burst_process_stream: n_in = 2147483648 must be below 2^31 per call",
+                           "burst_process_stream: n_streams * n_bursts = 2 * 1073741824 must be below 2^31 per call",
+                           "burst_process_stream: null buffer",
+                           "burst_process_stream: out_stride 15 < n_sym = 16 or status_stride 3 < n_bursts = 3",
+                           "burst_process_stream: out_stride 16 < n_sym = 16 or status_stride 2 < n_bursts = 3",
+                           "burst_process_stream: in_stride 999 < n_in 1000 with 2 streams",
+                           "burst_process_stream: start_base + b * start_step must stay within +-(2^63 - 2^33) for every burst",
+                           "burst_process_stream: a stride is so large that its buffer's byte range reaches 2^62",
+                           "burst_process_stream: buffers must be aligned to their element (cf32 8 B, u8 (I,Q) pairs 2 B, indices, gates, records and "
+                           "statuses 4 B)",
+                           "burst_process_stream: input and output ranges overlap (in-place operation is not supported)",
+                           "burst_process_stream: the output ranges overlap one another"};
+    const WindowCase ofdm{"ofdm_process_stream", "n_data * Nd", 3 * 48, 64, "ofdm_process_stream: n_in = 2147483648 must be below 2^31 per call",
+                          "ofdm_process_stream: n_streams * n_bursts = 2 * 1073741824 must be below 2^31 per call",
+                          "ofdm_process_stream: null buffer",
+                          "ofdm_process_stream: out_stride 143 < n_data * Nd = 144 or status_stride 3 < n_bursts = 3",
+                          "ofdm_process_stream: out_stride 144 < n_data * Nd = 144 or status_stride 2 < n_bursts = 3",
+                          "ofdm_process_stream: in_stride 999 < n_in 1000 with 2 streams",
+                          "ofdm_process_stream: start_base + b * start_step must stay within +-(2^63 - 2^33) for every burst",
+                          "ofdm_process_stream: a stride is so large that its buffer's byte range reaches 2^62",
+                          "ofdm_process_stream: buffers must be aligned to their element (cf32 8 B, u8 (I,Q) pairs 2 B, indices, gates, records and "
+                          "statuses 4 B)",
+                          "ofdm_process_stream: input and output ranges overlap (in-place operation is not supported)",
+                          "ofdm_process_stream: the output ranges overlap one another"};
+    for (size_t isz : {(size_t)8, (size_t)2}) {
+        test_windows(burst, isz);
+        test_windows(ofdm, isz);
+    }
+}
+
+// ---- frames
+struct FrameCase {
+    const char *who;
+    FrameNouns nn;
+    size_t in_row, ie;
+    bool even_starts;       // under TX10
+    const char *place, *null, *short_in, *huge, *misaligned, *in_out;
+};
+
+static void test_frames(const FrameCase &c, bool tx10)
+{
+    const int F = 8;
+    const size_t nb = 3, n_out = 40, in_b = (2 * c.in_row + c.in_row) * c.ie, out_b = tx10 ? n_out / 2 * 5 : n_out * 8;
+    const uintptr_t IN = 0x10000, OUT = 0x20000;
+    bool go;
+    auto call = [&](uintptr_t in, size_t is, size_t nb_, int64_t base, int64_t step, uintptr_t out, size_t n_out_) {
+        go = true;
+        return check_frames(c.who, c.nn, F, tx10, tx10 && c.even_starts, P(in), is, c.in_row, c.ie, nb_, base, step, P(out), n_out_, &go);
+    };
+    const size_t is = c.in_row;
+    CHECK(call(IN, is, nb, 0, 16, OUT, n_out), SFE_OK, "");
+    TRUE(go);
+    CHECK(call(0, 0, 0, -1, -1, 0, 0), SFE_OK, "");             // no stream: nothing to do
+    TRUE(!go);
+    CHECK(call(0, 0, 0, -1, -1, OUT, n_out), SFE_OK, "");       // no burst: a stream of zeros
+    TRUE(go);
+    CHECK(call(0, 0, nb, -1, 16, 0, n_out), SFE_EINVAL, c.place);
+    TRUE(!go);
+    CHECK(call(IN, is - 1, nb, 0, 16, 0, n_out), SFE_EINVAL, c.null);
+    CHECK(call(0, is - 1, nb, 0, 16, OUT, n_out), SFE_EINVAL, c.null);
+    CHECK(call(IN, is - 1, nb, 0, 16, OUT + 4, n_out), SFE_ERANGE, c.short_in);
+    CHECK(call(IN, is - 1, 0, 0, 16, OUT, n_out), SFE_OK, "");          // no burst: the stride is not looked at
+    CHECK(call(IN, T62, nb, 0, 16, OUT + 4, n_out), SFE_EINVAL, c.huge);
+    CHECK(call(IN, SIZE_MAX, nb, 0, 16, OUT, n_out), SFE_EINVAL, c.huge);
+    CHECK(call(IN, T62, 1, 0, 16, OUT, n_out), SFE_OK, "");             // one burst: the stride moves nothing
+    if (tx10) {
+        CHECK(call(IN, is, nb, 0, 16, OUT + 1, n_out), SFE_OK, "");
+    } else {
+        CHECK(call(IN, is, nb, 0, 16, OUT + 4, n_out), SFE_EINVAL, c.misaligned);
+        CHECK(call(IN, is, nb, 0, 16, IN + 1, n_out), SFE_EINVAL, c.misaligned);
+    }
+    if (c.ie > 1) {
+        CHECK(call(IN + c.ie / 2, is, nb, 0, 16, IN, n_out), SFE_EINVAL, c.misaligned);
+        CHECK(call(IN + 4, is, 0, 0, 16, OUT, n_out), SFE_EINVAL, c.misaligned);
+    } else {
+        CHECK(call(IN + 1, is, nb, 0, 16, OUT, n_out), SFE_OK, "");
+    }
+    CHECK(call(IN, is, nb, 0, 16, IN, n_out), SFE_EINVAL, c.in_out);
+    if (c.ie == 1) {        // to the byte, by the output's own width: 8 bytes a sample, or 5 bytes a pair
+        CHECK(call(OUT + out_b, is, nb, 0, 16, OUT, n_out), SFE_OK, "");
+        CHECK(call(OUT + out_b - 1, is, nb, 0, 16, OUT, n_out), SFE_EINVAL, c.in_out);
+    }
+    CHECK(call(OUT + ((out_b + 7) & ~(size_t)7), is, nb, 0, 16, OUT, n_out), SFE_OK, "");
+    CHECK(call(OUT + ((out_b - 1) & ~(size_t)7), is, nb, 0, 16, OUT, n_out), SFE_EINVAL, c.in_out);
+    CHECK(call(OUT - in_b, is, nb, 0, 16, OUT, n_out), SFE_OK, "");
+    CHECK(call(OUT - in_b + 8, is, nb, 0, 16, OUT, n_out), SFE_EINVAL, c.in_out);
+    CHECK(call(OUT, is, 0, 0, 16, OUT, n_out), SFE_OK, "");             // no burst: nothing is read
+    TRUE(go);
+}
+
+static void test_frames_all()
+{
+    const FrameCase mod{"mod_process_stream",
+                        FrameNouns{"ceil(n_info / 8) = ", "", "payloads'", "cf32 output 8 B; TX10 output and payload bytes need none"},
+                        5, 1, false, "mod_process_stream: start_base = -1 must not be negative", "mod_process_stream: null buffer",
+                        "mod_process_stream: in_stride 4 < ceil(n_info / 8) = 5",
+                        "mod_process_stream: in_stride is so large that the payloads' byte range reaches 2^62",
+                        "mod_process_stream: buffers must be aligned to their element (cf32 output 8 B; TX10 output and payload bytes need none)",
+                        "mod_process_stream: input and output ranges overlap (in-place operation is not supported)"};
+    const char *omod_al = "ofdmmod_process_stream: buffers must be aligned to their element (cf32 input and output 8 B; TX10 output and coded bytes "
+                          "need none)";
+    const FrameCase bits{"ofdmmod_process_stream",
+                         FrameNouns{"the ", " bytes a burst reads", "input's", "cf32 input and output 8 B; TX10 output and coded bytes need none"},
+                         18, 1, true, "ofdmmod_process_stream: start_base = -1 must not be negative", "ofdmmod_process_stream: null buffer",
+                         "ofdmmod_process_stream: in_stride 17 < the 18 bytes a burst reads",
+                         "ofdmmod_process_stream: in_stride is so large that the input's byte range reaches 2^62", omod_al,
+                         "ofdmmod_process_stream: input and output ranges overlap (in-place operation is not supported)"};
+    const FrameCase symbols{"ofdmmod_process_stream",
+                            FrameNouns{"the ", " cf32 symbols a burst reads", "input's", "cf32 input and output 8 B; TX10 output and coded bytes need none"},
+                            144, 8, true, "ofdmmod_process_stream: start_base = -1 must not be negative", "ofdmmod_process_stream: null buffer",
+                            "ofdmmod_process_stream: in_stride 143 < the 144 cf32 symbols a burst reads",
+                            "ofdmmod_process_stream: in_stride is so large that the input's byte range reaches 2^62", omod_al,
+                            "ofdmmod_process_stream: input and output ranges overlap (in-place operation is not supported)"};
+    for (bool tx10 : {false, true}) {
+        test_frames(mod, tx10);
+        test_frames(bits, tx10);
+        test_frames(symbols, tx10);
+    }
+    // the starts rule reaches the stream call of ofdmmod alone
+    bool go;
+    CHECK(check_frames("ofdmmod_process_stream", bits.nn, 8, true, true, P(0x10000), 18, 18, 1, 2, 1, 9, P(0x20000), 40, &go), SFE_EINVAL,
+          "ofdmmod_process_stream: start_base = 1 and start_step = 9 must be even with SFE_FMT_TX10 (a frame starts on a 5-byte group)");
+    CHECK(check_frames("mod_process_stream", mod.nn, 8, true, false, P(0x10000), 5, 5, 1, 2, 1, 9, P(0x20000), 40, &go), SFE_OK, "");
+}
+
+int main()
+{
+    test_span_bytes();
+    test_overlap();
+    test_outputs_overlap();
+    test_check_starts();
+    test_check_place();
+    test_rows_all();
+    test_windows_all();
+    test_frames_all();
+    if (g_fails) {
+        printf("call checks: %d of %d FAILED\n", g_fails, g_checks);
+        return 1;
+    }
+    printf("call checks ok: %d checks\n", g_checks);
+    return 0;
+}

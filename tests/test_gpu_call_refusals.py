@@ -1,0 +1,383 @@
+"""The call checks the burst chain's blocks share (csrc/call_checks.h) through the real C ABI, one table row per entry
+point -- vit, reed and ldpc (rows), burst and ofdm (windows), mod and ofdmmod (frames) -- at the shapes of the blocks' own
+test_refusals_launch_nothing.  Each shared rule refuses one bad call with its return code and the WHOLE message: the
+prefix and the block's nouns are wired per entry point, and only the whole text tells a swap.  The outputs are poisoned
+before the refused calls and bit-identical after them; then one good call gives the block's plan bit for bit (burst and
+ofdm, whose plans are float64 twins held to a tolerance by their own tests: a fresh handle through the wrapper).  The
+format setters that are one rule each get a row too.  Every bad call is refused on the host before any launch.  `-m gpu`."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import ldpc_cases as lc
+import mod_checks as mchk
+import ofdm_cases as oc
+import ofdmmod_cases as omc
+import reed_cases as rc
+from simplefe_amd import synth
+from vit_cases import rows_of
+
+pytestmark = pytest.mark.gpu
+F32 = np.float32
+POISON = 0x7FD5A5A5
+T31 = 1 << 31
+
+NULL = "%s: null buffer"
+HUGE = "%s: a stride is so large that its buffer's byte range reaches 2^62"
+ALIGN = "%s: buffers must be aligned to their element (%s)"
+IN_OUT = "%s: input and output ranges overlap (in-place operation is not supported)"
+OUT_OUT = "%s: the output ranges overlap one another"
+STARTS = "%s: start_base + b * start_step must stay within +-(2^63 - 2^33) for every burst"
+WINDOW_ELEMENTS = "cf32 8 B, u8 (I,Q) pairs 2 B, indices, gates, records and statuses 4 B"
+
+
+@pytest.fixture(scope="module")
+def api():
+    from simplefe_amd import api as a
+    return a
+
+
+@pytest.fixture(scope="module")
+def L():
+    from simplefe_amd import lib
+    return lib
+
+
+def _poisoned(api, n_words):
+    return api.DeviceArray.from_numpy(np.full(n_words, POISON, np.uint32).view(F32))
+
+
+def _words(d, n=None):
+    return d.to_numpy(n).view(np.uint32)
+
+
+class Entry:
+    """One entry point: its function, the names of its arguments between the handle and the counter, one good call, the
+    poisoned outputs, the refused calls as (overrides, return code, whole message), and what the good call must give."""
+
+    def __init__(self, L, who, handle, order, good, outs, bad, counted, check, keep=()):
+        self.fn = getattr(L.load(), "sfe_dsp_" + who)
+        self.who, self.handle, self.order, self.good, self.outs, self.bad, self.counted, self.check, self.keep = (
+            who, handle, order, good, outs, bad, counted, check, keep)
+
+    def call(self, k, **over):
+        a = dict(self.good, **over)
+        return self.fn(a.pop("hh", self.handle._h), *[a[name] for name in self.order], C.byref(k), None)
+
+
+def _rows_bad(who, count, elements, short_in, short_out, g, d_in, in_bytes, d_si, d_out, out_bytes, d_rec, decode, sym=None):
+    """The refusals of a row codec: g the good call, in_bytes and out_bytes the extents of its input and output."""
+    n = g["n"]
+    bad = [(dict(n=T31), -1, "%s: %s = 2147483648 must be below 2^31 per call" % (who, count)),
+           (dict(pi=None), -1, NULL % who), (dict(po=None), -1, NULL % who),
+           (dict(istride=g["istride"] - 1), -6, short_in), (dict(ostride=g["ostride"] - 1), -6, short_out),
+           (dict(istride=1 << 62), -1, HUGE % who), (dict(ostride=1 << 62), -1, HUGE % who),
+           (dict(po=d_in.ptr + in_bytes - 1), -1, IN_OUT % who), (dict(pi=d_out.ptr + 8 * ((out_bytes - 1) // 8)), -1, IN_OUT % who)]
+    if decode:
+        al = ALIGN % (who, elements)
+        bad += [(dict(psi=d_si.ptr + 2), -1, al), (dict(pr=d_rec.ptr + 2), -1, al), (dict(ps=g["ps"] + 1), -1, al),
+                (dict(pr=d_in.ptr), -1, IN_OUT % who), (dict(ps=d_si.ptr + 4 * (n - 1)), -1, IN_OUT % who),
+                (dict(pr=d_out.ptr + 4), -1, OUT_OUT % who), (dict(ps=d_out.ptr + 4 * ((out_bytes - 1) // 4)), -1, OUT_OUT % who),
+                (dict(ps=d_rec.ptr + 4), -1, OUT_OUT % who)]
+    if sym:
+        bad += sym
+    return bad
+
+
+DEC = ("pi", "istride", "psi", "n", "po", "ostride", "pr", "ps")
+ENC = ("pi", "istride", "n", "po", "ostride")
+
+
+def _decoder(api, L, who, h, count, elements, short_in, short_out, x_floats_or_bytes, in_bytes, istride, ostride, n, rec_words, want, sym=None):
+    d_in = x_floats_or_bytes
+    d_si = api.DeviceArray.from_numpy(np.zeros(64, F32))
+    d_out, d_rec, d_st = (_poisoned(api, 256) for _ in range(3))
+    g = dict(pi=d_in.ptr, istride=istride, psi=d_si.ptr, n=n, po=d_out.ptr, ostride=ostride, pr=d_rec.ptr, ps=d_st.ptr)
+    bad = _rows_bad(who, count, elements, short_in, short_out, g, d_in, in_bytes, d_si, d_out, n * ostride, d_rec, True, sym)
+
+    def check():
+        assert np.array_equal(d_out.to_numpy().view(np.uint8)[:n * ostride].reshape(n, ostride), want[0])
+        assert np.array_equal(_words(d_rec, rec_words * n).reshape(n, rec_words), want[1])
+        assert np.array_equal(d_st.to_numpy(n).view(np.int32), want[2])
+
+    return Entry(L, who, h, DEC, g, [d_out, d_rec, d_st], bad, n, check, keep=(d_in, d_si))
+
+
+def _encoder(api, L, who, h, count, short_in, short_out, rows, istride, ostride, n, want):
+    d_in = api.DeviceArray.from_bytes(np.concatenate([rows.ravel(), np.zeros(64, np.uint8)]))
+    d_out = _poisoned(api, 256)
+    g = dict(pi=d_in.ptr, istride=istride, n=n, po=d_out.ptr, ostride=ostride)
+    bad = _rows_bad(who, count, None, short_in, short_out, g, d_in, n * istride, None, d_out, n * ostride, None, False)
+
+    def check():
+        assert np.array_equal(d_out.to_numpy().view(np.uint8)[:n * ostride].reshape(n, ostride), want)
+
+    return Entry(L, who, h, ENC, g, [d_out], bad, n, check, keep=(d_in,))
+
+
+def _vit(api, L):
+    K, gen, n_info, nb = 7, (0o171, 0o133), 64, 3
+    h = api.Vit(K, gen, n_info)
+    hb = api.Vit(K, gen, n_info, in_mode=L.VIT_IN_BPSK, skip=4)
+    assert (h.n_soft, h.n_bytes) == (140, 8)
+    x = rows_of(api, K, gen, n_info, None, True, nb, 41)
+    who = "vit_process_stream"
+    el = "soft values 4 B, symbols 8 B, records and statuses 4 B"
+    d_in = api.DeviceArray.from_numpy(np.concatenate([x.ravel(), np.zeros(64, F32)]))
+    sym = [(dict(pi=d_in.ptr + 2), -1, ALIGN % (who, el)), (dict(hh=hb._h, pi=d_in.ptr + 4, istride=144), -1, ALIGN % (who, el)),
+           (dict(hh=hb._h, istride=143), -6, "vit_process_stream: in_stride 143 < the 144 elements of a burst's row, or out_stride 8 < ceil(n_info / 8) = 8")]
+    e = _decoder(api, L, who, h, "n_bursts", el,
+                 "vit_process_stream: in_stride 139 < the 140 elements of a burst's row, or out_stride 8 < ceil(n_info / 8) = 8",
+                 "vit_process_stream: in_stride 140 < the 140 elements of a burst's row, or out_stride 7 < ceil(n_info / 8) = 8",
+                 d_in, 4 * nb * 140, 140, 8, nb, 2, api.vit_plan(K, gen, n_info, x=x), sym)
+    e.keep += (hb,)
+    return e
+
+
+def _reed_parts(api):
+    shape, nf = rc.SHAPES["C"], 3
+    frames, wh = rc.many("C", nf)
+    h = api.Reed(*shape, whiten=wh)
+    assert (h.payload_bytes, h.frame_bytes) == (96, 120)
+    return shape, nf, frames, wh, h
+
+
+def _reed(api, L):
+    shape, nf, frames, wh, h = _reed_parts(api)
+    d_in = api.DeviceArray.from_bytes(np.concatenate([frames.ravel(), np.zeros(64, np.uint8)]))
+    return _decoder(api, L, "reed_process_stream", h, "n_frames", "records and statuses 4 B; payloads and frames need none",
+                    "reed_process_stream: in_stride 119 < the 120 bytes read per frame, or out_stride 96 < the 96 bytes written per frame",
+                    "reed_process_stream: in_stride 120 < the 120 bytes read per frame, or out_stride 95 < the 96 bytes written per frame",
+                    d_in, nf * 120, 120, 96, nf, 2, api.reed_plan(*shape, whiten=wh, data=frames))
+
+
+def _reed_enc(api, L):
+    shape, nf, frames, wh, h = _reed_parts(api)
+    pay = api.reed_plan(*shape, whiten=wh, data=frames)[0]
+    return _encoder(api, L, "reed_encode_stream", h, "n_frames",
+                    "reed_encode_stream: in_stride 95 < the 96 bytes read per frame, or out_stride 120 < the 120 bytes written per frame",
+                    "reed_encode_stream: in_stride 96 < the 96 bytes read per frame, or out_stride 119 < the 120 bytes written per frame",
+                    pay, 96, 120, nf, api.reed_plan(*shape, whiten=wh, data=pay, encode=True))
+
+
+LDPC_ELEMENTS = "soft values 4 B, symbols 8 B, records and statuses 4 B; payloads and codewords need none"
+
+
+def _ldpc_parts(api):
+    s, Z = lc.CASES["B"]
+    h = api.Ldpc(s, Z, lc.SCALE, 12, 0, 32)
+    assert (h.n, h.k_bytes, h.n_bytes) == (648, 41, 81)
+    return s, Z, 3, h
+
+
+def _ldpc(api, L):
+    s, Z, nw, h = _ldpc_parts(api)
+    hq = api.Ldpc(s, Z, lc.SCALE, 12, 0, 32, in_mode=L.VIT_IN_QPSK, skip=4)
+    x = lc.many("B", nw)
+    who = "ldpc_process_stream"
+    d_in = api.DeviceArray.from_numpy(np.concatenate([x.ravel(), np.zeros(64, F32)]))
+    sym = [(dict(pi=d_in.ptr + 2), -1, ALIGN % (who, LDPC_ELEMENTS)), (dict(hh=hq._h, pi=d_in.ptr + 4, istride=328), -1, ALIGN % (who, LDPC_ELEMENTS)),
+           (dict(hh=hq._h, istride=327), -6,
+            "ldpc_process_stream: in_stride 327 < the 328 elements read per codeword, or out_stride 41 < the 41 bytes written per codeword")]
+    e = _decoder(api, L, who, h, "n_words", LDPC_ELEMENTS,
+                 "ldpc_process_stream: in_stride 647 < the 648 elements read per codeword, or out_stride 41 < the 41 bytes written per codeword",
+                 "ldpc_process_stream: in_stride 648 < the 648 elements read per codeword, or out_stride 40 < the 41 bytes written per codeword",
+                 d_in, 4 * nw * 648, 648, 41, nw, 3, api.ldpc_plan(s, Z, lc.SCALE, 12, 0, 32, x=x), sym)
+    e.keep += (hq,)
+    return e
+
+
+def _ldpc_enc(api, L):
+    s, Z, nw, h = _ldpc_parts(api)
+    pay = api.ldpc_plan(s, Z, lc.SCALE, 12, 0, 32, x=lc.many("B", nw))[0]
+    return _encoder(api, L, "ldpc_encode_stream", h, "n_words",
+                    "ldpc_encode_stream: in_stride 40 < the 41 elements read per codeword, or out_stride 81 < the 81 bytes written per codeword",
+                    "ldpc_encode_stream: in_stride 41 < the 41 elements read per codeword, or out_stride 80 < the 81 bytes written per codeword",
+                    pay, 41, 81, nw, api.ldpc_plan(s, Z, data=pay))
+
+
+WIN = ("pi", "n_in", "in_stride", "px", "xstride", "pg", "gstride", "n_bursts", "base", "step", "po", "ostride")
+
+
+def _windows(api, L, who, h, fresh, x, row, row_name, base, chan_row):
+    """burst (chan_row 0) and ofdm: S = 2 streams of n samples, 3 windows each."""
+    S, nb = x.shape[0], 3
+    n = x.shape[1]
+    d_in = api.DeviceArray.from_numpy(np.concatenate([x.view(F32).ravel(), np.zeros(64, F32)]))
+    d_idx, d_gate = api.DeviceArray.from_numpy(np.zeros(S * nb + 8, F32)), api.DeviceArray.from_numpy(np.ones(S * nb + 8, F32))
+    words = S * nb * max(row, chan_row) * 2 + 64
+    d_out, d_ch, d_rec, d_st = (_poisoned(api, words) for _ in range(4))
+    order = WIN + (("pc",) if chan_row else ()) + ("pr", "ps", "sstride")
+    g = dict(pi=d_in.ptr, n_in=n, in_stride=n, px=d_idx.ptr, xstride=nb, pg=d_gate.ptr, gstride=nb, n_bursts=nb, base=base, step=2, po=d_out.ptr,
+             ostride=row, pc=d_ch.ptr, pr=d_rec.ptr, ps=d_st.ptr, sstride=nb)
+    al = ALIGN % (who, WINDOW_ELEMENTS)
+    short = "%s: out_stride %%d < %s = %d or status_stride %%d < n_bursts = 3" % (who, row_name, row)
+    bad = [(dict(n_in=T31, in_stride=T31), -1, "%s: n_in = 2147483648 must be below 2^31 per call" % who),
+           (dict(n_bursts=1 << 30, sstride=1 << 30), -1, "%s: n_streams * n_bursts = 2 * 1073741824 must be below 2^31 per call" % who),
+           (dict(pi=None), -1, NULL % who), (dict(po=None), -1, NULL % who),
+           (dict(ostride=row - 1), -6, short % (row - 1, 3)), (dict(sstride=nb - 1), -6, short % (row, 2)),
+           (dict(in_stride=n - 1), -1, "%s: in_stride %d < n_in %d with 2 streams" % (who, n - 1, n)),
+           (dict(base=2 ** 63 - 1, step=0), -1, STARTS % who), (dict(base=-2 ** 63, step=0), -1, STARTS % who),
+           (dict(base=0, step=2 ** 62), -1, STARTS % who), (dict(base=0, step=-2 ** 62), -1, STARTS % who),
+           (dict(in_stride=1 << 61), -1, HUGE % who), (dict(xstride=1 << 62), -1, HUGE % who), (dict(gstride=1 << 62), -1, HUGE % who),
+           (dict(ostride=1 << 60), -1, HUGE % who), (dict(sstride=1 << 61), -1, HUGE % who),
+           (dict(pi=d_in.ptr + 4), -1, al), (dict(px=d_idx.ptr + 2), -1, al), (dict(pg=d_gate.ptr + 1), -1, al), (dict(po=d_out.ptr + 4), -1, al),
+           (dict(pr=d_rec.ptr + 2), -1, al), (dict(ps=d_st.ptr + 3), -1, al),
+           (dict(po=d_in.ptr + 8 * (2 * n - 1)), -1, IN_OUT % who), (dict(pr=d_idx.ptr + 4), -1, IN_OUT % who), (dict(ps=d_gate.ptr), -1, IN_OUT % who),
+           (dict(pr=d_out.ptr + 8), -1, OUT_OUT % who), (dict(ps=d_out.ptr + 4 * (S * nb * row * 2 - 1)), -1, OUT_OUT % who),
+           (dict(ps=d_rec.ptr + 4), -1, OUT_OUT % who)]
+    if chan_row:
+        bad += [(dict(pc=d_ch.ptr + 4), -1, al), (dict(pc=d_in.ptr), -1, IN_OUT % who), (dict(pc=d_gate.ptr), -1, IN_OUT % who),
+                (dict(pc=d_out.ptr + 8 * (S * nb * row - 1)), -1, OUT_OUT % who), (dict(pr=d_ch.ptr + 8 * (S * nb * chan_row - 1)), -1, OUT_OUT % who),
+                (dict(ps=d_ch.ptr + 8), -1, OUT_OUT % who)]
+
+    def check():
+        want = fresh(x, np.zeros((S, nb)), np.ones((S, nb)))       # symbols, (channel,) record, status
+        assert not want[-1].any()
+        got = [d_out.to_numpy(S * nb * row * 2)] + ([d_ch.to_numpy(S * nb * chan_row * 2)] if chan_row else []) + [d_rec.to_numpy(S * nb * 8)]
+        for a, b in zip(got, want[:-1]):
+            assert np.array_equal(a.view(np.uint32), np.ascontiguousarray(b).view(np.uint32).ravel())
+        assert np.array_equal(d_st.to_numpy(S * nb).view(np.int32), want[-1].ravel())
+
+    return Entry(L, who, h, order, g, [d_out, d_rec, d_st] + ([d_ch] if chan_row else []), bad, nb, check, keep=(d_in, d_idx, d_gate, d_ch))
+
+
+def _burst(api, L):
+    sps, N, Lp, lag = 4, 32, 8, 1
+    n = (N + 2) * sps + 8
+    sig = [synth.burst_signal(synth.psk_symbols(n // sps + 2, 4, seed=synth.SEED + s), sps, n, 0, 0.37, 0.013, 0.5, 0.6) for s in (41, 42)]
+    pre = synth.psk_symbols(Lp + 2, 4, seed=synth.SEED + 7)[:Lp].astype(np.complex64)
+    new = lambda: api.Burst(pre, sps, N, lag, n_streams=2)
+    return _windows(api, L, "burst_process_stream", new(), lambda x, idx, gate: new().demodulate(x, idx=idx, gate=gate, start_base=sps, start_step=2),
+                    np.stack(sig), N, "n_sym", sps, 0)
+
+
+def _ofdm(api, L):
+    x0, starts, _ = oc.stream("n64")
+    n = oc.reach("n64") + 8
+    x = np.stack([x0[int(starts[0]):][:n], x0[int(starts[1]):][:n]])
+    a = oc.shape_args("n64", 0)
+    h = api.Ofdm(n_streams=2, **a)
+    return _windows(api, L, "ofdm_process_stream", h, lambda x, idx, gate: api.Ofdm(n_streams=2, **a).receive(x, idx=idx, gate=gate, start_step=2), x,
+                    h.n_sym, "n_data * Nd", 0, h.n_fft)
+
+
+FRM = ("pi", "istride", "n_bursts", "base", "step", "po", "n")
+PLACE_2_31 = "%s: n_out = %d and n_bursts = %d must be below 2^31"
+PLACE_END = "%s: the last frame ends behind the stream's n_out = %d samples"
+
+
+def _frames(api, L, who, h, ht, data, F, row, short, range_of, elements, want, extra):
+    nb, n_out = 3, 3 * F + 6
+    d_in = api.DeviceArray.from_bytes(np.concatenate([data.ravel(), np.zeros(64, np.uint8)]))
+    out = _poisoned(api, 2 * n_out + 64)
+    g = dict(pi=d_in.ptr, istride=row, n_bursts=nb, base=2, step=F, po=out.ptr, n=n_out)
+    bad = [(dict(n=T31), -1, PLACE_2_31 % (who, T31, nb)), (dict(n_bursts=T31), -1, PLACE_2_31 % (who, n_out, T31)),
+           (dict(hh=ht._h, n=n_out - 1), -1, "%s: n_out = %d must be even with SFE_FMT_TX10 (whole 5-byte groups)" % (who, n_out - 1)),
+           (dict(base=-1), -1, "%s: start_base = -1 must not be negative" % who),
+           (dict(step=F - 1), -1, "%s: start_step = %d is below the frame's F = %d samples (frames must not overlap)" % (who, F - 1, F)),
+           (dict(base=7), -1, PLACE_END % (who, n_out)), (dict(n=n_out - 5), -1, PLACE_END % (who, n_out - 5)),
+           (dict(po=None), -1, NULL % who), (dict(pi=None), -1, NULL % who), (dict(istride=row - 1), -6, short),
+           (dict(n_bursts=2, istride=1 << 62), -1, "%s: in_stride is so large that the %s byte range reaches 2^62" % (who, range_of)),
+           (dict(po=out.ptr + 4), -1, ALIGN % (who, elements)),
+           (dict(po=d_in.ptr + 8 * ((nb * row - 1) // 8)), -1, IN_OUT % who), (dict(pi=out.ptr + 8 * n_out - 1), -1, IN_OUT % who)] + extra
+
+    def check():
+        assert np.array_equal(_words(out, 2 * n_out), want(n_out).view(np.uint32))
+
+    return Entry(L, who, h, FRM, g, [out], bad, n_out, check, keep=(d_in, ht))
+
+
+def _mod(api, L):
+    K, gen, n_info, sps = 7, (0o171, 0o133), 64, 4
+    taps = mchk.rc_taps(4, 2)
+    h, ht = api.Mod(K, gen, n_info, taps, sps, amp=0.5), api.Mod(K, gen, n_info, taps, sps, amp=0.5, out_fmt=L.FMT_TX10)
+    assert (h.frame_len, h.n_bytes) == (576, 8)
+    data = mchk.payload_bytes(n_info, 3, 41)
+    return _frames(api, L, "mod_process_stream", h, ht, data, 576, 8, "mod_process_stream: in_stride 7 < ceil(n_info / 8) = 8", "payloads'",
+                   "cf32 output 8 B; TX10 output and payload bytes need none",
+                   lambda n_out: api.mod_plan(K, gen, n_info, taps, sps, amp=0.5, data=data, n_out=n_out, start_base=2, start_step=576),
+                   [(dict(hh=ht._h, base=3, n=3 * 576 + 8), 0, "")])      # odd starts under TX10: the modulator's own business
+
+
+def _ofdmmod(api, L):
+    args = omc.shape_args("n64", amp=0.5)
+    h, ht = api.OfdmMod(**args), api.OfdmMod(**{**args, "out_fmt": L.FMT_TX10})
+    hs = api.OfdmMod(**{**args, "in_mode": L.OFDMMOD_IN_SYMBOLS})
+    assert (h.frame_len, h.n_in, hs.n_in) == (640, 81, 324)
+    who, el = "ofdmmod_process_stream", "cf32 input and output 8 B; TX10 output and coded bytes need none"
+    data = omc.rows(args, 3, 41)
+    d_sym = api.DeviceArray(2 * 3 * 324 + 4)
+    even = "ofdmmod_process_stream: start_base = %d and start_step = %d must be even with SFE_FMT_TX10 (a frame starts on a 5-byte group)"
+    e = _frames(api, L, who, h, ht, data, 640, 81, "ofdmmod_process_stream: in_stride 80 < the 81 bytes a burst reads", "input's", el,
+                lambda n_out: api.ofdmmod_plan(**args, data=data, n_out=n_out, start_base=2, start_step=640),
+                [(dict(hh=ht._h, base=3), -1, even % (3, 640)), (dict(hh=ht._h, base=0, step=641), -1, even % (0, 641)),
+                 (dict(hh=hs._h, pi=d_sym.ptr, istride=323), -6, "ofdmmod_process_stream: in_stride 323 < the 324 cf32 symbols a burst reads"),
+                 (dict(hh=hs._h, pi=d_sym.ptr + 4, istride=324), -1, ALIGN % (who, el))])
+    e.keep += (hs, d_sym)
+    return e
+
+
+ENTRIES = {"vit_process_stream": _vit, "reed_encode_stream": _reed_enc, "reed_process_stream": _reed, "ldpc_encode_stream": _ldpc_enc,
+           "ldpc_process_stream": _ldpc, "burst_process_stream": _burst, "ofdm_process_stream": _ofdm, "mod_process_stream": _mod,
+           "ofdmmod_process_stream": _ofdmmod}
+
+
+@pytest.mark.parametrize("name", list(ENTRIES))
+def test_shared_rules_refuse_with_the_entry_points_words(api, L, name):
+    e = ENTRIES[name](api, L)
+    assert e.who == name and (L.SFE_EINVAL, L.SFE_ERANGE) == (-1, -6)
+    lib = L.load()
+    k = C.c_size_t(7)
+    for over, code, text in e.bad:
+        if code == L.SFE_OK:            # a call another block of the family refuses: accepted here, and it may write
+            continue
+        k.value = 7
+        assert e.call(k, **over) == code, (over, lib.sfe_dsp_last_error())
+        assert lib.sfe_dsp_last_error() == text.encode() and k.value == 0, (over, lib.sfe_dsp_last_error())
+    api.sync()
+    for d in e.outs:
+        assert (_words(d) == POISON).all(), "a refused call wrote"
+    assert e.call(k) == L.SFE_OK and k.value == e.counted
+    api.sync()
+    e.check()
+    for over, code, text in e.bad:
+        if code == L.SFE_OK:
+            assert e.call(k, **over) == L.SFE_OK, (over, lib.sfe_dsp_last_error())
+    api.sync()
+
+
+def _setters(api):
+    """(prefix, a handle at a small shape, the setter, the second format's name and value)"""
+    lp = synth.lowpass_taps(16, 0.25)
+    w = np.hanning(256).astype(F32)
+    tpl = np.ones(13, np.complex64)
+    a = oc.shape_args("n64", 0)
+    pre = synth.psk_symbols(10, 4, seed=synth.SEED + 7)[:8].astype(np.complex64)
+    return [("chan", lambda: api.Chan(lp, 4, 4), "set_input_format", "SFE_FMT_U8", 1),
+            ("ddc", lambda: api.Ddc(synth.lowpass_taps(24, 0.5 / 3), 3, [0.125, -0.3]), "set_input_format", "SFE_FMT_U8", 1),
+            ("psd", lambda: api.Psd(w, 128, 2), "set_input_format", "SFE_FMT_U8", 1),
+            ("corr", lambda: api.Corr(tpl, 3840), "set_input_format", "SFE_FMT_U8", 1),
+            ("iir", lambda: api.Iir(synth.iir_dc_blocker(0.995)), "set_input_format", "SFE_FMT_U8", 1),
+            ("beam", lambda: api.Beam(np.ones((2, 3), np.complex64)), "set_input_format", "SFE_FMT_U8", 1),
+            ("cov", lambda: api.Cov(2), "set_input_format", "SFE_FMT_U8", 1),
+            ("burst", lambda: api.Burst(pre, 4, 32, 1), "set_input_format", "SFE_FMT_U8", 1),
+            ("ofdm", lambda: api.Ofdm(**a), "set_input_format", "SFE_FMT_U8", 1),
+            ("combine", lambda: api.Combiner(lp, 4, 4), "set_output_format", "SFE_FMT_TX10", 2)]
+
+
+@pytest.mark.parametrize("row", range(10), ids=["chan", "ddc", "psd", "corr", "iir", "beam", "cov", "burst", "ofdm", "combine"])
+def test_format_setters(api, L, row):
+    """A format outside the two allowed, and a null handle: SFE_EINVAL with the setter's sentence; each allowed one: SFE_OK."""
+    prefix, new, setter, other_name, other = _setters(api)[row]
+    assert (L.FMT_F32, getattr(L, other_name[4:])) == (0, other)
+    lib = L.load()
+    fn = getattr(lib, "sfe_dsp_%s_%s" % (prefix, setter))
+    text = ("%s_%s: null handle or a format other than SFE_FMT_F32 / %s" % (prefix, setter, other_name)).encode()
+    h = new()
+    for fmt in (3 - other, 3, -1):
+        assert fn(h._h, fmt) == L.SFE_EINVAL and lib.sfe_dsp_last_error() == text, (fmt, lib.sfe_dsp_last_error())
+    assert fn(None, L.FMT_F32) == L.SFE_EINVAL and lib.sfe_dsp_last_error() == text
+    assert fn(h._h, other) == L.SFE_OK and fn(h._h, L.FMT_F32) == L.SFE_OK
+    h.close()
