@@ -191,7 +191,8 @@ int sfe_dsp_rs_pipe_create(sfe_rs_t rs, size_t batch_items, float rate, sfe_pipe
     p->out_e = (size_t)r->esz();
     p->in_e = r->in_u8 ? (r->data_complex ? 2 : 1) : p->out_e;      // u8 wire-format items in (integer-valued steps)
     {
-        // an integer-valued step gives the same items wherever the calls are cut; any other step does not
+        // an integer-valued step gives the same items wherever the calls are cut; any other step does not.  (Not rs_plan.h's
+        // rs_step_is_integer, which also asks for a step below 1e6: a pipe made with a larger one has a quantum of 1.)
         const float stepf = rate * (float)r->U;
         p->quantum = (stepf >= 1.0f && stepf == floorf(stepf)) ? 1 : (size_t)r->blksize;
     }

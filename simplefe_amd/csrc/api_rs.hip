@@ -1,5 +1,7 @@
 // api_rs.hip -- the resample / decimate handle behind sfe_rs_t (libdsp/resample.cxx:37-153, libdsp/decimate.cxx:37-140):
-// the time law and its run memo, the choice of kernel, carried state, and the sfe_dsp_rs_* entry points.  Host code only.
+// a call's checks, the choice of kernel, the upload of the plans, carried state, and the sfe_dsp_rs_* entry points.  What a call
+// works out before it launches -- the integer-step closed form, the general-rate plan and its run memo -- is rs_plan.h's.
+// Host code only.
 #include "host.h"
 #include <stdlib.h>
 
@@ -9,40 +11,48 @@ namespace sfe {
 
 Rs *as_rs(void *h) { return as_handle<Rs>(h, "resample/decimate"); }
 
-static int rs_ensure_sched(Rs *r, size_t n)
+// the class-compatible path's buffers double from 1024; its staging is sized exactly
+static size_t rs_doubled(size_t cap, size_t n)
 {
-    if (n <= r->sched_cap) return SFE_OK;
-    size_t cap = r->sched_cap ? r->sched_cap : 1024;
+    if (!cap) cap = 1024;
     while (cap < n) cap *= 2;
-    r->sched_cap = 0;
-    int rc;
-    if ((rc = r->d_pos.grow(cap)) != SFE_OK || (rc = r->d_mu.grow(cap)) != SFE_OK || (rc = r->h_pos.grow(cap)) != SFE_OK ||
-        (rc = r->h_mu.grow(cap)) != SFE_OK)
-        return rc;
-    r->sched_cap = cap;
-    return SFE_OK;
+    return cap;
 }
-
+static int rs_ensure_sched(Rs *r, size_t n) { return r->sched.reserve(n, rs_doubled(r->sched.cap, n)); }
 static int rs_ensure_out(Rs *r, size_t n)
 {
-    if (n <= r->out_cap) return SFE_OK;
-    size_t cap = r->out_cap ? r->out_cap : 1024;
-    while (cap < n) cap *= 2;
-    r->out_cap = 0;
-    const int rc = r->d_out.grow(cap * r->esz());
-    if (rc != SFE_OK) return rc;
-    r->out_cap = cap;
-    return SFE_OK;
+    const size_t e = (size_t)r->esz();
+    return r->d_out.reserve(n * e, rs_doubled(r->d_out.cap / e, n) * e);
 }
 
-static int rs_ensure_stage(Rs *r, size_t bytes)
+// where a call's samples lie, and the seven fields every polyphase kernel's arguments open with (common.h: Poly*Args)
+struct RsIo {
+    const void *in;
+    void *out;
+    long long n_in, in_stride, out_stride;
+};
+template <class A>
+static void fill_io(A &a, const Rs *r, const RsIo &io)
 {
-    if (bytes <= r->h_stage_bytes) return SFE_OK;
-    r->h_stage_bytes = 0;
-    const int rc = r->h_stage.grow(bytes);
-    if (rc != SFE_OK) return rc;
-    r->h_stage_bytes = bytes;
-    return SFE_OK;
+    a.in = io.in;
+    a.out = io.out;
+    a.hist = r->hist.cur();
+    a.n_in = io.n_in;
+    a.in_stride = io.in_stride;
+    a.out_stride = io.out_stride;
+    a.hl = r->hl;
+}
+
+// the generic kernels' arguments (launch_poly_int, launch_poly_sched): the caller adds the law -- pos0 / step or the schedule
+static PolyArgs rs_poly_args(const Rs *r, const RsIo &io)
+{
+    PolyArgs a;
+    memset(&a, 0, sizeof(a));
+    fill_io(a, r, io);
+    a.taps = r->d_taps;
+    a.U = r->U;
+    a.plen = r->plen;
+    return a;
 }
 
 }  // namespace sfe
@@ -152,22 +162,18 @@ int sfe_dsp_rs_process(sfe_rs_t h, const float *in, int n_in, float *out, int ou
     // operations.  Same bits (tests/test_gpu_parity.py: class calls against the compiled reference).
     if (n_in > 0 && !r->in_u8) {
         const float stepf = rate * (float)r->U;
-        const bool int_step = stepf >= 1.0f && stepf == floorf(stepf) && stepf < 1.0e6f && r->ts.mu == 0.0f &&
-                              ((double)r->blksize * r->U + stepf) < 16777216.0;
         bool roomy;
-        if (int_step) {
-            const long long S = (long long)stepf, pos0 = r->ts.leftover ? -1 : (long long)r->ts.pos;
-            const long long lim = (long long)n_in * r->U - 2;
-            roomy = (pos0 <= lim ? (lim - pos0) / S + 1 : 0) <= (long long)out_len;
-        } else
+        if (rs_int_step_law(stepf, r->ts, r->blksize, r->U))
+            roomy = rs_int_call(r->ts, r->U, n_in, (long long)stepf).K <= (long long)out_len;
+        else
             roomy = (long long)out_len >= (long long)ceilf((float)n_in / rate) + 2;
         if (roomy) {
             const size_t in_b = (size_t)n_in * r->esz(), out_off = (in_b + 255) & ~(size_t)255;
-            int rc = rs_ensure_stage(r, out_off + ((size_t)out_len + 1) * r->esz());
+            int rc = r->h_stage.reserve(out_off + ((size_t)out_len + 1) * r->esz());
             if (rc != SFE_OK) return rc;
-            char *h_out = r->h_stage.p + out_off;
-            memcpy(r->h_stage, in, in_b);
-            SFE_HIP(hipMemcpyAsync(r->d_in, r->h_stage, in_b, hipMemcpyHostToDevice, r->stream));
+            char *h_out = r->h_stage->p + out_off;
+            memcpy(r->h_stage->p, in, in_b);
+            SFE_HIP(hipMemcpyAsync(r->d_in, r->h_stage->p, in_b, hipMemcpyHostToDevice, r->stream));
             const int keep = r->exact_stream;
             r->exact_stream = 1;
             size_t n = 0;
@@ -188,46 +194,36 @@ int sfe_dsp_rs_process(sfe_rs_t h, const float *in, int n_in, float *out, int ou
     if (rc != SFE_OK) return rc;
     const size_t in_b = (size_t)n_in * r->esz();
     const size_t out_b = ((size_t)out_len + 1) * r->esz();
-    rc = rs_ensure_stage(r, in_b > out_b ? in_b : out_b);
+    rc = r->h_stage.reserve(in_b > out_b ? in_b : out_b);
     if (rc != SFE_OK) return rc;
+    Rs::Sched &sc = r->sched.b;
 
     int k = 0;
     const int n = time_law(&r->ts, r->U, n_in, out_len, rate, [&](int p, float m) {
-        r->h_pos.p[k] = p;
-        r->h_mu.p[k] = m;
+        sc.pos.h.p[k] = p;
+        sc.mu.h.p[k] = m;
         k++;
     });
     if (n_in) {
-        memcpy(r->h_stage, in, in_b);
-        SFE_HIP(hipMemcpyAsync(r->d_in, r->h_stage, in_b, hipMemcpyHostToDevice, r->stream));
+        memcpy(r->h_stage->p, in, in_b);
+        SFE_HIP(hipMemcpyAsync(r->d_in, r->h_stage->p, in_b, hipMemcpyHostToDevice, r->stream));
     }
     if (n > 0) {
-        SFE_HIP(hipMemcpyAsync(r->d_pos, r->h_pos, (size_t)n * sizeof(long long), hipMemcpyHostToDevice, r->stream));
-        SFE_HIP(hipMemcpyAsync(r->d_mu, r->h_mu, (size_t)n * sizeof(float), hipMemcpyHostToDevice, r->stream));
-        PolyArgs a;
-        memset(&a, 0, sizeof(a));
-        a.in = r->d_in;
-        a.out = r->d_out;
-        a.hist = r->hist.cur();
-        a.taps = r->d_taps;
-        a.n_in = n_in;
-        a.in_stride = n_in;
-        a.out_stride = n;
-        a.hl = r->hl;
-        a.U = r->U;
-        a.plen = r->plen;
+        SFE_HIP(hipMemcpyAsync(sc.pos.d, sc.pos.h, (size_t)n * sizeof(long long), hipMemcpyHostToDevice, r->stream));
+        SFE_HIP(hipMemcpyAsync(sc.mu.d, sc.mu.h, (size_t)n * sizeof(float), hipMemcpyHostToDevice, r->stream));
+        PolyArgs a = rs_poly_args(r, RsIo{r->d_in, r->d_out->p, n_in, n_in, n});
         a.n_out = n;
-        a.sched_pos = r->d_pos;
-        a.sched_mu = r->d_mu;
+        a.sched_pos = sc.pos.d;
+        a.sched_mu = sc.mu.d;
         rc = launch_poly_sched(a, r->data_complex, 1, 1, r->stream);
         if (rc != SFE_OK) return rc;
     }
     rc = launch_history_update(r->d_in, n_in, n_in, r->hist.cur(), r->hist.next(), r->hl, r->data_complex ? 2 : 1, 1, r->stream);
     if (rc == SFE_OK) rc = r->hist.carry(r->captured, r->stream);
     if (rc != SFE_OK) return rc;
-    if (n > 0) SFE_HIP(hipMemcpyAsync(r->h_stage, r->d_out, (size_t)n * r->esz(), hipMemcpyDeviceToHost, r->stream));
+    if (n > 0) SFE_HIP(hipMemcpyAsync(r->h_stage->p, r->d_out->p, (size_t)n * r->esz(), hipMemcpyDeviceToHost, r->stream));
     SFE_HIP(hipStreamSynchronize(r->stream));
-    if (n > 0) memcpy(out, r->h_stage, (size_t)n * r->esz());
+    if (n > 0) memcpy(out, r->h_stage->p, (size_t)n * r->esz());
     *n_out = n;
     return SFE_OK;
 }
@@ -250,36 +246,43 @@ int sfe_dsp_rs_process_stream(sfe_rs_t h, const void *d_in, size_t n_in, size_t 
     SFE_ON_DEVICE(r->device);
     hipStream_t s = (hipStream_t)stream;
     const size_t w = r->data_complex ? 2 : 1, floats = (size_t)r->n_channels * n_in * w;
-    if (floats > r->d_u8f_floats) {
+    if (floats > r->d_u8f.cap) {
         if (stream_is_capturing(s)) {
             set_error("rs_process_stream: this u8 call needs %zu bytes of conversion scratch, which cannot be allocated while the stream is being captured",
                       floats * 4);
             return SFE_ESTATE;
         }
-        r->d_u8f_floats = 0;
-        if ((rc = r->d_u8f.grow(floats)) != SFE_OK) return rc;
-        r->d_u8f_floats = floats;
+        if ((rc = r->d_u8f.reserve(floats)) != SFE_OK) return rc;
     } else if (r->u8f_stream != s && r->u8f_stream) {
         SFE_HIP(hipStreamSynchronize(r->u8f_stream));         // the previous call on another stream may still read the scratch
     }
     r->u8f_stream = s;
     for (int c = 0; c < r->n_channels; c++) {
-        rc = launch_rx_u8_to_f32(static_cast<const uint8_t *>(d_in) + (size_t)c * in_stride * w, r->d_u8f.p + (size_t)c * n_in * w, n_in * w, s);
+        rc = launch_rx_u8_to_f32(static_cast<const uint8_t *>(d_in) + (size_t)c * in_stride * w, r->d_u8f->p + (size_t)c * n_in * w, n_in * w, s);
         if (rc != SFE_OK) return rc;
     }
     r->in_u8 = 0;
-    rc = rs_process_stream_impl(h, r->d_u8f, n_in, n_in, d_out, out_cap, out_stride, rate, n_out, stream);
+    rc = rs_process_stream_impl(h, r->d_u8f->p, n_in, n_in, d_out, out_cap, out_stride, rate, n_out, stream);
     r->in_u8 = 1;
     return rc;
 }
 
-static int rs_process_stream_impl(sfe_rs_t h, const void *d_in, size_t n_in, size_t in_stride,
-                                  void *d_out, size_t out_cap, size_t out_stride, float rate,
-                                  size_t *n_out, sfe_stream_t stream)
+}  // extern "C"
+
+// ------------------------------------------------------------------ one process_stream call, step by step
+namespace {
+
+struct RsCall {                 // the call's arguments, past its checks
+    RsIo io;
+    size_t n_in, out_cap;
+    float rate, stepf;          // stepf = fl(rate * U)
+    hipStream_t s;
+    bool capturing;
+};
+
+// The checks in front of the device: SFE_OK with n_in == 0 is a call with nothing to do (the caller returns as well).
+int rs_check_call(const Rs *r, const void *d_in, size_t n_in, size_t in_stride, void *d_out, size_t out_cap, size_t out_stride, float rate)
 {
-    Rs *r = as_rs(h);
-    if (!r || !n_out) return SFE_EINVAL;
-    *n_out = 0;
     if (r->mode == SFE_RS_RESAMPLE ? (rate < 1.0 / r->U) : (rate < 1.0)) {
         set_error("rs_process_stream: rate %g not accepted by this mode", (double)rate);
         return SFE_EINVAL;
@@ -294,445 +297,330 @@ static int rs_process_stream_impl(sfe_rs_t h, const void *d_in, size_t n_in, siz
         set_error("rs_process_stream: channel stride smaller than the channel (in_stride >= n_in, out_stride >= out_cap)");
         return SFE_EINVAL;
     }
-    {
-        const size_t isz = r->in_u8 ? (r->data_complex ? 2 : 1) : (size_t)r->esz();
-        const size_t osz = (size_t)r->esz();
-        if ((reinterpret_cast<uintptr_t>(d_in) & (isz - 1)) || (reinterpret_cast<uintptr_t>(d_out) & (osz - 1))) {
-            set_error("rs_process_stream: buffers must be aligned to their element (cf32 8 B, f32 4 B, u8 (I,Q) pairs 2 B)");
-            return SFE_EINVAL;
-        }
-        const size_t in_b = ((size_t)(r->n_channels - 1) * in_stride + n_in) * isz;
-        const size_t out_b = ((size_t)(r->n_channels - 1) * out_stride + out_cap) * osz;
-        if (ranges_overlap(d_in, in_b, d_out, out_b)) {
-            set_error("rs_process_stream: input and output ranges overlap");
-            return SFE_EINVAL;
+    const size_t isz = r->in_u8 ? (r->data_complex ? 2 : 1) : (size_t)r->esz();
+    const size_t osz = (size_t)r->esz();
+    if ((reinterpret_cast<uintptr_t>(d_in) & (isz - 1)) || (reinterpret_cast<uintptr_t>(d_out) & (osz - 1))) {
+        set_error("rs_process_stream: buffers must be aligned to their element (cf32 8 B, f32 4 B, u8 (I,Q) pairs 2 B)");
+        return SFE_EINVAL;
+    }
+    const size_t in_b = ((size_t)(r->n_channels - 1) * in_stride + n_in) * isz;
+    const size_t out_b = ((size_t)(r->n_channels - 1) * out_stride + out_cap) * osz;
+    if (ranges_overlap(d_in, in_b, d_out, out_b)) {
+        set_error("rs_process_stream: input and output ranges overlap");
+        return SFE_EINVAL;
+    }
+    return SFE_OK;
+}
+
+// ---- integer-valued step: one of the kernels of the closed form
+int rs_launch_fft(Rs *r, const RsCall &c, const PolyFftPlan *fp, long long K, bool can_fuse, bool *hist_fused)
+{
+    PolyFftArgs fa;
+    memset(&fa, 0, sizeof(fa));
+    fill_io(fa, r, c.io);
+    fa.hist_out = can_fuse ? r->hist.next() : nullptr;
+    *hist_fused = can_fuse;
+    fa.H = fp->d_H;
+    fa.tw = fp->d_tw;
+    fa.n_out = K;
+    fa.e_max = fp->e_max;
+    fa.ovl = fp->Li - 1;
+    fa.V = 256 - fa.ovl;
+    fa.ticket = r->d_ticket;
+    return launch_poly_fft(*fp, fa, r->data_complex, r->in_u8, r->n_channels, c.s);
+}
+
+int rs_launch_mfma(Rs *r, const RsCall &c, const PolyMfmaPlan *mp, long long K)
+{
+    PolyMfmaArgs ma;
+    memset(&ma, 0, sizeof(ma));
+    fill_io(ma, r, c.io);
+    ma.A = mp->d_A;
+    ma.n_out = K;
+    ma.GS = mp->GS;
+    ma.RG = mp->RG;
+    ma.Kp = mp->Kp;
+    ma.u_lo = mp->u_lo;
+    return launch_poly_mfma(ma, r->n_channels, c.s);
+}
+
+// the generic kernel: any (step, pos0), float32 input
+int rs_launch_int(Rs *r, const RsCall &c, const RsIntCall &ic)
+{
+    if (r->in_u8) {
+        r->u8_refused = true;          // (the public entry converts the bytes and comes back with float32)
+        set_error("rs_process_stream: u8 input needs a tiled kernel for this rate/tap shape");
+        return SFE_ESTATE;
+    }
+    PolyArgs a = rs_poly_args(r, c.io);
+    a.pos0 = ic.pos0;
+    a.step = (int)c.stepf;
+    a.n_out = ic.K;
+    return launch_poly_int(a, r->data_complex, 0, r->exact_stream, r->n_channels, c.s);
+}
+
+// the tiled kernels, in the order they are tried: LDS-DMA runtime shape, compiled / runtime shape, the generic kernel
+int rs_launch_tiled(Rs *r, const RsCall &c, const PolyTiledPlan *pl, const RsIntCall &ic, bool can_fuse, bool *hist_fused)
+{
+    PolyTiledArgs ta;
+    fill_io(ta, r, c.io);
+    ta.hist_out = can_fuse && !r->exact_stream ? r->hist.next() : nullptr;      // exact kernels: separate carry-over launch
+    *hist_fused = ta.hist_out != nullptr;
+    ta.G = pl->d_G;
+    ta.Gt = pl->d_Gt;
+    ta.n_out = ic.K;
+    ta.Lp = pl->Lp;
+    ta.e_max = pl->e_max;
+    // shapes outside the compiled tables, float32 streams (complex or real), fused arithmetic: the tile by LDS-DMA, read in place (poly_rt_dma.hip)
+    int rc = SFE_ESTATE;
+    bool window_shape = !r->data_complex && poly_rt_dma_window_shape(pl->SP, pl->UP);      // real streams at small steps: the register-window kernel
+#ifdef SFE_DIAG
+    if (const char *e = getenv("SFE_RT_DMA_WINDOW")) window_shape = window_shape && pl->SP <= atoi(e);
+#endif
+    // wire-format input: four shapes have compile-time u8 kernels (/2, /4, /8, 5/3) and keep them; every other one -- the compile-time
+    // float shapes included -- ran poly_rt_kernel's sample-by-sample byte loads (/7 0.71 ms where the float32 stream takes 0.45) and now
+    // has its raw tile fetched by DMA and converted once (0.38 ms): profiles/r05/shapes_u8.txt
+    const bool compiled = r->in_u8 ? poly_tiled_u8_is_compiled(pl->SP, pl->UP, pl->Lp) : poly_tiled_is_compiled(pl->SP, pl->UP, pl->Lp);
+    bool try_dma = !r->exact_stream && (!compiled || window_shape);       // (real u8 streams at the window form's shapes: /2 0.72 -> 0.6 ms, profiles/r05/shapes_u8.txt)
+#ifdef SFE_DIAG
+    if (const char *e = getenv("SFE_RT_DMA_FORCE"))        // scripts/ab_dec8_dma.py: the LDS-DMA form also where a compile-time kernel exists
+        if (atoi(e) && !r->exact_stream) try_dma = true;
+    if (const char *e = getenv("SFE_RT_DMA_U8"))           // =0: wire-format input keeps poly_rt_kernel / the compile-time kernels (scripts/time_u8_shapes.py)
+        if (!atoi(e) && r->in_u8) try_dma = false;
+#endif
+    if (try_dma) rc = launch_poly_rt_dma(*pl, ta, r->data_complex, r->in_u8, r->n_channels, c.s);
+    if (rc == SFE_ESTATE && pl->UP <= 8) rc = launch_poly_tiled(*pl, ta, r->data_complex, r->exact_stream, r->in_u8, r->n_channels, c.s);
+    if (rc == SFE_ESTATE && pl->UP > 8) {            // 9 ... 256 outputs per period and the tiled form declined: the generic kernel
+        *hist_fused = false;
+        rc = rs_launch_int(r, c, ic);
+    }
+    return rc;
+}
+
+int rs_run_int_step(Rs *r, const RsCall &c, size_t *n_out, bool *hist_fused)
+{
+    const long long S = (long long)c.stepf;
+    const RsIntCall ic = rs_int_call(r->ts, r->U, (long long)c.n_in, S);
+    const long long K = ic.K, pos0 = ic.pos0;
+    if ((size_t)K > c.out_cap) {
+        set_error("rs_process_stream: need room for %lld outputs, got %zu", K, c.out_cap);
+        return SFE_ERANGE;
+    }
+    int rc = SFE_OK;
+    // matrix-pipe form (fused numerics, cf32): opt-in with sfe_dsp_rs_set_algo(SFE_RS_ALGO_MFMA).  Measured slower
+    // than the VALU kernel on the one shape where its tap matrix is dense (polyphase.hip).
+    const PolyMfmaPlan *mp = nullptr;
+    if (r->use_mfma && !r->exact_stream && r->data_complex && !r->in_u8) {
+        mp = get_mfma_plan(r->mfma_plans, r->h_taps_pm, r->U, r->plen, (int)S, pos0, &rc);
+        if (rc != SFE_OK) return rc;
+    }
+    // transform-domain form (fused numerics, cf32): long filters on streams long enough to fill the chip
+    const PolyFftPlan *fp = nullptr;
+    if (!mp && !r->exact_stream && K >= 4096) {
+        fp = get_fft_plan(r->fft_plans, r->h_taps_pm, r->U, r->plen, (int)S, pos0, r->fft_mode, &rc);
+        if (rc != SFE_OK) return rc;
+    }
+    const PolyTiledPlan *pl = (mp || fp) ? nullptr : get_tiled_plan(r->plans, r->h_taps_pm, r->U, r->plen, (int)S, pos0, &rc);
+    if (rc != SFE_OK) return rc;
+    // the transform-domain and the tiled kernels write the next call's history themselves (one launch per call)
+    const bool can_fuse = c.n_in >= (size_t)r->hl && K > 0 && !c.capturing;
+    if (fp) rc = rs_launch_fft(r, c, fp, K, can_fuse, hist_fused);
+    else if (mp) rc = rs_launch_mfma(r, c, mp, K);
+    else if (pl) rc = rs_launch_tiled(r, c, pl, ic, can_fuse, hist_fused);
+    else rc = rs_launch_int(r, c, ic);
+    if (rc != SFE_OK) return rc;
+    r->ts = ic.after;
+    *n_out = (size_t)K;
+    return SFE_OK;
+}
+
+// ---- general rate: the plan (rs_plan.h), its upload, then the transform kernel, the direct kernel, the host schedule
+// Plan tables: grow-only device arrays + pinned staging.  The previous call's UPLOADS may still be reading the
+// staging: wait for them -- the event behind them -- not for the stream: that call's kernel runs on while this
+// call is planned and queued (waiting for the stream here made every call a full host/device round trip).
+// The device arrays themselves are ordered by the stream; a call on ANOTHER stream than the last waits for that one.
+int rs_upload_plan(Rs *r, const RsPlan<SegChunk> &plan, hipStream_t s)
+{
+    int rc;
+    if (r->ev_plan) {
+        if (r->plan_stream != s) SFE_HIP(hipStreamSynchronize(r->plan_stream));
+        else SFE_HIP(hipEventSynchronize(r->ev_plan));
+    } else if ((rc = r->ev_plan.create()) != SFE_OK) {
+        return rc;
+    }
+    const size_t n_table = plan.n_table, n_segs = plan.n_segs(), n_chunks = plan.chunks.size();
+    if (n_segs > r->segs.cap) r->seg_uploaded = 0;          // regrown: the device holds nothing of the table
+    if ((rc = r->segs.reserve(n_segs, n_segs * 2 + 1024)) != SFE_OK || (rc = r->chunks.reserve(n_chunks, n_chunks * 2 + 64)) != SFE_OK) return rc;
+    // upload what the device does not hold yet: the table's new tail, then this call's own runs behind it
+    TlSeg *hs = r->segs->h;
+    const size_t from = r->seg_uploaded < n_table ? r->seg_uploaded : n_table;
+    if (n_table > from) memcpy(hs + from, r->memo.table.data() + from, (n_table - from) * sizeof(TlSeg));
+    if (!plan.extra.empty()) memcpy(hs + n_table, plan.extra.data(), plan.extra.size() * sizeof(TlSeg));
+    if (n_segs > from)
+        SFE_HIP(hipMemcpyAsync(r->segs->d.p + from, hs + from, (n_segs - from) * sizeof(TlSeg), hipMemcpyHostToDevice, s));
+    r->seg_uploaded = n_table;
+    memcpy(r->chunks->h, plan.chunks.data(), n_chunks * sizeof(SegChunk));
+    SFE_HIP(hipMemcpyAsync(r->chunks->d, r->chunks->h, n_chunks * sizeof(SegChunk), hipMemcpyHostToDevice, s));
+    SFE_HIP(hipEventRecord(r->ev_plan, s));
+    r->plan_stream = s;
+    return SFE_OK;
+}
+
+// Bulk calls (complex or real, float32 or u8) in fused arithmetic, at any rate: the transform-domain kernel (poly_gen.hip) --
+// all U phases of every input by one forward and U inverse 4096-point transforms, outputs picked and blended from
+// LDS by the same runs.  sfe_dsp_rs_set_algo(SFE_RS_ALGO_DIRECT) and the exact mode keep poly_seg_kernel.
+// SFE_ESTATE: not a call for it (nothing launched).
+int rs_launch_gen(Rs *r, const RsCall &c, const RsPlan<SegChunk> &plan)
+{
+    // (1 + U) transforms per block against two dot products of plen taps per output: the transform kernel while U <= 2 + plen / 16 (measured at
+    // 2^26 samples and rate 1.77, profiles/r05/speed_sweep.txt: it takes 0.43 + 0.11 U ms, the direct kernel 0.69 + 0.0072 plen; until round 5
+    // the rule was "12 taps per phase or more" and 16 phases of 127 taps ran 2.2 ms where the direct kernel takes 1.6)
+    const bool gen_pays = r->plen >= 12 && r->U <= 2 + r->plen / 16;
+    if (plan.exhausted || r->exact_stream || r->fft_mode < 0 ||
+        !(r->fft_mode > 0 || r->in_u8 || (c.n_in >= ((size_t)1 << 16) && gen_pays)))
+        return SFE_ESTATE;
+    if (!r->gen_tried) {
+        // spectra of the U phase filters (taps[i U + j], i < plen; one zero behind so that the overlap the FIR
+        // planner picks covers plen samples, not plen - 1) through fir_build_tables: one "channel" per phase
+        r->gen_tried = true;
+        std::vector<float> rows((size_t)r->U * (r->plen + 1), 0.0f);
+        for (int j = 0; j < r->U; j++)
+            for (int i = 0; i < r->plen; i++) rows[(size_t)j * (r->plen + 1) + i] = r->h_taps_pm[(size_t)j * r->plen + i];
+        sfe_fir_t gh = nullptr;
+        if (fir_create_impl(rows.data(), r->plen + 1, 0, 1, r->U, 0, r->device, 1, &gh) == SFE_OK) {
+            r->gen_tables.reset(static_cast<Fir *>(gh));
+            if (r->gen_tables->parts != 1) r->gen_tables.reset();
         }
     }
+    if (!r->gen_tables) return SFE_ESTATE;
+    const std::vector<SegChunk> &chunks = plan.chunks;
+    PolyGenArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    fill_io(ga, r, c.io);
+    ga.hs = r->gen_tables->tab.hs;
+    ga.tw1 = r->gen_tables->tab.tw1;
+    ga.tw2 = r->gen_tables->tab.tw2;
+    ga.segs = r->segs->d;
+    ga.chunks = r->chunks->d;
+    ga.U = r->U;
+    ga.plen = r->plen;
+    ga.ovl = (r->plen + 15) & ~15;              // >= plen; the spectra do not depend on it
+    ga.blksize = r->blksize;
+    ga.n_chunks = (int)chunks.size();
+    ga.real = r->data_complex ? 0 : 1;
+    ga.in_u8 = r->in_u8 ? 1 : 0;
+    int max_runs = 0;              // over any two (a real stream's pairs of blocks: three) consecutive calls
+    for (size_t i = 0; i < chunks.size(); i++) {
+        int sum = chunks[i].n_seg + (i + 1 < chunks.size() ? chunks[i + 1].n_seg : 0);
+        if (ga.real && i + 2 < chunks.size()) sum += chunks[i + 2].n_seg;
+        max_runs = sum > max_runs ? sum : max_runs;
+    }
+    return launch_poly_gen(ga, max_runs, c.stepf, r->n_channels, c.s);
+}
+
+// The direct kernel's LDS: a call larger than it is dealt to `split` workgroups, each tile sized by the largest input
+// span any part of any call of this launch really reaches (segtile.h; rs_plan.h: rs_plan_max_span).  SFE_ESTATE: a part of a
+// call reaches more input than the LDS holds, at any split (huge blksize).
+int rs_launch_seg(Rs *r, const RsCall &c, const RsPlan<SegChunk> &plan)
+{
+    SegTilePlan tp;
+    auto max_span = [&](int split) { return rs_plan_max_span(r->memo, plan, r->U, r->plen, split); };
+    if (seg_tile_plan(r->U, r->plen, r->esz(), plan.max_m, max_span, &tp) != SFE_OK) return SFE_ESTATE;
+    PolySegArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    fill_io(sa, r, c.io);
+    sa.taps = r->d_taps;
+    sa.segs = r->segs->d;
+    sa.chunks = r->chunks->d;
+    sa.U = r->U;
+    sa.plen = r->plen;
+    sa.n_chunks = (int)plan.chunks.size();
+    sa.max_m = plan.max_m;
+    sa.split = tp.split;
+    sa.tile_cap = tp.tile_cap;
+    sa.taps_global = tp.taps_global;
+    return launch_poly_seg(sa, r->data_complex, r->exact_stream, r->n_channels, c.s);
+}
+
+// the last resort: expand on the host and use the per-output schedule kernel
+int rs_launch_sched(Rs *r, const RsCall &c, const RsPlan<SegChunk> &plan)
+{
+    const size_t K = plan.K;
+    std::vector<long long> pos;
+    std::vector<float> mu;
+    rs_plan_expand(r->memo, plan, r->U, pos, mu);
+    const int rc = rs_ensure_sched(r, K + 1);
+    if (rc != SFE_OK) return rc;
+    Rs::Sched &sc = r->sched.b;
+    SFE_HIP(hipStreamSynchronize(c.s));        // the schedule staging may still be read by the previous call's uploads
+    memcpy(sc.pos.h, pos.data(), K * sizeof(long long));
+    memcpy(sc.mu.h, mu.data(), K * sizeof(float));
+    SFE_HIP(hipMemcpyAsync(sc.pos.d, sc.pos.h, K * sizeof(long long), hipMemcpyHostToDevice, c.s));
+    SFE_HIP(hipMemcpyAsync(sc.mu.d, sc.mu.h, K * sizeof(float), hipMemcpyHostToDevice, c.s));
+    PolyArgs a = rs_poly_args(r, c.io);
+    a.n_out = (long long)K;
+    a.sched_pos = sc.pos.d;
+    a.sched_mu = sc.mu.d;
+    return launch_poly_sched(a, r->data_complex, r->exact_stream, r->n_channels, c.s);
+}
+
+int rs_run_general(Rs *r, const RsCall &c, size_t *n_out)
+{
+    // u8 input at a general rate: the transform-domain kernel converts on load (poly_gen.hip: IN_U8); the direct kernels
+    // (exact mode, SFE_RS_ALGO_DIRECT) have no u8 form
+    if (r->in_u8 && (r->exact_stream || r->fft_mode < 0)) {
+        set_error("rs_process_stream: u8 input at a non-integer step runs the transform-domain kernel only (not the exact mode, not SFE_RS_ALGO_DIRECT)");
+        return SFE_ESTATE;
+    }
+    const RsPlan<SegChunk> plan = rs_plan_calls<SegChunk>(r->memo, r->ts, r->U, r->blksize, c.n_in, c.rate);
+    if (plan.memo_cleared) r->seg_uploaded = 0;
+    if (plan.K > c.out_cap) {
+        set_error("rs_process_stream: need room for %zu outputs, got %zu", plan.K, c.out_cap);
+        return SFE_ERANGE;
+    }
+    int rc = rs_upload_plan(r, plan, c.s);
+    if (rc != SFE_OK) return rc;
+    rc = rs_launch_gen(r, c, plan);
+    if (rc == SFE_ESTATE && r->in_u8) {
+        r->u8_refused = true;              // (the public entry converts the bytes and comes back with float32)
+        set_error("rs_process_stream: u8 input at a non-integer step: this call is outside what the transform-domain kernel takes "
+                  "(more than 2032 taps per phase, more than 32 phases, blksize below a block's advance, or a call in the "
+                  "reference's out_len-exhausted state)");
+        return SFE_ESTATE;
+    }
+    if (rc == SFE_ESTATE) rc = rs_launch_seg(r, c, plan);
+    if (rc == SFE_ESTATE) rc = rs_launch_sched(r, c, plan);
+    if (rc != SFE_OK) return rc;
+    r->ts = plan.after;
+    *n_out = plan.K;
+    return SFE_OK;
+}
+
+}  // namespace
+
+static int rs_process_stream_impl(sfe_rs_t h, const void *d_in, size_t n_in, size_t in_stride,
+                                  void *d_out, size_t out_cap, size_t out_stride, float rate,
+                                  size_t *n_out, sfe_stream_t stream)
+{
+    Rs *r = as_rs(h);
+    if (!r || !n_out) return SFE_EINVAL;
+    *n_out = 0;
+    int rc = rs_check_call(r, d_in, n_in, in_stride, d_out, out_cap, out_stride, rate);
+    if (rc != SFE_OK || n_in == 0) return rc;
     SFE_ON_DEVICE(r->device);
     hipStream_t s = (hipStream_t)stream;
     const float stepf = rate * (float)r->U;
-    const bool int_step = stepf >= 1.0f && stepf == floorf(stepf) && stepf < 1.0e6f && r->ts.mu == 0.0f &&
-                          ((double)r->blksize * r->U + stepf) < 16777216.0;
-    const bool capturing = stream_is_capturing(s);
-    if (capturing && (!int_step || n_in < (size_t)r->hl || ((unsigned long long)n_in * (unsigned long long)r->U) % (unsigned long long)stepf != 0)) {
+    const bool int_step = rs_int_step_law(stepf, r->ts, r->blksize, r->U);
+    const RsCall c = {{d_in, d_out, (long long)n_in, (long long)in_stride, (long long)out_stride}, n_in, out_cap, rate, stepf, s, stream_is_capturing(s)};
+    if (c.capturing && (!int_step || n_in < (size_t)r->hl || ((unsigned long long)n_in * (unsigned long long)r->U) % (unsigned long long)stepf != 0)) {
         set_error("rs_process_stream: a call captured into a hipGraph must leave the time state where it found it "
                   "(integer-valued step, n_in*upsample a multiple of it) and bring at least %d samples", r->hl);
         return SFE_ESTATE;
     }
-    PolyArgs a;
-    memset(&a, 0, sizeof(a));
-    a.in = d_in;
-    a.out = d_out;
-    a.hist = r->hist.cur();
-    a.taps = r->d_taps;
-    a.n_in = (long long)n_in;
-    a.in_stride = (long long)in_stride;
-    a.out_stride = (long long)out_stride;
-    a.hl = r->hl;
-    a.U = r->U;
-    a.plen = r->plen;
-    int rc;
     bool hist_fused = false;
-    if (int_step) {
-        // closed form of the law: output k at pos0 + k*S, emitted while pos <= n_in*U - 2
-        // (pos == n_in*U - 1 is the reference's "leftover": it comes out first next call).
-        const long long S = (long long)stepf;
-        const long long pos0 = r->ts.leftover ? -1 : (long long)r->ts.pos;
-        const long long lim = (long long)n_in * r->U - 2;
-        const long long K = pos0 <= lim ? (lim - pos0) / S + 1 : 0;
-        if ((size_t)K > out_cap) {
-            set_error("rs_process_stream: need room for %lld outputs, got %zu", K, out_cap);
-            return SFE_ERANGE;
-        }
-        a.pos0 = pos0;
-        a.step = (int)S;
-        a.n_out = K;
-        // matrix-pipe form (fused numerics, cf32): opt-in with sfe_dsp_rs_set_algo(SFE_RS_ALGO_MFMA).  Measured slower
-        // than the VALU kernel on the one shape where its tap matrix is dense (polyphase.hip).
-        const PolyMfmaPlan *mp = nullptr;
-        if (r->use_mfma && !r->exact_stream && r->data_complex && !r->in_u8) {
-            mp = get_mfma_plan(r->mfma_plans, r->h_taps_pm, r->U, r->plen, (int)S, pos0, &rc);
-            if (rc != SFE_OK) return rc;
-        }
-        // transform-domain form (fused numerics, cf32): long filters on streams long enough to fill the chip
-        const PolyFftPlan *fp = nullptr;
-        if (!mp && !r->exact_stream && K >= 4096) {
-            fp = get_fft_plan(r->fft_plans, r->h_taps_pm, r->U, r->plen, (int)S, pos0, r->fft_mode, &rc);
-            if (rc != SFE_OK) return rc;
-        }
-        const PolyTiledPlan *pl = (mp || fp) ? nullptr : get_tiled_plan(r->plans, r->h_taps_pm, r->U, r->plen, (int)S, pos0, &rc);
-        if (rc != SFE_OK) return rc;
-        // the transform-domain and the tiled kernels write the next call's history themselves (one launch per call)
-        const bool can_fuse = n_in >= (size_t)r->hl && K > 0 && !capturing;
-        if (fp) {
-            PolyFftArgs fa;
-            memset(&fa, 0, sizeof(fa));
-            fa.in = d_in;
-            fa.out = d_out;
-            fa.hist = r->hist.cur();
-            fa.hist_out = can_fuse ? r->hist.next() : nullptr;
-            hist_fused = can_fuse;
-            fa.H = fp->d_H;
-            fa.tw = fp->d_tw;
-            fa.n_in = (long long)n_in;
-            fa.in_stride = (long long)in_stride;
-            fa.out_stride = (long long)out_stride;
-            fa.n_out = K;
-            fa.hl = r->hl;
-            fa.e_max = fp->e_max;
-            fa.ovl = fp->Li - 1;
-            fa.V = 256 - fa.ovl;
-            fa.ticket = r->d_ticket;
-            rc = launch_poly_fft(*fp, fa, r->data_complex, r->in_u8, r->n_channels, s);
-        } else if (mp) {
-            PolyMfmaArgs ma;
-            memset(&ma, 0, sizeof(ma));
-            ma.in = d_in;
-            ma.out = d_out;
-            ma.hist = r->hist.cur();
-            ma.A = mp->d_A;
-            ma.n_in = (long long)n_in;
-            ma.in_stride = (long long)in_stride;
-            ma.out_stride = (long long)out_stride;
-            ma.n_out = K;
-            ma.hl = r->hl;
-            ma.GS = mp->GS;
-            ma.RG = mp->RG;
-            ma.Kp = mp->Kp;
-            ma.u_lo = mp->u_lo;
-            rc = launch_poly_mfma(ma, r->n_channels, s);
-        } else if (pl) {
-            PolyTiledArgs ta;
-            ta.in = d_in;
-            ta.out = d_out;
-            ta.hist = r->hist.cur();
-            ta.hist_out = can_fuse && !r->exact_stream ? r->hist.next() : nullptr;      // exact kernels: separate carry-over launch
-            hist_fused = ta.hist_out != nullptr;
-            ta.G = pl->d_G;
-            ta.Gt = pl->d_Gt;
-            ta.n_in = (long long)n_in;
-            ta.in_stride = (long long)in_stride;
-            ta.out_stride = (long long)out_stride;
-            ta.n_out = K;
-            ta.hl = r->hl;
-            ta.Lp = pl->Lp;
-            ta.e_max = pl->e_max;
-            // shapes outside the compiled tables, float32 streams (complex or real), fused arithmetic: the tile by LDS-DMA, read in place (poly_rt_dma.hip)
-            rc = SFE_ESTATE;
-            bool window_shape = !r->data_complex && poly_rt_dma_window_shape(pl->SP, pl->UP);      // real streams at small steps: the register-window kernel
-#ifdef SFE_DIAG
-            if (const char *e = getenv("SFE_RT_DMA_WINDOW")) window_shape = window_shape && pl->SP <= atoi(e);
-#endif
-            // wire-format input: four shapes have compile-time u8 kernels (/2, /4, /8, 5/3) and keep them; every other one -- the compile-time
-            // float shapes included -- ran poly_rt_kernel's sample-by-sample byte loads (/7 0.71 ms where the float32 stream takes 0.45) and now
-            // has its raw tile fetched by DMA and converted once (0.38 ms): profiles/r05/shapes_u8.txt
-            const bool compiled = r->in_u8 ? poly_tiled_u8_is_compiled(pl->SP, pl->UP, pl->Lp) : poly_tiled_is_compiled(pl->SP, pl->UP, pl->Lp);
-            bool try_dma = !r->exact_stream && (!compiled || window_shape);       // (real u8 streams at the window form's shapes: /2 0.72 -> 0.6 ms, profiles/r05/shapes_u8.txt)
-#ifdef SFE_DIAG
-            if (const char *e = getenv("SFE_RT_DMA_FORCE"))        // scripts/ab_dec8_dma.py: the LDS-DMA form also where a compile-time kernel exists
-                if (atoi(e) && !r->exact_stream) try_dma = true;
-            if (const char *e = getenv("SFE_RT_DMA_U8"))           // =0: wire-format input keeps poly_rt_kernel / the compile-time kernels (scripts/time_u8_shapes.py)
-                if (!atoi(e) && r->in_u8) try_dma = false;
-#endif
-            if (try_dma) rc = launch_poly_rt_dma(*pl, ta, r->data_complex, r->in_u8, r->n_channels, s);
-            if (rc == SFE_ESTATE && pl->UP <= 8) rc = launch_poly_tiled(*pl, ta, r->data_complex, r->exact_stream, r->in_u8, r->n_channels, s);
-            if (rc == SFE_ESTATE && pl->UP > 8) {            // 9 ... 256 outputs per period and the tiled form declined: the generic kernel
-                if (r->in_u8) {
-                    r->u8_refused = true;
-                    set_error("rs_process_stream: u8 input needs a tiled kernel for this rate/tap shape");
-                    return SFE_ESTATE;
-                }
-                hist_fused = false;
-                rc = launch_poly_int(a, r->data_complex, 0, r->exact_stream, r->n_channels, s);
-            }
-        } else {
-            if (r->in_u8) {
-                r->u8_refused = true;          // (the public entry converts the bytes and comes back with float32)
-                set_error("rs_process_stream: u8 input needs a tiled kernel for this rate/tap shape");
-                return SFE_ESTATE;
-            }
-            rc = launch_poly_int(a, r->data_complex, 0, r->exact_stream, r->n_channels, s);
-        }
-        if (rc != SFE_OK) return rc;
-        const long long next = pos0 + K * S - (long long)n_in * r->U;
-        r->ts.leftover = next == -1 ? 1 : 0;
-        r->ts.pos = (int32_t)next;
-        r->ts.mu = 0.0f;
-        *n_out = (size_t)K;
-    } else {
-        // u8 input at a general rate: the transform-domain kernel converts on load (poly_gen.hip: IN_U8); the direct kernels
-        // (exact mode, SFE_RS_ALGO_DIRECT) have no u8 form
-        if (r->in_u8 && (r->exact_stream || r->fft_mode < 0)) {
-            set_error("rs_process_stream: u8 input at a non-integer step runs the transform-domain kernel only (not the exact mode, not SFE_RS_ALGO_DIRECT)");
-            return SFE_ESTATE;
-        }
-        // Replay the float32 recurrence call by call (blksize samples each), as the reference
-        // object would see the stream -- in closed form: each call becomes a few constant-increment
-        // runs (timelaw.h) that one workgroup expands on the GPU.  A call's runs are a function of
-        // the state it starts in; full-size calls are memoised per start state (Rs::seg_memo).
-        sfe_rs_timestate st = r->ts;
-        if (r->memo_rate != rate || r->memo_m != r->blksize) {
-            r->seg_memo.clear();
-            r->seg_refs.clear();
-            r->seg_table.clear();
-            r->seg_uploaded = 0;
-            r->memo_rate = rate;
-            r->memo_m = r->blksize;
-        }
-        constexpr size_t MEMO_MAX_SEGS = (size_t)2 << 20;       // 64 MiB of runs: beyond, calls are planned without the memo
-        std::vector<TlSeg> extra;                               // runs of calls that are not memoised (the ragged last one)
-        std::vector<size_t> extra_chunks;
-        std::vector<SegChunk> chunks;
-        chunks.reserve(n_in / (size_t)r->blksize + 1);
-        std::vector<int> chunk_ref;                             // per call: its memoised plan, -1 for the calls in `extra`
-        chunk_ref.reserve(n_in / (size_t)r->blksize + 1);
-        size_t K = 0;
-        int max_m = 0;
-        int prev_ref = -1;          // plan of the previous (memoised) call of this launch: its `next` link is followed / filled in
-        // A reference call that runs out of out_len mid-block leaves its time state BEFORE the next call's first sample
-        // (pos < -1; SURVEY.md section 5 -- it happens when the float32 recurrence drifts by more outputs than the
-        // ceil(n_in / rate) + 2 a call is given, e.g. blksize 16384 x 3 phases at a step of 3.005).  The direct kernel
-        // reproduces that state output for output; the transform-domain kernel assigns outputs to blocks by position and
-        // does not take such calls.
-        bool exhausted = false;
-        for (size_t off = 0; off < n_in; off += (size_t)r->blksize) {
-            const int m = (int)((n_in - off) < (size_t)r->blksize ? (n_in - off) : (size_t)r->blksize);
-            const int cap = (int)ceilf((float)m / rate) + 2;
-            exhausted = exhausted || st.pos < -1;
-            SegChunk c;
-            c.in_off = (long long)off;
-            c.k_first = (long long)K;
-            c.m = m;
-            if (m == r->blksize && r->seg_table.size() < MEMO_MAX_SEGS) {
-                int idx = prev_ref >= 0 ? r->seg_refs[(size_t)prev_ref].next : -1;
-                if (idx < 0) {
-                    uint32_t mu_bits;
-                    memcpy(&mu_bits, &st.mu, 4);
-                    const uint64_t key = ((uint64_t)(uint32_t)(st.pos + 1) << 33) | ((uint64_t)mu_bits << 1) | (uint64_t)(st.leftover ? 1 : 0);   // pos >= -1
-                    auto it = r->seg_memo.find(key);
-                    if (it == r->seg_memo.end()) {
-                        Rs::SegPlanRef ref;
-                        ref.seg_first = (int)r->seg_table.size();
-                        sfe_rs_timestate st2 = st;
-                        ref.n_out = time_law_segments(&st2, r->U, m, cap, rate, r->seg_table);
-                        ref.n_seg = (int)r->seg_table.size() - ref.seg_first;
-                        ref.after = st2;
-                        idx = (int)r->seg_refs.size();
-                        r->seg_refs.push_back(ref);
-                        r->seg_memo.emplace(key, idx);
-                    } else {
-                        idx = it->second;
-                    }
-                    if (prev_ref >= 0) r->seg_refs[(size_t)prev_ref].next = idx;
-                }
-                const Rs::SegPlanRef &ref = r->seg_refs[(size_t)idx];
-                st = ref.after;
-                c.seg_first = ref.seg_first;
-                c.n_seg = ref.n_seg;
-                c.n_out = ref.n_out;
-                prev_ref = idx;
-                chunk_ref.push_back(idx);
-            } else {
-                prev_ref = -1;
-                c.seg_first = (int)extra.size();                 // + the table's final size, below
-                c.n_out = time_law_segments(&st, r->U, m, cap, rate, extra);
-                c.n_seg = (int)extra.size() - c.seg_first;
-                extra_chunks.push_back(chunks.size());
-                chunk_ref.push_back(-1);
-            }
-            chunks.push_back(c);
-            K += (size_t)c.n_out;
-            max_m = m > max_m ? m : max_m;
-        }
-        const size_t n_table = r->seg_table.size(), n_segs = n_table + extra.size();
-        for (size_t ci : extra_chunks) chunks[ci].seg_first += (int)n_table;
-        auto seg_at = [&](size_t i) -> const TlSeg & { return i < n_table ? r->seg_table[i] : extra[i - n_table]; };
-        if (K > out_cap) {
-            set_error("rs_process_stream: need room for %zu outputs, got %zu", K, out_cap);
-            return SFE_ERANGE;
-        }
-        PolySegArgs sa;
-        memset(&sa, 0, sizeof(sa));
-        sa.in = d_in;
-        sa.out = d_out;
-        sa.hist = r->hist.cur();
-        sa.taps = r->d_taps;
-        sa.n_in = (long long)n_in;
-        sa.in_stride = (long long)in_stride;
-        sa.out_stride = (long long)out_stride;
-        sa.hl = r->hl;
-        sa.U = r->U;
-        sa.plen = r->plen;
-        sa.n_chunks = (int)chunks.size();
-        sa.max_m = max_m;
-        sa.taps_global = 0;
-        sa.split = 1;
-        sa.tile_cap = 0;
-        // plan tables: grow-only device arrays + pinned staging.  The previous call's UPLOADS may still be reading the
-        // staging: wait for them -- the event behind them -- not for the stream: that call's kernel runs on while this
-        // call is planned and queued (waiting for the stream here made every call a full host/device round trip).
-        // The device arrays themselves are ordered by the stream; a call on ANOTHER stream than the last waits for that one.
-        if (r->ev_plan) {
-            if (r->plan_stream != s) SFE_HIP(hipStreamSynchronize(r->plan_stream));
-            else SFE_HIP(hipEventSynchronize(r->ev_plan));
-        } else if ((rc = r->ev_plan.create()) != SFE_OK) {
-            return rc;
-        }
-        if (n_segs > r->segs_cap) {
-            r->segs_cap = 0;
-            r->seg_uploaded = 0;
-            const size_t cap2 = n_segs * 2 + 1024;
-            if ((rc = r->d_segs.grow(cap2)) != SFE_OK || (rc = r->h_segs.grow(cap2)) != SFE_OK) return rc;
-            r->segs_cap = cap2;
-        }
-        if (chunks.size() > r->chunks_cap) {
-            r->chunks_cap = 0;
-            const size_t cap2 = chunks.size() * 2 + 64;
-            if ((rc = r->d_chunks.grow(cap2)) != SFE_OK || (rc = r->h_chunks.grow(cap2)) != SFE_OK) return rc;
-            r->chunks_cap = cap2;
-        }
-        // upload what the device does not hold yet: the table's new tail, then this call's own runs behind it
-        {
-            TlSeg *hs = r->h_segs;
-            const size_t from = r->seg_uploaded < n_table ? r->seg_uploaded : n_table;
-            if (n_table > from) memcpy(hs + from, r->seg_table.data() + from, (n_table - from) * sizeof(TlSeg));
-            if (!extra.empty()) memcpy(hs + n_table, extra.data(), extra.size() * sizeof(TlSeg));
-            if (n_segs > from)
-                SFE_HIP(hipMemcpyAsync(r->d_segs.p + from, hs + from, (n_segs - from) * sizeof(TlSeg),
-                                       hipMemcpyHostToDevice, s));
-            r->seg_uploaded = n_table;
-        }
-        memcpy(r->h_chunks, chunks.data(), chunks.size() * sizeof(SegChunk));
-        SFE_HIP(hipMemcpyAsync(r->d_chunks, r->h_chunks, chunks.size() * sizeof(SegChunk), hipMemcpyHostToDevice, s));
-        SFE_HIP(hipEventRecord(r->ev_plan, s));
-        r->plan_stream = s;
-        sa.segs = r->d_segs;
-        sa.chunks = r->d_chunks;
-        // Bulk calls (complex or real, float32 or u8) in fused arithmetic, at any rate: the transform-domain kernel (poly_gen.hip) --
-        // all U phases of every input by one forward and U inverse 4096-point transforms, outputs picked and blended from
-        // LDS by the same runs.  sfe_dsp_rs_set_algo(SFE_RS_ALGO_DIRECT) and the exact mode keep poly_seg_kernel.
-        rc = SFE_ESTATE;
-        // (1 + U) transforms per block against two dot products of plen taps per output: the transform kernel while U <= 2 + plen / 16 (measured at
-        // 2^26 samples and rate 1.77, profiles/r05/speed_sweep.txt: it takes 0.43 + 0.11 U ms, the direct kernel 0.69 + 0.0072 plen; until round 5
-        // the rule was "12 taps per phase or more" and 16 phases of 127 taps ran 2.2 ms where the direct kernel takes 1.6)
-        const bool gen_pays = r->plen >= 12 && r->U <= 2 + r->plen / 16;
-        if (!exhausted && !r->exact_stream && r->fft_mode >= 0 &&
-            (r->fft_mode > 0 || r->in_u8 || (n_in >= ((size_t)1 << 16) && gen_pays))) {
-            if (!r->gen_tried) {
-                // spectra of the U phase filters (taps[i U + j], i < plen; one zero behind so that the overlap the FIR
-                // planner picks covers plen samples, not plen - 1) through fir_build_tables: one "channel" per phase
-                r->gen_tried = true;
-                std::vector<float> rows((size_t)r->U * (r->plen + 1), 0.0f);
-                for (int j = 0; j < r->U; j++)
-                    for (int i = 0; i < r->plen; i++) rows[(size_t)j * (r->plen + 1) + i] = r->h_taps_pm[(size_t)j * r->plen + i];
-                sfe_fir_t gh = nullptr;
-                if (fir_create_impl(rows.data(), r->plen + 1, 0, 1, r->U, 0, r->device, 1, &gh) == SFE_OK) {
-                    r->gen_tables.reset(static_cast<Fir *>(gh));
-                    if (r->gen_tables->parts != 1) r->gen_tables.reset();
-                }
-            }
-            if (r->gen_tables) {
-                PolyGenArgs ga;
-                memset(&ga, 0, sizeof(ga));
-                ga.in = d_in;
-                ga.out = d_out;
-                ga.hist = r->hist.cur();
-                ga.hs = r->gen_tables->tab.hs;
-                ga.tw1 = r->gen_tables->tab.tw1;
-                ga.tw2 = r->gen_tables->tab.tw2;
-                ga.segs = r->d_segs;
-                ga.chunks = r->d_chunks;
-                ga.n_in = (long long)n_in;
-                ga.in_stride = (long long)in_stride;
-                ga.out_stride = (long long)out_stride;
-                ga.hl = r->hl;
-                ga.U = r->U;
-                ga.plen = r->plen;
-                ga.ovl = (r->plen + 15) & ~15;              // >= plen; the spectra do not depend on it
-                ga.blksize = r->blksize;
-                ga.n_chunks = (int)chunks.size();
-                ga.real = r->data_complex ? 0 : 1;
-                ga.in_u8 = r->in_u8 ? 1 : 0;
-                int max_runs = 0;              // over any two (a real stream's pairs of blocks: three) consecutive calls
-                for (size_t i = 0; i < chunks.size(); i++) {
-                    int sum = chunks[i].n_seg + (i + 1 < chunks.size() ? chunks[i + 1].n_seg : 0);
-                    if (ga.real && i + 2 < chunks.size()) sum += chunks[i + 2].n_seg;
-                    max_runs = sum > max_runs ? sum : max_runs;
-                }
-                rc = launch_poly_gen(ga, max_runs, stepf, r->n_channels, s);
-            }
-        }
-        if (rc == SFE_ESTATE && r->in_u8) {
-            r->u8_refused = true;              // (the public entry converts the bytes and comes back with float32)
-            set_error("rs_process_stream: u8 input at a non-integer step: this call is outside what the transform-domain kernel takes "
-                      "(more than 2032 taps per phase, more than 32 phases, blksize below a block's advance, or a call in the "
-                      "reference's out_len-exhausted state)");
-            return SFE_ESTATE;
-        }
-        if (rc == SFE_ESTATE) {
-            // the direct kernel's LDS: a call larger than it is dealt to `split` workgroups, each tile sized by the largest input
-            // span any part of any call of this launch really reaches (segtile.h).  Per memoised plan and split that span is
-            // worked out once (Rs::SegPlanRef::max_span); the calls outside the memo are walked here.
-            auto max_span = [&](int split) -> long long {
-                int li = 0;
-                while ((1 << li) < split) li++;
-                long long mx = 0;
-                for (size_t i = 0; i < chunks.size(); i++) {
-                    const SegChunk &c = chunks[i];
-                    long long v;
-                    if (c.n_out <= 0) {
-                        v = 0;                          // (every workgroup of the call returns at once)
-                    } else if (chunk_ref[i] >= 0) {
-                        Rs::SegPlanRef &ref = r->seg_refs[(size_t)chunk_ref[i]];
-                        if (ref.max_span[li] < 0)
-                            ref.max_span[li] = (int)seg_max_span(r->seg_table.data() + ref.seg_first, c.m, c.n_out, r->U, r->plen, split);
-                        v = ref.max_span[li];
-                    } else {
-                        v = seg_max_span(&seg_at((size_t)c.seg_first), c.m, c.n_out, r->U, r->plen, split);
-                    }
-                    mx = v > mx ? v : mx;
-                }
-                return mx;
-            };
-            SegTilePlan tp;
-            if (seg_tile_plan(r->U, r->plen, r->esz(), max_m, max_span, &tp) == SFE_OK) {
-                sa.split = tp.split;
-                sa.tile_cap = tp.tile_cap;
-                sa.taps_global = tp.taps_global;
-                rc = launch_poly_seg(sa, r->data_complex, r->exact_stream, r->n_channels, s);
-            }
-        }
-        if (rc == SFE_ESTATE) {
-            // a part of a call reaches more input than the LDS holds, at any split (huge blksize): expand on the host and use
-            // the per-output schedule kernel
-            std::vector<long long> pos(K);
-            std::vector<float> mu(K);
-            for (const SegChunk &c : chunks)
-                for (int i = 0; i < c.n_seg; i++) {
-                    const TlSeg &g = seg_at((size_t)c.seg_first + i);
-                    for (int q = 0; q < g.count; q++) {
-                        const double t = g.t0 + (double)q * (double)g.d, fl = floor(t);
-                        pos[(size_t)c.k_first + g.k0 + q] = c.in_off * r->U + (long long)fl;
-                        mu[(size_t)c.k_first + g.k0 + q] = (float)(t - fl);
-                    }
-                }
-            rc = rs_ensure_sched(r, K + 1);
-            if (rc != SFE_OK) return rc;
-            SFE_HIP(hipStreamSynchronize(s));        // the schedule staging may still be read by the previous call's uploads
-            memcpy(r->h_pos, pos.data(), K * sizeof(long long));
-            memcpy(r->h_mu, mu.data(), K * sizeof(float));
-            SFE_HIP(hipMemcpyAsync(r->d_pos, r->h_pos, K * sizeof(long long), hipMemcpyHostToDevice, s));
-            SFE_HIP(hipMemcpyAsync(r->d_mu, r->h_mu, K * sizeof(float), hipMemcpyHostToDevice, s));
-            a.n_out = (long long)K;
-            a.sched_pos = r->d_pos;
-            a.sched_mu = r->d_mu;
-            rc = launch_poly_sched(a, r->data_complex, r->exact_stream, r->n_channels, s);
-        }
-        if (rc != SFE_OK) return rc;
-        r->ts = st;
-        *n_out = K;
-    }
-    if (capturing) {        // in place behind the main launch: with n_in >= hl the kernel reads `in` only; the time state did not move
+    rc = int_step ? rs_run_int_step(r, c, n_out, &hist_fused) : rs_run_general(r, c, n_out);
+    if (rc != SFE_OK) return rc;
+    if (c.capturing) {        // in place behind the main launch: with n_in >= hl the kernel reads `in` only; the time state did not move
         r->captured = true;
         return launch_history_update(d_in, (long long)n_in, (long long)in_stride, r->hist.cur(),
                                      r->hist.cur(), r->hl, r->data_complex ? 2 : 1, r->n_channels, s, r->in_u8);
@@ -747,6 +635,7 @@ static int rs_process_stream_impl(sfe_rs_t h, const void *d_in, size_t n_in, siz
     return r->hist.carry(r->captured, s);
 }
 
+extern "C" {
 
 // ---- cutting one stream into spans -------------------------
 int sfe_dsp_rs_load_history(sfe_rs_t h, const void *d_prev, size_t n_prev, size_t stride, sfe_stream_t stream)
@@ -802,7 +691,7 @@ int sfe_dsp_rs_plan_seek(sfe_rs_timestate *state, int upsample, uint64_t first_s
 {
     if (!state || upsample < 1) return SFE_EINVAL;
     const float stepf = rate * (float)upsample;
-    if (!(stepf >= 1.0f && stepf == floorf(stepf) && stepf < 1.0e6f)) {
+    if (!rs_step_is_integer(stepf)) {
         set_error("rs_seek: fl(rate*upsample) = %g is not integer-valued: the float32 time recurrence has no closed form "
                   "(carry the state with sfe_dsp_rs_get_state / set_state instead)", (double)stepf);
         return SFE_ESTATE;

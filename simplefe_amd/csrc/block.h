@@ -1,6 +1,6 @@
-// block.h -- what every handle of libsfe_dsp.so is built from: owners of its device memory, pinned host memory, streams and
-// events, the carried pair, the device scope of a create, the handle cast, the table of the unit circle, the opening of
-// every process_stream and the format setter.  The checks of a call's buffers need no HIP and live in call_checks.h, which
+// block.h -- what every handle of libsfe_dsp.so is built from: owners of its device memory, pinned host memory (Buf; the
+// grow-only GrowScratch and Grown), streams and events, the carried pair, the device scope of a create, the handle cast,
+// the table of the unit circle, the opening of every process_stream and the format setter.  The checks of a call's buffers need no HIP and live in call_checks.h, which
 // this includes: the pieces (Span, span_bytes, refuse_*) and the one check each of the burst chain's three families --
 // rows (api_vit.hip, api_reed.hip, api_ldpc.hip), windows (api_burst.hip, api_ofdm.hip), frames (api_mod.hip,
 // api_ofdmmod.hip).  The FIR, resampler and pipe handles (host.h, api_pipe.hip) and every block's api_*.hip use it.  HOST CODE
@@ -159,6 +159,36 @@ struct GrowScratch {
         return rc;
     }
     template <class T> T *as() const { return reinterpret_cast<T *>(d.p); }
+};
+
+// Memory that only grows, with the capacity it was last given: reserve(n) is a comparison while n fits.  The caller orders
+// the regrowth against work in flight (GrowScratch above does so itself) and picks the policy: `to` is the new capacity (exact: n).
+// A failed regrowth leaves capacity 0 and nothing to read.  B: a Buf, or several that share one capacity (Mirror; grow(n)).
+template <class B>
+struct Grown {
+    B b;
+    size_t cap = 0;
+    int reserve(size_t n, size_t to)
+    {
+        if (n <= cap) return SFE_OK;
+        cap = 0;
+        const int rc = b.grow(to);
+        if (rc == SFE_OK) cap = to;
+        return rc;
+    }
+    int reserve(size_t n) { return reserve(n, n); }
+    B *operator->() { return &b; }
+};
+// a device array and the pinned staging it is uploaded from
+template <class T>
+struct Mirror {
+    DevBuf<T> d;
+    PinnedBuf<T> h;
+    int grow(size_t n)
+    {
+        const int rc = d.grow(n);
+        return rc != SFE_OK ? rc : h.grow(n);
+    }
 };
 
 // A create runs on the handle's device and leaves the caller's current device as it found it, on every way out.

@@ -3,11 +3,13 @@
 //   api.hip          errors, devices, memory, timers, the synthetic stream, the wire-format converters
 //   api_plans.hip    folding (U, step, pos0) into the polyphase kernels' tap tables and spectra
 //   api_fir.hip      the FIR handle: tables, partitions, variants, carried state, sfe_dsp_fir_*
-//   api_rs.hip       the resample / decimate handle: time law, run memo, kernel choice, sfe_dsp_rs_*
+//   api_rs.hip       the resample / decimate handle: a call's checks, kernel choice, plan upload, carried state, sfe_dsp_rs_*
+//   rs_plan.h        what api_rs.hip works out before it launches, without HIP: the integer-step closed form, the general-rate
+//                    plan and its run memo, the walks over a plan (included below; tests/host/test_rs_plan.cpp)
 //   api_pipe.hip     the pinned host pipe over either handle, sfe_dsp_*_pipe_*
 //   group.hip        channel blocks over several devices, sfe_dsp_*_group_* (over the public C ABI only)
-//   block.h          what every handle is built from: owners of device and pinned memory, streams and events, the carried pair,
-//                    create's device scope, the handle cast, process_stream's refusals (included below)
+//   block.h          what every handle is built from: owners of device and pinned memory (grow-only ones too), streams and events,
+//                    the carried pair, create's device scope, the handle cast, process_stream's refusals (included below)
 //   api_<block>.hip  the streaming blocks over block.h: chan, combine, ddc, psd, corr, iir, beam, cov, mvdr, eig, burst, vit, mod
 #pragma once
 #include <math.h>
@@ -29,6 +31,7 @@
 
 #include "common.h"
 #include "block.h"
+#include "rs_plan.h"
 #include "segtile.h"
 #include "timelaw.h"
 
@@ -125,48 +128,31 @@ struct Rs {
     CarriedPair hist;
     bool captured = false;                 // a call of this handle sits in a hipGraph that names hist.cur() (see CarriedPair::carry)
     sfe_rs_timestate ts = {0, 0.0f, 0};
-    // class-compatible host path staging (one channel)
-    DevBuf<char> d_in, d_out;
-    DevBuf<long long> d_pos;
-    DevBuf<float> d_mu;
-    size_t out_cap = 0, sched_cap = 0;
-    PinnedBuf<char> h_stage;               // in/out staging
-    size_t h_stage_bytes = 0;
+    // class-compatible host path staging (one channel); the grow-only ones (block.h: Grown) keep the policy of their caller
+    DevBuf<char> d_in;
+    Grown<DevBuf<char>> d_out;             // bytes
+    struct Sched {                         // per-output schedule, (pos, mu): device arrays and their staging, one capacity
+        Mirror<long long> pos;
+        Mirror<float> mu;
+        int grow(size_t n)
+        {
+            const int rc = pos.grow(n);
+            return rc != SFE_OK ? rc : mu.grow(n);
+        }
+    };
+    Grown<Sched> sched;
+    Grown<PinnedBuf<char>> h_stage;        // in/out staging
     // wire-format input on a shape no fused u8 kernel takes (steps beyond the tiled kernels, a general rate outside the transform kernel):
     // the call's bytes are converted ONCE into this grow-only float32 buffer and the float path runs (api_rs.hip: sfe_dsp_rs_process_stream)
-    DevBuf<float> d_u8f;
-    size_t d_u8f_floats = 0;
+    Grown<DevBuf<float>> d_u8f;
     hipStream_t u8f_stream = nullptr;      // the caller's: borrowed
     bool u8_refused = false;               // set by the implementation where it would have refused a u8 call, nothing launched, no state touched
-    PinnedBuf<long long> h_pos;            // schedule staging
-    PinnedBuf<float> h_mu;
-    DevBuf<TlSeg> d_segs;                  // run-length plans
-    DevBuf<SegChunk> d_chunks;
-    PinnedBuf<TlSeg> h_segs;
-    PinnedBuf<SegChunk> h_chunks;
-    size_t segs_cap = 0, chunks_cap = 0;
+    Grown<Mirror<TlSeg>> segs;             // run-length plans: the memo's table, a launch's own runs behind it
+    Grown<Mirror<SegChunk>> chunks;
     Event ev_plan;                         // recorded behind a call's plan uploads: the pinned staging is free again once it fires
     hipStream_t plan_stream = nullptr;     // ... on this stream, the caller's: borrowed (the device-side plan arrays are ordered by it)
-    // General rate: the plan of one blksize-sample reference call depends only on the time state the call
-    // starts in, and that state is a multiple of the float32 grid of the call's LAST binade inside
-    // [-1, step) -- a few thousand possible values (blksize*U = 16384: 2^-10 apart) -- so plans are
-    // memoised per start state: a 2^28-sample call replays 65 536 reference calls as table look-ups
-    // instead of 65 536 x ~40 runs of float arithmetic (36 ms -> ~2 ms on the host), and the run table
-    // lives on the device across calls (only what is new is uploaded).
-    struct SegPlanRef {
-        int seg_first, n_seg, n_out;
-        sfe_rs_timestate after;
-        int next = -1;                     // index of the plan for the state this call ends in, once it has been met:
-                                           // a stream of full-size calls then walks the plans by index, no hashing
-        int max_span[7] = {-1, -1, -1, -1, -1, -1, -1};     // per log2(split): the largest tile a part of this call needs
-                                                            // (segtile.h: seg_max_span), once it has been asked for
-    };
-    std::unordered_map<uint64_t, int> seg_memo;      // start state -> index into seg_refs
-    std::vector<SegPlanRef> seg_refs;
-    std::vector<TlSeg> seg_table;          // runs of the memoised calls, in the order they were first met
-    size_t seg_uploaded = 0;               // leading entries of seg_table already in d_segs
-    float memo_rate = 0.0f;                // the memo is for one (rate, blksize)
-    int memo_m = 0;
+    RsMemo memo;                           // general rate: the plans of the reference calls met so far, per start state (rs_plan.h)
+    size_t seg_uploaded = 0;               // leading entries of memo.table already in segs->d (void once the memo is cleared or segs regrown)
     int esz() const { return data_complex ? 8 : 4; }
 };
 Rs *as_rs(void *h);
