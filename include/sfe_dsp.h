@@ -441,6 +441,7 @@ int sfe_dsp_chan_set_input_format(sfe_chan_t h, int fmt);
  * a refusal.  Cutting a stream into calls at any multiple of D gives the one-call result bit for
  * bit.  Asynchronous on `stream`, no host synchronisation or allocation.  The output counter
  * lives on the host: a call on a stream under graph capture is SFE_ESTATE, nothing enqueued. */
+/* A stride that takes a buffer's byte range to 2^62 is SFE_EINVAL too; nothing is launched. */
 int sfe_dsp_chan_process_stream(sfe_chan_t h, const void *d_in, size_t n_in, size_t in_stride,
                                 void *d_out, size_t out_stride, size_t *n_out, sfe_stream_t stream);
 /* Zero the carried state and the output counter (a fresh handle). */
@@ -487,6 +488,7 @@ int sfe_dsp_combine_set_output_format(sfe_combine_t h, int fmt);
  * calls at any instant gives the one-call result bit for bit.  Asynchronous on `stream`, no host
  * synchronisation or allocation.  The instant counter lives on the host: a call on a stream under
  * graph capture is SFE_ESTATE, nothing enqueued. */
+/* A stride that takes a buffer's byte range to 2^62 is SFE_EINVAL too; nothing is launched. */
 int sfe_dsp_combine_process_stream(sfe_combine_t h, const void *d_in, size_t n_in, size_t in_stride,
                                    void *d_out, size_t out_stride, size_t *n_out, sfe_stream_t stream);
 /* Zero the carried state and the instant counter (a fresh handle). */
@@ -542,6 +544,7 @@ int sfe_dsp_ddc_set_freqs(sfe_ddc_t h, const double *freqs);
  * a refusal.  Cutting a stream into calls at any multiple of D gives the one-call result bit for
  * bit.  Asynchronous on `stream`, no host synchronisation or allocation.  The sample counter
  * lives on the host: a call on a stream under graph capture is SFE_ESTATE, nothing enqueued. */
+/* A stride that takes a buffer's byte range to 2^62 is SFE_EINVAL too; nothing is launched. */
 int sfe_dsp_ddc_process_stream(sfe_ddc_t h, const void *d_in, size_t n_in, size_t in_stride,
                                void *d_out, size_t out_stride, size_t *n_out, sfe_stream_t stream);
 /* Zero the carried state and the sample counter; the tunings are kept. */
@@ -602,6 +605,7 @@ int sfe_dsp_psd_set_input_format(sfe_psd_t h, int fmt);
  * call arrives (synchronise, free, allocate): that is the one allocation, and the one host
  * synchronisation, a call may make.  The segment counter lives on the host: a call on a stream
  * under graph capture is SFE_ESTATE, nothing enqueued. */
+/* A stride that takes a buffer's byte range to 2^62 is SFE_EINVAL too; nothing is launched. */
 int sfe_dsp_psd_process_stream(sfe_psd_t h, const void *d_in, size_t n_in, size_t in_stride,
                                void *d_out, size_t out_stride, size_t *n_rows, sfe_stream_t stream);
 /* Zero the carried state and the segment counter (a fresh handle); an unfinished row is dropped. */
@@ -667,6 +671,7 @@ int sfe_dsp_corr_set_input_format(sfe_corr_t h, int fmt);
  * when a larger call arrives (synchronise, free, allocate): the one allocation, and the one host
  * synchronisation, a call may make.  The sample counter lives on the host: a call on a stream
  * under graph capture is SFE_ESTATE, nothing enqueued. */
+/* A stride that takes a buffer's byte range to 2^62 is SFE_EINVAL too; nothing is launched. */
 int sfe_dsp_corr_process_stream(sfe_corr_t h, const void *d_in, size_t n_in, size_t in_stride,
                                 void *d_peak_val, void *d_peak_idx, size_t peak_stride,
                                 void *d_metric, size_t metric_stride,
@@ -737,6 +742,7 @@ int sfe_dsp_iir_set_input_format(sfe_iir_t h, int fmt);
  * call and grown only when a larger call arrives (synchronise, free, allocate): that is the one
  * allocation, and the one host synchronisation, a call may make.  The sample counter lives on the
  * host: a call on a stream under graph capture is SFE_ESTATE, nothing enqueued. */
+/* A stride that takes a buffer's byte range to 2^62 is SFE_EINVAL too; nothing is launched. */
 int sfe_dsp_iir_process_stream(sfe_iir_t h, const void *d_in, size_t n_in, size_t in_stride,
                                void *d_out, size_t out_stride, size_t *n_out, sfe_stream_t stream);
 /* Zero the carried state and the sample counter (a fresh handle); the coefficients are kept. */
@@ -808,6 +814,7 @@ int sfe_dsp_beam_set_weights(sfe_beam_t h, const float *weights, const float *we
  * stream under graph capture is SFE_ESTATE, nothing enqueued: sfe_dsp_beam_set_weights may
  * replace the table a captured call would have pinned.
  * There is no reset: there is nothing to reset. */
+/* A stride that takes a buffer's byte range to 2^62 is SFE_EINVAL too; nothing is launched. */
 int sfe_dsp_beam_process_stream(sfe_beam_t h, const void *d_in, size_t n_in, size_t in_stride,
                                 void *d_out, size_t out_stride, size_t *n_out, sfe_stream_t stream);
 int sfe_dsp_beam_destroy(sfe_beam_t h);
@@ -882,6 +889,7 @@ int sfe_dsp_cov_set_input_format(sfe_cov_t h, int fmt);
  * arrives (synchronise, free, allocate): that is the one allocation, and the one host
  * synchronisation, a call may make.  The instant counter lives on the host: a call on a stream
  * under graph capture is SFE_ESTATE, nothing enqueued. */
+/* A stride that takes a buffer's byte range to 2^62 is SFE_EINVAL too; nothing is launched. */
 int sfe_dsp_cov_process_stream(sfe_cov_t h, const void *d_in, size_t n_in, size_t in_stride,
                                void *d_out, size_t out_stride, size_t *n_rows, sfe_stream_t stream);
 /* Zero the carried state and the instant counter (a fresh handle); an unfinished row is dropped. */
@@ -976,6 +984,7 @@ int sfe_dsp_mvdr_set_loading(sfe_mvdr_t h, float load_rel, float load_abs);
  * does not synchronise the host, carries no state (there is no reset).  A call on a stream under
  * graph capture is SFE_ESTATE, nothing enqueued: sfe_dsp_mvdr_set_steering may replace the tables
  * a captured call would have pinned. */
+/* A stride that takes a buffer's byte range to 2^62 is SFE_EINVAL too; nothing is launched. */
 int sfe_dsp_mvdr_process_stream(sfe_mvdr_t h, const void *d_gram, size_t n_rows, size_t in_stride,
                                 void *d_real_matrix, size_t out_stride, void *d_power,
                                 size_t power_stride, void *d_status, size_t status_stride,
@@ -1108,6 +1117,7 @@ int sfe_dsp_eig_set_signal_dim(sfe_eig_t h, int signal_dim);
  * on `stream`; allocates nothing, does not synchronise the host, carries no state (there is no
  * reset).  A call on a stream under graph capture is SFE_ESTATE, nothing enqueued:
  * sfe_dsp_eig_set_steering may replace the table a captured call would have pinned. */
+/* A stride that takes a buffer's byte range to 2^62 is SFE_EINVAL too; nothing is launched. */
 int sfe_dsp_eig_process_stream(sfe_eig_t h, const void *d_gram, size_t n_rows, size_t in_stride,
                                void *d_values, size_t values_stride, void *d_null,
                                size_t null_stride, void *d_vectors, size_t vectors_stride,

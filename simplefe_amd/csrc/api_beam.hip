@@ -166,27 +166,12 @@ int sfe_dsp_beam_process_stream(sfe_beam_t h, const void *d_in, size_t n_in, siz
     static const char who[] = "beam_process_stream";
     Beam *p = stream_handle(as_beam(h), who, n_out);
     if (!p) return SFE_EINVAL;
-    int rc = refuse_2_31(who, n_in);
-    if (rc != SFE_OK) return rc;
-    if (n_in == 0) return SFE_OK;
-    rc = refuse_null(who, {d_in, d_out});
-    if (rc != SFE_OK) return rc;
-    if (out_stride < n_in) {
-        set_error("beam_process_stream: out_stride %zu < n_in = %zu", out_stride, n_in);
-        return SFE_ERANGE;
-    }
-    if (in_stride < n_in) {
-        set_error("beam_process_stream: in_stride %zu < n_in %zu", in_stride, n_in);
-        return SFE_EINVAL;
-    }
-    const size_t isz = p->in_u8 ? 2 : 8;
-    const size_t in_b = (((size_t)p->S * p->M - 1) * in_stride + n_in) * isz;
-    const size_t out_b = (((size_t)p->B * p->M - 1) * out_stride + n_in) * sizeof(v2f);
-    const Span in{d_in, in_b, isz}, out{d_out, out_b, sizeof(v2f)};
+    static const StreamNouns nouns{"n_in = ", "cf32 8 B, u8 (I,Q) pairs 2 B", true, false};
+    bool go;
+    int rc = check_streams(who, nouns, d_in, n_in, in_stride, (size_t)p->S * p->M, p->in_u8 ? 2 : 8, d_out, out_stride, n_in,
+                           (size_t)p->B * p->M, sizeof(v2f), &go);
+    if (rc != SFE_OK || !go) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = refuse_misaligned(who, "cf32 8 B, u8 (I,Q) pairs 2 B", {in, out})) != SFE_OK ||
-        (rc = refuse_overlap(who, in, {out})) != SFE_OK)
-        return rc;
     if (stream_is_capturing(s)) {       // set_weights may replace the table a captured call would have pinned
         set_error("beam_process_stream: graph capture is not supported (set_weights may replace the weight table)");
         return SFE_ESTATE;

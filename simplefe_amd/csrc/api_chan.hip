@@ -114,26 +114,14 @@ int sfe_dsp_chan_process_stream(sfe_chan_t h, const void *d_in, size_t n_in, siz
         set_error("chan_process_stream: n_in = %zu is not a multiple of decim = %d", n_in, c->D);
         return SFE_EINVAL;
     }
+    static const StreamNouns nouns{"n_out ", "cf32 8 B, u8 (I,Q) pairs 2 B", false, true};
     const size_t no = n_in / c->D;
-    if (n_in == 0) return SFE_OK;
-    int rc = refuse_null(who, {d_in, d_out});
-    if (rc != SFE_OK) return rc;
-    if (out_stride < no) {
-        set_error("chan_process_stream: out_stride %zu < n_out %zu", out_stride, no);
-        return SFE_ERANGE;
-    }
-    if (c->n_streams > 1 && in_stride < n_in) {
-        set_error("chan_process_stream: in_stride %zu < n_in %zu with %d streams", in_stride, n_in, c->n_streams);
-        return SFE_EINVAL;
-    }
-    const size_t isz = c->in_u8 ? 2 : 8;
-    const size_t in_b = ((size_t)(c->n_streams - 1) * in_stride + n_in) * isz;
-    const size_t out_b = ((size_t)c->n_streams * c->M - 1) * out_stride * sizeof(v2f) + no * sizeof(v2f);
-    const Span in{d_in, in_b, isz}, out{d_out, out_b, sizeof(v2f)};
+    bool go;
+    int rc = check_streams(who, nouns, d_in, n_in, in_stride, c->n_streams, c->in_u8 ? 2 : 8, d_out, out_stride, no,
+                           (size_t)c->n_streams * c->M, sizeof(v2f), &go);
+    if (rc != SFE_OK || !go) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = refuse_misaligned(who, "cf32 8 B, u8 (I,Q) pairs 2 B", {in, out})) != SFE_OK || (rc = refuse_overlap(who, in, {out})) != SFE_OK ||
-        (rc = refuse_capture(who, "output", s)) != SFE_OK)     // the counter: the D = M/2 parity
-        return rc;
+    if ((rc = refuse_capture(who, "output", s)) != SFE_OK) return rc;       // the counter: the D = M/2 parity
     SFE_ON_DEVICE(c->device);
     rc = launch_chan(c->logm, c->D != c->M, c->in_u8, d_in, (long long)in_stride, c->hist.cur<v2f>(), c->hist.next<v2f>(), c->d_taps,
                      c->d_tw, static_cast<v2f *>(d_out), (long long)out_stride, (long long)n_in, (long long)no, c->Ppad, c->H,

@@ -131,10 +131,8 @@ int sfe_dsp_combine_process_stream(sfe_combine_t h, const void *d_in, size_t n_i
         set_error("combine_process_stream: out_stride %zu must be even with SFE_FMT_TX10 (whole 5-byte groups per stream)", out_stride);
         return SFE_EINVAL;
     }
-    const size_t in_b = ((size_t)c->n_streams * c->M - 1) * in_stride * sizeof(v2f) + n_in * sizeof(v2f);
-    const size_t out_b = c->out_tx10 ? ((size_t)(c->n_streams - 1) * (out_stride / 2) + no / 2) * 5
-                                     : ((size_t)(c->n_streams - 1) * out_stride + no) * sizeof(v2f);
-    const Span in{d_in, in_b, sizeof(v2f)}, out{d_out, out_b, c->out_tx10 ? 1 : sizeof(v2f)};
+    Span in, out;
+    if (!combine_ranges(c->n_streams, c->M, c->out_tx10, d_in, n_in, in_stride, d_out, no, out_stride, &in, &out)) return refuse_2_62(who);
     rc = refuse_misaligned(who, "cf32 8 B", {in, out});
     if (rc != SFE_OK) return rc;
     // the kernel indexes within one stream in 32 bits

@@ -187,13 +187,13 @@ int sfe_dsp_corr_process_stream(sfe_corr_t h, const void *d_in, size_t n_in, siz
         set_error("corr_process_stream: in_stride %zu < n_in %zu with %d streams", in_stride, n_in, p->n_streams);
         return SFE_EINVAL;
     }
-    const size_t isz = p->in_u8 ? 2 : 8;
-    const size_t in_b = ((size_t)(p->n_streams - 1) * in_stride + n_in) * isz;
-    const size_t peak_b = ((rows - 1) * peak_stride + blocks) * 4;
-    const size_t met_b = d_metric ? ((rows - 1) * metric_stride + n_in) * 4 : 0;
-    const Span in{d_in, in_b, isz}, val{d_peak_val, peak_b, 4}, idx{d_peak_idx, peak_b, 4}, met{d_metric, met_b, 4};
-    if ((rc = refuse_misaligned(who, "cf32 8 B, u8 (I,Q) pairs 2 B, outputs 4 B", {in, val, idx, met})) != SFE_OK ||
-        (rc = refuse_overlap(who, in, {val, idx, met})) != SFE_OK || (rc = refuse_outputs_overlap(who, {val, idx, met})) != SFE_OK)
+    CorrRanges r;
+    if (!corr_ranges(p->n_streams, p->K, p->in_u8 ? 2 : 8, d_in, n_in, in_stride, d_peak_val, d_peak_idx, blocks, peak_stride, d_metric,
+                     metric_stride, &r))
+        return refuse_2_62(who);
+    if ((rc = refuse_misaligned(who, "cf32 8 B, u8 (I,Q) pairs 2 B, outputs 4 B", {r.in, r.val, r.idx, r.met})) != SFE_OK ||
+        (rc = refuse_overlap(who, r.in, {r.val, r.idx, r.met})) != SFE_OK ||
+        (rc = refuse_outputs_overlap(who, {r.val, r.idx, r.met})) != SFE_OK)
         return rc;
     hipStream_t s = (hipStream_t)stream;
     rc = refuse_capture(who, "sample", s);

@@ -104,29 +104,15 @@ int sfe_dsp_cov_process_stream(sfe_cov_t h, const void *d_in, size_t n_in, size_
         set_error("cov_process_stream: n_in = %zu is not a multiple of the chunk = %d", n_in, COV_T);
         return SFE_EINVAL;
     }
-    int rc = refuse_2_31(who, n_in);
-    if (rc != SFE_OK) return rc;
-    if (n_in == 0) return SFE_OK;
+    static const StreamNouns nouns{"n_rows * (2 n_in_streams)^2 = ", "cf32 8 B, u8 (I,Q) pairs 2 B, float32 rows 4 B", true, false};
     const size_t q = n_in / COV_T, j0 = (size_t)(p->chunks % (unsigned long long)p->AC), rows = (j0 + q) / p->AC;
     const size_t n2 = 2 * (size_t)p->S, gram = n2 * n2;
-    rc = refuse_null(who, {d_in, d_out});
-    if (rc != SFE_OK) return rc;
-    if (out_stride < rows * gram) {
-        set_error("cov_process_stream: out_stride %zu < n_rows * (2 n_in_streams)^2 = %zu", out_stride, rows * gram);
-        return SFE_ERANGE;
-    }
-    if (in_stride < n_in) {
-        set_error("cov_process_stream: in_stride %zu < n_in %zu", in_stride, n_in);
-        return SFE_EINVAL;
-    }
-    const size_t isz = p->in_u8 ? 2 : 8;
-    const size_t in_b = (((size_t)p->S * p->M - 1) * in_stride + n_in) * isz;
-    const size_t out_b = rows ? ((size_t)(p->M - 1) * out_stride + rows * gram) * sizeof(float) : 0;
-    const Span in{d_in, in_b, isz}, out{d_out, out_b, sizeof(float)};
+    bool go;
+    int rc = check_streams(who, nouns, d_in, n_in, in_stride, (size_t)p->S * p->M, p->in_u8 ? 2 : 8, d_out, out_stride, rows * gram, p->M,
+                           sizeof(float), &go);
+    if (rc != SFE_OK || !go) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = refuse_misaligned(who, "cf32 8 B, u8 (I,Q) pairs 2 B, float32 rows 4 B", {in, out})) != SFE_OK ||
-        (rc = refuse_overlap(who, in, {out})) != SFE_OK || (rc = refuse_capture(who, "instant", s)) != SFE_OK)
-        return rc;
+    if ((rc = refuse_capture(who, "instant", s)) != SFE_OK) return rc;
     SFE_ON_DEVICE(p->device);
     // the one allocation a call may make: the scratch of group sums grows when a larger call than any before arrives
     // (none when a chunk is a whole row, A = T: the rows are written without it)

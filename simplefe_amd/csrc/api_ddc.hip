@@ -183,28 +183,14 @@ int sfe_dsp_ddc_process_stream(sfe_ddc_t h, const void *d_in, size_t n_in, size_
         set_error("ddc_process_stream: n_in = %zu is not a multiple of decim = %d", n_in, c->D);
         return SFE_EINVAL;
     }
-    int rc = refuse_2_31(who, n_in);
-    if (rc != SFE_OK) return rc;
+    static const StreamNouns nouns{"n_out ", "cf32 8 B, real float 4 B, u8 (I,Q) pairs 2 B", true, true};
     const size_t no = n_in / c->D;
-    if (n_in == 0) return SFE_OK;
-    rc = refuse_null(who, {d_in, d_out});
-    if (rc != SFE_OK) return rc;
-    if (out_stride < no) {
-        set_error("ddc_process_stream: out_stride %zu < n_out %zu", out_stride, no);
-        return SFE_ERANGE;
-    }
-    if (c->n_streams > 1 && in_stride < n_in) {
-        set_error("ddc_process_stream: in_stride %zu < n_in %zu with %d streams", in_stride, n_in, c->n_streams);
-        return SFE_EINVAL;
-    }
-    const size_t isz = c->in_u8 ? 2 : c->complex_in ? 8 : 4;
-    const size_t in_b = ((size_t)(c->n_streams - 1) * in_stride + n_in) * isz;
-    const size_t out_b = ((size_t)c->n_streams * c->K - 1) * out_stride * sizeof(v2f) + no * sizeof(v2f);
-    const Span in{d_in, in_b, isz}, out{d_out, out_b, sizeof(v2f)};
+    bool go;
+    int rc = check_streams(who, nouns, d_in, n_in, in_stride, c->n_streams, c->in_u8 ? 2 : c->complex_in ? 8 : 4, d_out, out_stride, no,
+                           (size_t)c->n_streams * c->K, sizeof(v2f), &go);
+    if (rc != SFE_OK || !go) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = refuse_misaligned(who, "cf32 8 B, real float 4 B, u8 (I,Q) pairs 2 B", {in, out})) != SFE_OK ||
-        (rc = refuse_overlap(who, in, {out})) != SFE_OK || (rc = refuse_capture(who, "sample", s)) != SFE_OK)   // the lead factors' phase
-        return rc;
+    if ((rc = refuse_capture(who, "sample", s)) != SFE_OK) return rc;       // the lead factors' phase
     SFE_ON_DEVICE(c->device);
     const int fmt = c->in_u8 ? 1 : c->complex_in ? 0 : 2;
     rc = launch_ddc(fmt, d_in, (long long)in_stride, c->hist.cur<void>(), c->hist.next<void>(), c->d_taps, c->d_inc,

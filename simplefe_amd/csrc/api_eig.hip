@@ -381,14 +381,15 @@ int sfe_dsp_eig_process_stream(sfe_eig_t h, const void *d_gram, size_t n_rows, s
         set_error("eig_process_stream: in_stride %zu < n_rows * (2 n_in)^2 = %zu", in_stride, n_rows * gram);
         return SFE_EINVAL;
     }
-    const Span in{d_gram, ((M - 1) * in_stride + n_rows * gram) * sizeof(float), sizeof(float)};
-    const Span va{d_values, ((n_rows - 1) * values_stride + M * n2) * sizeof(float), sizeof(float)};
-    const Span nu{d_null, d_null ? ((n_rows - 1) * null_stride + M * B) * sizeof(float) : 0, sizeof(float)};
-    const Span ve{d_vectors, d_vectors ? ((n_rows - 1) * vectors_stride + M * mat) * sizeof(float) : 0, sizeof(float)};
-    const Span st{d_status, d_status ? ((n_rows - 1) * status_stride + M) * sizeof(int) : 0, sizeof(int)};
+    Span in, o[4];      // the values, the null spectrum, the vectors, the status
+    if (!solver_ranges(M, d_gram, n_rows, in_stride, gram,
+                       {RowOut{d_values, values_stride, M * n2}, RowOut{d_null, null_stride, M * B}, RowOut{d_vectors, vectors_stride, M * mat},
+                        RowOut{d_status, status_stride, M}},
+                       &in, o))
+        return refuse_2_62(who);
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = refuse_misaligned(who, "float32 and int32 4 B", {in, va, nu, ve, st})) != SFE_OK ||
-        (rc = refuse_overlap(who, in, {va, nu, ve, st})) != SFE_OK)
+    if ((rc = refuse_misaligned(who, "float32 and int32 4 B", {in, o[0], o[1], o[2], o[3]})) != SFE_OK ||
+        (rc = refuse_overlap(who, in, {o[0], o[1], o[2], o[3]})) != SFE_OK)
         return rc;
     if (stream_is_capturing(s)) {       // set_steering may replace the table a captured call would have pinned
         set_error("eig_process_stream: graph capture is not supported (set_steering may replace the steering table)");

@@ -215,27 +215,13 @@ int sfe_dsp_iir_process_stream(sfe_iir_t h, const void *d_in, size_t n_in, size_
         set_error("iir_process_stream: n_in = %zu is not a multiple of the block = %zu", n_in, G);
         return SFE_EINVAL;
     }
-    int rc = refuse_2_31(who, n_in);
-    if (rc != SFE_OK) return rc;
-    if (n_in == 0) return SFE_OK;
-    rc = refuse_null(who, {d_in, d_out});
-    if (rc != SFE_OK) return rc;
-    if (out_stride < n_in) {
-        set_error("iir_process_stream: out_stride %zu < n_in = %zu", out_stride, n_in);
-        return SFE_ERANGE;
-    }
-    if (p->n_streams > 1 && in_stride < n_in) {
-        set_error("iir_process_stream: in_stride %zu < n_in %zu with %d streams", in_stride, n_in, p->n_streams);
-        return SFE_EINVAL;
-    }
-    const size_t isz = p->in_u8 ? 2 : p->data_complex ? 8 : 4, osz = p->data_complex ? 8 : 4;
-    const size_t in_b = ((size_t)(p->n_streams - 1) * in_stride + n_in) * isz;
-    const size_t out_b = ((size_t)(p->n_streams - 1) * out_stride + n_in) * osz;
-    const Span in{d_in, in_b, isz}, out{d_out, out_b, osz};
+    static const StreamNouns nouns{"n_in = ", "cf32 8 B, u8 (I,Q) pairs 2 B, float32 4 B", true, true};
+    bool go;
+    int rc = check_streams(who, nouns, d_in, n_in, in_stride, p->n_streams, p->in_u8 ? 2 : p->data_complex ? 8 : 4, d_out, out_stride, n_in,
+                           p->n_streams, p->data_complex ? 8 : 4, &go);
+    if (rc != SFE_OK || !go) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = refuse_misaligned(who, "cf32 8 B, u8 (I,Q) pairs 2 B, float32 4 B", {in, out})) != SFE_OK ||
-        (rc = refuse_overlap(who, in, {out})) != SFE_OK || (rc = refuse_capture(who, "sample", s)) != SFE_OK)   // counted in blocks
-        return rc;
+    if ((rc = refuse_capture(who, "sample", s)) != SFE_OK) return rc;       // counted in blocks
     SFE_ON_DEVICE(p->device);
     // the one allocation a call may make: the table of block and group states grows when a larger call than any before arrives
     // (sized for the most groups a call of nb blocks can touch, wherever it starts)

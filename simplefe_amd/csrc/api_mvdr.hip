@@ -319,13 +319,13 @@ int sfe_dsp_mvdr_process_stream(sfe_mvdr_t h, const void *d_gram, size_t n_rows,
         set_error("mvdr_process_stream: in_stride %zu < n_rows * (2 n_in)^2 = %zu", in_stride, n_rows * gram);
         return SFE_EINVAL;
     }
-    const Span in{d_gram, ((M - 1) * in_stride + n_rows * gram) * sizeof(float), sizeof(float)};
-    const Span out{d_real_matrix, ((n_rows - 1) * out_stride + M * mat) * sizeof(float), sizeof(float)};
-    const Span pw{d_power, d_power ? ((n_rows - 1) * power_stride + M * B) * sizeof(float) : 0, sizeof(float)};
-    const Span st{d_status, d_status ? ((n_rows - 1) * status_stride + M) * sizeof(int) : 0, sizeof(int)};
+    Span in, o[3];      // the matrix, the power, the status
+    if (!solver_ranges(M, d_gram, n_rows, in_stride, gram,
+                       {RowOut{d_real_matrix, out_stride, M * mat}, RowOut{d_power, power_stride, M * B}, RowOut{d_status, status_stride, M}}, &in, o))
+        return refuse_2_62(who);
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = refuse_misaligned(who, "float32 and int32 4 B", {in, out, pw, st})) != SFE_OK ||
-        (rc = refuse_overlap(who, in, {out, pw, st})) != SFE_OK)
+    if ((rc = refuse_misaligned(who, "float32 and int32 4 B", {in, o[0], o[1], o[2]})) != SFE_OK ||
+        (rc = refuse_overlap(who, in, {o[0], o[1], o[2]})) != SFE_OK)
         return rc;
     if (stream_is_capturing(s)) {       // set_steering may replace the tables a captured call would have pinned
         set_error("mvdr_process_stream: graph capture is not supported (set_steering may replace the steering table)");

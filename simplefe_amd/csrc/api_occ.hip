@@ -130,10 +130,8 @@ int sfe_dsp_occ_process_stream(sfe_occ_t h, const float *d_in, size_t n_streams,
     if (!span_bytes(n_streams - 1, in_stride, n_rows * N, sizeof(float), &in_b) ||
         !span_bytes(n_streams - 1, out_stride, n_rows, sizeof(sfe_occ_info), &info_b) ||
         !span_bytes(n_streams - 1, out_stride, n_rows, sizeof(sfe_occ_rec) * E, &rec_b) ||
-        (d_mask && !span_bytes(n_streams - 1, out_stride, n_rows, N, &mask_b))) {
-        set_error("occ_process_stream: the strides take a byte range to 2^62");
-        return SFE_EINVAL;
-    }
+        (d_mask && !span_bytes(n_streams - 1, out_stride, n_rows, N, &mask_b)))
+        return refuse_2_62(who);
     const Span in{d_in, in_b, sizeof(float)}, info{d_info, info_b, 4}, rec{d_rec, rec_b, 4}, mask{d_mask, mask_b, 1};
     if ((rc = refuse_misaligned(who, "float32, info and records 4 B", {in, info, rec})) != SFE_OK ||
         (rc = refuse_overlap(who, in, {info, rec, mask})) != SFE_OK)

@@ -133,31 +133,12 @@ int sfe_dsp_polar_process_stream(sfe_polar_t h, const void *d_in, size_t n_in, s
     static const char who[] = "polar_process_stream";
     Polar *p = stream_handle(as_polar(h), who, n_out);
     if (!p) return SFE_EINVAL;
-    int rc = refuse_2_31(who, n_in);
-    if (rc != SFE_OK) return rc;
-    if (n_in == 0) return SFE_OK;
-    rc = refuse_null(who, {d_in, d_out});
-    if (rc != SFE_OK) return rc;
-    if (out_stride < n_in) {
-        set_error("polar_process_stream: out_stride %zu < n_in = %zu", out_stride, n_in);
-        return SFE_ERANGE;
-    }
-    if (p->n_streams > 1 && in_stride < n_in) {
-        set_error("polar_process_stream: in_stride %zu < n_in %zu with %d streams", in_stride, n_in, p->n_streams);
-        return SFE_EINVAL;
-    }
-    const size_t isz = p->in_u8 ? 2 : 8;
-    size_t in_b, out_b;
-    if (!span_bytes((size_t)p->n_streams - 1, in_stride, n_in, isz, &in_b) ||
-        !span_bytes((size_t)p->n_streams - 1, out_stride, n_in, sizeof(float), &out_b)) {
-        set_error("polar_process_stream: the strides take a byte range to 2^62");
-        return SFE_EINVAL;
-    }
-    const Span in{d_in, in_b, isz}, out{d_out, out_b, sizeof(float)};
+    static const StreamNouns nouns{"n_in = ", "cf32 8 B, u8 (I,Q) pairs 2 B, float32 4 B", true, true};
+    bool go;
+    int rc = check_streams(who, nouns, d_in, n_in, in_stride, p->n_streams, p->in_u8 ? 2 : 8, d_out, out_stride, n_in, p->n_streams,
+                           sizeof(float), &go);
+    if (rc != SFE_OK || !go) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = refuse_misaligned(who, "cf32 8 B, u8 (I,Q) pairs 2 B, float32 4 B", {in, out})) != SFE_OK ||
-        (rc = refuse_overlap(who, in, {out})) != SFE_OK)
-        return rc;
     SFE_ON_DEVICE(p->device);
     const bool fm = p->mode == SFE_POLAR_FM;
     if (fm && stream_is_capturing(s)) p->captured = true;

@@ -120,28 +120,14 @@ int sfe_dsp_psd_process_stream(sfe_psd_t h, const void *d_in, size_t n_in, size_
         set_error("psd_process_stream: n_in = %zu is not a multiple of hop = %d", n_in, p->H);
         return SFE_EINVAL;
     }
-    int rc = refuse_2_31(who, n_in);
-    if (rc != SFE_OK) return rc;
-    if (n_in == 0) return SFE_OK;
+    static const StreamNouns nouns{"n_rows * n_fft = ", "cf32 8 B, u8 (I,Q) pairs 2 B, float32 rows 4 B", true, true};
     const size_t q = n_in / p->H, j0 = (size_t)(p->seg % (unsigned long long)p->A), rows = (j0 + q) / p->A;
-    rc = refuse_null(who, {d_in, d_out});
-    if (rc != SFE_OK) return rc;
-    if (out_stride < rows * p->N) {
-        set_error("psd_process_stream: out_stride %zu < n_rows * n_fft = %zu", out_stride, rows * p->N);
-        return SFE_ERANGE;
-    }
-    if (p->n_streams > 1 && in_stride < n_in) {
-        set_error("psd_process_stream: in_stride %zu < n_in %zu with %d streams", in_stride, n_in, p->n_streams);
-        return SFE_EINVAL;
-    }
-    const size_t isz = p->in_u8 ? 2 : 8;
-    const size_t in_b = ((size_t)(p->n_streams - 1) * in_stride + n_in) * isz;
-    const size_t out_b = rows ? ((size_t)(p->n_streams - 1) * out_stride + rows * p->N) * sizeof(float) : 0;
-    const Span in{d_in, in_b, isz}, out{d_out, out_b, sizeof(float)};
+    bool go;
+    int rc = check_streams(who, nouns, d_in, n_in, in_stride, p->n_streams, p->in_u8 ? 2 : 8, d_out, out_stride, rows * p->N, p->n_streams,
+                           sizeof(float), &go);
+    if (rc != SFE_OK || !go) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = refuse_misaligned(who, "cf32 8 B, u8 (I,Q) pairs 2 B, float32 rows 4 B", {in, out})) != SFE_OK ||
-        (rc = refuse_overlap(who, in, {out})) != SFE_OK || (rc = refuse_capture(who, "segment", s)) != SFE_OK)
-        return rc;
+    if ((rc = refuse_capture(who, "segment", s)) != SFE_OK) return rc;
     SFE_ON_DEVICE(p->device);
     // the one allocation a call may make: the scratch of chunk sums grows when a larger call than any before arrives
     // (none when a chunk is a whole row, A <= 2: the rows are written without it)

@@ -1,7 +1,9 @@
 // call_checks.h -- the argument checks a process_stream makes before it launches anything: what stands between a caller's
 // bad stride and an out-of-bounds kernel.  The pieces every block uses (Span, span_bytes, refuse_*), the rules of the burst
-// chain's windows and frames (check_starts, check_place), and one check per family of the chain: rows (vit, reed, ldpc),
-// windows (burst, ofdm), frames (mod, ofdmmod).  HOST CODE ONLY, plain C++17 and no HIP: block.h includes it, and
+// chain's windows and frames (check_starts, check_place), one check per family of blocks: rows (vit, reed, ldpc), windows
+// (burst, ofdm), frames (mod, ofdmmod), streams (chan, ddc, psd, iir, polar, beam, cov), and the byte ranges of the four entry
+// points that fit no family (combine, corr, mvdr, eig).  Every byte range comes from span_bytes, so a stride that would wrap
+// one is refused, never multiplied out.  HOST CODE ONLY, plain C++17 and no HIP: block.h includes it, and
 // tests/host/test_call_checks.cpp compiles it alone.  `who` is the message prefix ("vit_process_stream") throughout; what
 // else differs between the blocks of a family -- their nouns -- comes in as words, never as a format.
 #pragma once
@@ -85,6 +87,12 @@ inline bool span_bytes(size_t rows_less_1, size_t stride, size_t tail, size_t el
         return false;
     *bytes = v;
     return true;
+}
+
+inline int refuse_2_62(const char *who)      // where a span_bytes failed
+{
+    set_error("%s: the strides take a byte range to 2^62", who);
+    return SFE_EINVAL;
 }
 
 // ---- windows cut from a stream (burst, ofdm; their plans too).  o = start_base + b start_step + idx, and what a kernel
@@ -253,6 +261,96 @@ inline int check_frames(const char *who, const FrameNouns &nn, int F, bool tx10,
     if ((rc = refuse_misaligned(who, nn.elements, {in, ou})) != SFE_OK || (rc = refuse_overlap(who, in, {ou})) != SFE_OK) return rc;
     *go = true;
     return SFE_OK;
+}
+
+// ---- streams: a block that reads in_rows rows of n_in samples (isz bytes each) and writes out_rows rows of `need` elements
+// (osz bytes each): chan, ddc, psd, iir, polar, beam, cov, after the block's own granule rule and ahead of its capture refusal.
+// The SFE_ERANGE sentence reads "out_stride S < <need>N".  A call that writes nothing (psd and cov complete no row: need = 0)
+// has an output of no bytes.
+struct StreamNouns {
+    const char *need;                   // "n_out ", "n_rows * n_fft = "
+    const char *elements;               // refuse_misaligned's
+    bool below_2_31;                    // the kernels index n_in in 32 bits (not chan's)
+    bool name_streams;                  // the rows are the handle's streams: one row's in_stride is not looked at, and the sentence names them
+};
+inline int check_streams(const char *who, const StreamNouns &nn, const void *d_in, size_t n_in, size_t in_stride, size_t in_rows, size_t isz,
+                         const void *d_out, size_t out_stride, size_t need, size_t out_rows, size_t osz, bool *go)
+{
+    *go = false;
+    int rc = nn.below_2_31 ? refuse_2_31(who, n_in) : SFE_OK;
+    if (rc != SFE_OK || n_in == 0) return rc;
+    if ((rc = refuse_null(who, {d_in, d_out})) != SFE_OK) return rc;
+    if (out_stride < need) {
+        set_error("%s: out_stride %zu < %s%zu", who, out_stride, nn.need, need);
+        return SFE_ERANGE;
+    }
+    if (in_stride < n_in && (in_rows > 1 || !nn.name_streams)) {
+        if (nn.name_streams) set_error("%s: in_stride %zu < n_in %zu with %d streams", who, in_stride, n_in, (int)in_rows);
+        else set_error("%s: in_stride %zu < n_in %zu", who, in_stride, n_in);
+        return SFE_EINVAL;
+    }
+    size_t in_b = 0, out_b = 0;
+    if (!span_bytes(in_rows - 1, in_stride, n_in, isz, &in_b) || (need && !span_bytes(out_rows - 1, out_stride, need, osz, &out_b)))
+        return refuse_2_62(who);
+    const Span in{d_in, in_b, isz}, out{d_out, out_b, osz};
+    if ((rc = refuse_misaligned(who, nn.elements, {in, out})) != SFE_OK || (rc = refuse_overlap(who, in, {out})) != SFE_OK) return rc;
+    *go = true;
+    return SFE_OK;
+}
+
+// ==== the byte ranges of the entry points that keep their own sequence of rules, because their shapes fit no family:
+// combine (its TX10 and 2^31 rules sit between the shared ones), corr (two peak outputs and an optional metric), mvdr and eig
+// (several optional outputs under one compound SFE_ERANGE sentence).  Each is false where a range is not below 2^62: the
+// caller then returns refuse_2_62.
+
+// combine: n_streams * M rows of n_in cf32 in; per stream a row of n_out cf32, or of n_out / 2 TX10 groups of 5 bytes, out
+inline bool combine_ranges(size_t n_streams, size_t M, bool tx10, const void *d_in, size_t n_in, size_t in_stride, const void *d_out,
+                           size_t n_out, size_t out_stride, Span *in, Span *out)
+{
+    size_t in_b, out_b;
+    if (!span_bytes(n_streams * M - 1, in_stride, n_in, 8, &in_b) ||
+        !(tx10 ? span_bytes(n_streams - 1, out_stride / 2, n_out / 2, 5, &out_b) : span_bytes(n_streams - 1, out_stride, n_out, 8, &out_b)))
+        return false;
+    *in = Span{d_in, in_b, 8};
+    *out = Span{d_out, out_b, tx10 ? (size_t)1 : (size_t)8};
+    return true;
+}
+
+// corr: n_streams rows of n_in samples in; n_streams * K rows of `blocks` peak values and indices, and of n_in metric
+// values where d_metric is given, out
+struct CorrRanges {
+    Span in, val, idx, met;
+};
+inline bool corr_ranges(size_t n_streams, size_t K, size_t isz, const void *d_in, size_t n_in, size_t in_stride, const void *d_val,
+                        const void *d_idx, size_t blocks, size_t peak_stride, const void *d_metric, size_t metric_stride, CorrRanges *r)
+{
+    const size_t rows = n_streams * K;
+    size_t in_b, peak_b, met_b = 0;
+    if (!span_bytes(n_streams - 1, in_stride, n_in, isz, &in_b) || !span_bytes(rows - 1, peak_stride, blocks, 4, &peak_b) ||
+        (d_metric && !span_bytes(rows - 1, metric_stride, n_in, 4, &met_b)))
+        return false;
+    *r = CorrRanges{Span{d_in, in_b, isz}, Span{d_val, peak_b, 4}, Span{d_idx, peak_b, 4}, Span{d_metric, met_b, 4}};
+    return true;
+}
+
+// mvdr and eig: M bands of n_rows Gram matrices of `gram` floats in; per row one record of `row` 4-byte words for each output,
+// a null one having no bytes.  out[i] is the i-th of outs.
+struct RowOut {
+    const void *p;
+    size_t stride, row;
+};
+inline bool solver_ranges(size_t M, const void *d_gram, size_t n_rows, size_t in_stride, size_t gram, std::initializer_list<RowOut> outs,
+                          Span *in, Span *out)
+{
+    size_t b;
+    if (!span_bytes(M - 1, in_stride, n_rows * gram, 4, &b)) return false;
+    *in = Span{d_gram, b, 4};
+    for (const RowOut &o : outs) {
+        b = 0;
+        if (o.p && !span_bytes(n_rows - 1, o.stride, o.row, 4, &b)) return false;
+        *out++ = Span{o.p, b, 4};
+    }
+    return true;
 }
 
 }  // namespace sfe

@@ -2,7 +2,9 @@
 // (tests/test_call_checks_host.py): the return code and the whole message of every check, at the boundary values.  The
 // header is the only library file included -- it needs no HIP -- and set_error is this program's own.  Pointers are made-up
 // integers: nothing is dereferenced.  Every expected message is written out here as the entry point worded it before the
-// checks were shared; none is composed from the code under test.
+// checks were shared; none is composed from the code under test.  The refusal of a stride that would wrap a byte range
+// is asserted here for every entry point that gained it (the streams family; combine, corr, mvdr and eig through the
+// functions that compute their ranges): on a GPU a build that forgot it would launch the call.
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -591,6 +593,210 @@ static void test_frames_all()
     CHECK(check_frames("mod_process_stream", mod.nn, 8, true, false, P(0x10000), 5, 5, 1, 2, 1, 9, P(0x20000), 40, &go), SFE_OK, "");
 }
 
+// ---- streams.  The words each block hands over, and what its entry point said before the checks were shared.
+struct StreamCase {
+    const char *who;
+    StreamNouns nn;
+    size_t n_in, need, in_rows, out_rows, isz, osz;
+    const char *n_2_31, *null, *short_out, *short_in, *short_in_one, *wrapped, *misaligned, *in_out;   // short_in_one "": one row's stride is not looked at
+};
+
+static void test_streams(const StreamCase &c)
+{
+    const size_t n = c.n_in, in_b = c.in_rows * n * c.isz, out_b = c.out_rows * c.need * c.osz;
+    const uintptr_t IN = 0x100000, OUT = 0x200000;
+    bool go;
+    auto call = [&](uintptr_t in, size_t n_in, size_t is, size_t in_rows, uintptr_t out, size_t os, size_t need) {
+        go = true;
+        return check_streams(c.who, c.nn, P(in), n_in, is, in_rows, c.isz, P(out), os, need, c.out_rows, c.osz, &go);
+    };
+    CHECK(call(IN, n, n, c.in_rows, OUT, c.need, c.need), SFE_OK, "");
+    TRUE(go);
+    // step 2 ahead of step 3
+    CHECK(call(0, 0, 0, c.in_rows, 0, 0, 0), SFE_OK, "");
+    TRUE(!go);
+    // step 1, ahead of step 3; below the bound the next rule speaks
+    if (c.nn.below_2_31) {
+        CHECK(call(0, T31, T31, c.in_rows, 0, T31, T31), SFE_EINVAL, c.n_2_31);
+        TRUE(!go);
+    } else {
+        CHECK(call(IN, T31, T31, c.in_rows, IN + (uintptr_t)T31 * 64, T31 / 4, T31 / 4), SFE_OK, "");
+        TRUE(go);
+    }
+    CHECK(call(0, T31 - 1, T31, c.in_rows, OUT, T31, T31), SFE_EINVAL, c.null);
+    // step 3 ahead of step 4
+    CHECK(call(0, n, n, c.in_rows, OUT, c.need - 1, c.need), SFE_EINVAL, c.null);
+    CHECK(call(IN, n, n, c.in_rows, 0, c.need - 1, c.need), SFE_EINVAL, c.null);
+    TRUE(!go);
+    // step 4 ahead of step 5
+    CHECK(call(IN, n, n - 1, c.in_rows, OUT, c.need - 1, c.need), SFE_ERANGE, c.short_out);
+    TRUE(!go);
+    // step 5 ahead of step 6
+    CHECK(call(IN, n, n - 1, c.in_rows, OUT, T62, c.need), SFE_EINVAL, c.short_in);
+    if (c.short_in_one[0]) {
+        CHECK(call(IN, n, 0, 1, OUT, c.need, c.need), SFE_EINVAL, c.short_in_one);
+    } else {
+        CHECK(call(IN, n, 0, 1, OUT, c.need, c.need), SFE_OK, "");
+        CHECK(call(IN, n, T62, 1, OUT, c.need, c.need), SFE_OK, "");                 // one row: the stride moves nothing
+        TRUE(go);
+    }
+    // step 6 ahead of step 7: the input's range, then the output's, at 2^62 bytes and at the last element below
+    CHECK(call(IN + 1, n, T62 / c.isz - n, 2, OUT, c.need, c.need), SFE_EINVAL, c.wrapped);
+    TRUE(!go);
+    CHECK(call(IN, n, T62 / c.isz - n - 1, 2, IN - out_b, c.need, c.need), SFE_OK, "");
+    TRUE(go);
+    CHECK(call(IN, n, T62, 2, OUT, c.need, c.need), SFE_EINVAL, c.wrapped);         // * elem overflows
+    CHECK(call(IN, n, SIZE_MAX, 2, OUT, c.need, c.need), SFE_EINVAL, c.wrapped);    // + tail overflows
+    if (c.in_rows > 2) CHECK(call(IN, n, T63, c.in_rows, OUT, c.need, c.need), SFE_EINVAL, c.wrapped);      // rows * stride overflows
+    if (c.out_rows > 1) {
+        CHECK(call(IN + 1, n, n, c.in_rows, OUT, T62 / c.osz / (c.out_rows - 1), c.need), SFE_EINVAL, c.wrapped);
+        CHECK(call(IN, n, n, c.in_rows, OUT, SIZE_MAX, c.need), SFE_EINVAL, c.wrapped);
+        if (c.out_rows > 2) CHECK(call(IN, n, n, c.in_rows, OUT, T63, c.need), SFE_EINVAL, c.wrapped);
+    } else {
+        CHECK(call(IN, n, n, c.in_rows, OUT, T62, c.need), SFE_OK, "");
+    }
+    // step 7 ahead of step 8
+    CHECK(call(IN + c.isz / 2, n, n, c.in_rows, IN, c.need, c.need), SFE_EINVAL, c.misaligned);
+    CHECK(call(IN, n, n, c.in_rows, OUT + c.osz / 2, c.need, c.need), SFE_EINVAL, c.misaligned);
+    if (c.isz == 2) CHECK(call(IN + 2, n, n, c.in_rows, OUT, c.need, c.need), SFE_OK, "");
+    // step 8, to the element, and the strides count
+    CHECK(call(IN, n, n, c.in_rows, IN + in_b - c.osz, c.need, c.need), SFE_EINVAL, c.in_out);
+    TRUE(!go);
+    CHECK(call(IN, n, n, c.in_rows, IN + in_b, c.need, c.need), SFE_OK, "");
+    CHECK(call(IN, n, n, c.in_rows, IN - out_b, c.need, c.need), SFE_OK, "");
+    CHECK(call(IN, n, n, c.in_rows, IN - out_b + c.osz, c.need, c.need), SFE_EINVAL, c.in_out);
+    CHECK(call(IN, n, 2 * n, c.in_rows, IN + in_b, c.need, c.need), SFE_EINVAL, c.in_out);
+    CHECK(call(IN, n, 2 * n, c.in_rows, IN + (2 * c.in_rows - 1) * n * c.isz, c.need, c.need), SFE_OK, "");
+    CHECK(call(IN, n, n, c.in_rows, IN - (2 * c.out_rows - 1) * c.need * c.osz + c.osz, 2 * c.need, c.need), SFE_EINVAL, c.in_out);
+    CHECK(call(IN, n, n, c.in_rows, IN - (2 * c.out_rows - 1) * c.need * c.osz, 2 * c.need, c.need), SFE_OK, "");
+    TRUE(go);
+}
+
+static const char CF_U8[] = "cf32 8 B, u8 (I,Q) pairs 2 B", CF_U8_F[] = "cf32 8 B, u8 (I,Q) pairs 2 B, float32 4 B";
+static const char CF_U8_ROWS[] = "cf32 8 B, u8 (I,Q) pairs 2 B, float32 rows 4 B", DDC_EL[] = "cf32 8 B, real float 4 B, u8 (I,Q) pairs 2 B";
+
+static void test_streams_all()
+{
+    // chan: M 4, D 4, two streams; the only block without the 2^31 rule
+    const StreamCase chan{"chan_process_stream", StreamNouns{"n_out ", CF_U8, false, true}, 64, 16, 2, 8, 8, 8, "", "chan_process_stream: null buffer",
+                          "chan_process_stream: out_stride 15 < n_out 16", "chan_process_stream: in_stride 63 < n_in 64 with 2 streams", "",
+                          "chan_process_stream: the strides take a byte range to 2^62",
+                          "chan_process_stream: buffers must be aligned to their element (cf32 8 B, u8 (I,Q) pairs 2 B)",
+                          "chan_process_stream: input and output ranges overlap (in-place operation is not supported)"};
+    // ddc: D 3, K 2, two streams
+    const StreamCase ddc{"ddc_process_stream", StreamNouns{"n_out ", DDC_EL, true, true}, 192, 64, 2, 4, 8, 8,
+                         "ddc_process_stream: n_in = 2147483648 must be below 2^31 per call", "ddc_process_stream: null buffer",
+                         "ddc_process_stream: out_stride 63 < n_out 64", "ddc_process_stream: in_stride 191 < n_in 192 with 2 streams", "",
+                         "ddc_process_stream: the strides take a byte range to 2^62",
+                         "ddc_process_stream: buffers must be aligned to their element (cf32 8 B, real float 4 B, u8 (I,Q) pairs 2 B)",
+                         "ddc_process_stream: input and output ranges overlap (in-place operation is not supported)"};
+    // psd: N 256, hop 128, n_avg 2, eight segments: four rows
+    const StreamCase psd{"psd_process_stream", StreamNouns{"n_rows * n_fft = ", CF_U8_ROWS, true, true}, 1024, 1024, 2, 2, 8, 4,
+                         "psd_process_stream: n_in = 2147483648 must be below 2^31 per call", "psd_process_stream: null buffer",
+                         "psd_process_stream: out_stride 1023 < n_rows * n_fft = 1024", "psd_process_stream: in_stride 1023 < n_in 1024 with 2 streams", "",
+                         "psd_process_stream: the strides take a byte range to 2^62",
+                         "psd_process_stream: buffers must be aligned to their element (cf32 8 B, u8 (I,Q) pairs 2 B, float32 rows 4 B)",
+                         "psd_process_stream: input and output ranges overlap (in-place operation is not supported)"};
+    const StreamCase iir{"iir_process_stream", StreamNouns{"n_in = ", CF_U8_F, true, true}, 64, 64, 2, 2, 8, 8,
+                         "iir_process_stream: n_in = 2147483648 must be below 2^31 per call", "iir_process_stream: null buffer",
+                         "iir_process_stream: out_stride 63 < n_in = 64", "iir_process_stream: in_stride 63 < n_in 64 with 2 streams", "",
+                         "iir_process_stream: the strides take a byte range to 2^62",
+                         "iir_process_stream: buffers must be aligned to their element (cf32 8 B, u8 (I,Q) pairs 2 B, float32 4 B)",
+                         "iir_process_stream: input and output ranges overlap (in-place operation is not supported)"};
+    const StreamCase polar{"polar_process_stream", StreamNouns{"n_in = ", CF_U8_F, true, true}, 64, 64, 2, 2, 8, 4,
+                           "polar_process_stream: n_in = 2147483648 must be below 2^31 per call", "polar_process_stream: null buffer",
+                           "polar_process_stream: out_stride 63 < n_in = 64", "polar_process_stream: in_stride 63 < n_in 64 with 2 streams", "",
+                           "polar_process_stream: the strides take a byte range to 2^62",
+                           "polar_process_stream: buffers must be aligned to their element (cf32 8 B, u8 (I,Q) pairs 2 B, float32 4 B)",
+                           "polar_process_stream: input and output ranges overlap (in-place operation is not supported)"};
+    // beam: S 2, B 3, M 2
+    const StreamCase beam{"beam_process_stream", StreamNouns{"n_in = ", CF_U8, true, false}, 64, 64, 4, 6, 8, 8,
+                          "beam_process_stream: n_in = 2147483648 must be below 2^31 per call", "beam_process_stream: null buffer",
+                          "beam_process_stream: out_stride 63 < n_in = 64", "beam_process_stream: in_stride 63 < n_in 64",
+                          "beam_process_stream: in_stride 0 < n_in 64", "beam_process_stream: the strides take a byte range to 2^62",
+                          "beam_process_stream: buffers must be aligned to their element (cf32 8 B, u8 (I,Q) pairs 2 B)",
+                          "beam_process_stream: input and output ranges overlap (in-place operation is not supported)"};
+    // cov: S 2, M 1, two rows of (2 S)^2 floats
+    const StreamCase cov{"cov_process_stream", StreamNouns{"n_rows * (2 n_in_streams)^2 = ", CF_U8_ROWS, true, false}, 64, 32, 2, 1, 8, 4,
+                         "cov_process_stream: n_in = 2147483648 must be below 2^31 per call", "cov_process_stream: null buffer",
+                         "cov_process_stream: out_stride 31 < n_rows * (2 n_in_streams)^2 = 32", "cov_process_stream: in_stride 63 < n_in 64",
+                         "cov_process_stream: in_stride 0 < n_in 64", "cov_process_stream: the strides take a byte range to 2^62",
+                         "cov_process_stream: buffers must be aligned to their element (cf32 8 B, u8 (I,Q) pairs 2 B, float32 rows 4 B)",
+                         "cov_process_stream: input and output ranges overlap (in-place operation is not supported)"};
+    for (const StreamCase *c : {&chan, &ddc, &psd, &iir, &polar, &beam, &cov}) {
+        test_streams(*c);
+        StreamCase u8 = *c;
+        u8.isz = 2;
+        test_streams(u8);
+    }
+    StreamCase real = ddc;          // the real inputs of ddc and iir, and iir's real output
+    real.isz = 4;
+    test_streams(real);
+    real = iir, real.isz = real.osz = 4;
+    test_streams(real);
+    // one byte below 2^62, with a byte for an element
+    bool go = false;
+    CHECK(check_streams(chan.who, chan.nn, P(0x100000), 64, T62 - 65, 2, 1, P(0x80000), 16, 16, 8, 8, &go), SFE_OK, "");
+    TRUE(go);
+    CHECK(check_streams(chan.who, chan.nn, P(0x100000), 64, T62 - 64, 2, 1, P(0x80000), 16, 16, 8, 8, &go), SFE_EINVAL, chan.wrapped);
+    TRUE(!go);
+    // psd and cov: a call that completes no row writes nothing, so an output inside the input overlaps nothing
+    for (const StreamCase *c : {&psd, &cov}) {
+        go = false;
+        CHECK(check_streams(c->who, c->nn, P(0x100000), c->n_in, c->n_in, c->in_rows, 8, P(0x100010), 0, 0, c->out_rows, 4, &go), SFE_OK, "");
+        TRUE(go);
+        CHECK(check_streams(c->who, c->nn, P(0x100000), c->n_in, c->n_in, c->in_rows, 8, P(0x100010), 4, 4, c->out_rows, 4, &go), SFE_EINVAL, c->in_out);
+        CHECK(check_streams(c->who, c->nn, P(0x100000), c->n_in, c->n_in, c->in_rows, 8, P(0x100012), 0, 0, c->out_rows, 4, &go), SFE_EINVAL,
+              c->misaligned);           // its alignment is still looked at
+    }
+}
+
+// ---- the four entry points that keep their own sequence: their byte ranges, at ordinary and at wrapping strides
+static void test_own_ranges()
+{
+    CHECK(refuse_2_62("mvdr_process_stream"), SFE_EINVAL, "mvdr_process_stream: the strides take a byte range to 2^62");
+    CHECK(refuse_2_62("occ_process_stream"), SFE_EINVAL, "occ_process_stream: the strides take a byte range to 2^62");
+    const void *I = P(0x100000), *O = P(0x200000);
+    Span in{}, out{};
+    // combine: n_streams * M rows of n_in cf32 in; a row of n_out cf32, or of n_out / 2 groups of 5 bytes, per stream out
+    TRUE(combine_ranges(2, 4, false, I, 64, 100, O, 256, 300, &in, &out));
+    TRUE(in.p == I && in.bytes == (7 * 100 + 64) * 8 && in.align == 8 && out.p == O && out.bytes == (300 + 256) * 8 && out.align == 8);
+    TRUE(combine_ranges(2, 4, true, I, 64, 100, O, 256, 300, &in, &out));
+    TRUE(in.bytes == (7 * 100 + 64) * 8 && out.bytes == (150 + 128) * 5 && out.align == 1);
+    TRUE(combine_ranges(1, 4, false, I, 64, 64, O, 256, T62, &in, &out) && out.bytes == 256 * 8);     // one stream: its stride moves nothing
+    TRUE(!combine_ranges(1, 2, false, I, 64, T62 / 2, O, 256, 300, &in, &out));         // (2^61 + n) * 8 would come out as 8 n
+    TRUE(!combine_ranges(2, 4, false, I, 64, T62 / 8, O, 256, 300, &in, &out));
+    TRUE(!combine_ranges(2, 4, false, I, 64, T62, O, 256, 300, &in, &out));             // rows * stride
+    TRUE(!combine_ranges(1, 4, false, I, 64, SIZE_MAX / 3, O, 256, 300, &in, &out));    // + tail
+    TRUE(!combine_ranges(2, 4, false, I, 64, 100, O, 256, T62 / 8, &in, &out));
+    TRUE(!combine_ranges(2, 4, true, I, 64, 100, O, 256, T62, &in, &out));
+    TRUE(combine_ranges(2, 4, false, I, 64, 100, O, 256, T62 / 8 - 257, &in, &out) && out.bytes == T62 - 8);
+    // corr: n_streams rows in; n_streams * K rows of peaks, twice, and of the optional metric
+    CorrRanges c;
+    TRUE(corr_ranges(2, 3, 8, I, 1000, 1100, O, P(0x300000), 4, 5, P(0x400000), 1200, &c));
+    TRUE(c.in.bytes == 2100 * 8 && c.in.align == 8 && c.val.bytes == (5 * 5 + 4) * 4 && c.idx.bytes == c.val.bytes && c.val.p == O &&
+         c.idx.p == P(0x300000) && c.met.bytes == (5 * 1200 + 1000) * 4 && c.met.align == 4);
+    TRUE(corr_ranges(2, 3, 2, I, 1000, 1100, O, P(0x300000), 4, 5, nullptr, T62, &c) && c.in.bytes == 2100 * 2 && c.met.bytes == 0);   // no metric: its stride is not looked at
+    TRUE(!corr_ranges(2, 3, 8, I, 1000, T62 / 8, O, P(0x300000), 4, 5, P(0x400000), 1200, &c));
+    TRUE(!corr_ranges(2, 3, 2, I, 1000, T62, O, P(0x300000), 4, 5, P(0x400000), 1200, &c));
+    TRUE(!corr_ranges(2, 3, 8, I, 1000, 1100, O, P(0x300000), 4, T62 / 4, P(0x400000), 1200, &c));
+    TRUE(!corr_ranges(2, 3, 8, I, 1000, 1100, O, P(0x300000), 4, T62, P(0x400000), 1200, &c));
+    TRUE(!corr_ranges(2, 3, 8, I, 1000, 1100, O, P(0x300000), 4, 5, P(0x400000), T62 / 4, &c));
+    TRUE(!corr_ranges(2, 3, 8, I, 1000, 1100, O, P(0x300000), 4, 5, P(0x400000), SIZE_MAX / 5, &c));
+    TRUE(corr_ranges(1, 1, 8, I, 1000, T62, O, P(0x300000), 4, T62, P(0x400000), T62, &c) && c.in.bytes == 8000);      // one row each
+    // mvdr and eig: M bands of n_rows grams in; per row one record of each output, the optional ones null
+    Span o[4];
+    TRUE(solver_ranges(3, I, 5, 100, 16, {RowOut{O, 50, 40}, RowOut{nullptr, T62, 7}, RowOut{P(0x300000), 9, 3}}, &in, o));
+    TRUE(in.bytes == (2 * 100 + 5 * 16) * 4 && in.align == 4 && o[0].p == O && o[0].bytes == (4 * 50 + 40) * 4 && o[1].p == nullptr &&
+         o[1].bytes == 0 && o[2].bytes == (4 * 9 + 3) * 4 && o[2].align == 4);
+    TRUE(!solver_ranges(3, I, 5, T62 / 4, 16, {RowOut{O, 50, 40}}, &in, o));
+    TRUE(!solver_ranges(3, I, 5, T62, 16, {RowOut{O, 50, 40}}, &in, o));
+    TRUE(!solver_ranges(3, I, 5, 100, 16, {RowOut{O, T62 / 4, 40}}, &in, o));
+    TRUE(!solver_ranges(3, I, 5, 100, 16, {RowOut{O, 50, 40}, RowOut{P(0x300000), T62 / 16, 7}}, &in, o));
+    TRUE(!solver_ranges(3, I, 5, 100, 16, {RowOut{O, 50, 40}, RowOut{P(0x300000), 9, 3}, RowOut{P(0x400000), 9, 3}, RowOut{P(0x500000), T63, 3}}, &in, o));
+    TRUE(solver_ranges(1, I, 1, T62, 16, {RowOut{O, T62, 40}}, &in, o) && in.bytes == 64 && o[0].bytes == 160);       // one band, one row
+}
+
 int main()
 {
     test_span_bytes();
@@ -601,6 +807,8 @@ int main()
     test_rows_all();
     test_windows_all();
     test_frames_all();
+    test_streams_all();
+    test_own_ranges();
     if (g_fails) {
         printf("call checks: %d of %d FAILED\n", g_fails, g_checks);
         return 1;

@@ -1,8 +1,9 @@
 """The argument checks every process_stream makes before it launches anything (csrc/call_checks.h), on the host: the header
 is plain C++ and includes nothing from HIP, so a stand-alone program (tests/host/test_call_checks.cpp) compiles it alone
 with the host compiler under -fsanitize=address,undefined and asserts the return code and the whole message of every
-rule at its boundary values -- span_bytes, the overlap tests, the starts and placement rules, and the one check of each
-family of the burst chain (rows, windows, frames) with every entry point's own words.  Then the build's bookkeeping.
+rule at its boundary values -- span_bytes, the overlap tests, the starts and placement rules, the one check of each
+family (rows, windows, frames, streams) with every entry point's own words, and the byte ranges of combine, corr, mvdr
+and eig at strides that would wrap them.  Then the build's bookkeeping.
 No GPU."""
 import os
 import subprocess
@@ -33,9 +34,13 @@ def test_the_header_is_host_code_without_hip():
 
 
 def test_each_rule_is_written_once():
-    """The starts rule, the placement rule and the pairwise test of the outputs each have one definition in csrc."""
+    """The starts rule, the placement rule, the pairwise test of the outputs and the refusal of a wrapped byte range each have
+    one definition in csrc; the in_stride sentence that names the streams has two there, windows and streams, and a third in
+    corr, which keeps its own sequence of rules."""
     import glob
-    src = {p: open(p).read() for p in glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hip"))}
-    for words in ("must stay within +-(2^63 - 2^33)", "frames must not overlap", "the output ranges overlap one another"):
-        assert [os.path.basename(p) for p, t in src.items() if words in t] == ["call_checks.h"], words
-        assert src[os.path.join(CSRC, "call_checks.h")].count(words) == 1, words
+    src = {os.path.basename(p): open(p).read() for p in glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hip"))}
+    for words, count, also in (("must stay within +-(2^63 - 2^33)", 1, []), ("frames must not overlap", 1, []),
+                               ("the output ranges overlap one another", 1, []), ("the strides take a byte range to 2^62", 1, []),
+                               ("in_stride %zu < n_in %zu with %d streams", 2, ["api_corr.hip"])):
+        assert sorted(p for p, t in src.items() if words in t) == sorted(["call_checks.h"] + also), words
+        assert src["call_checks.h"].count(words) == count and all(src[p].count(words) == 1 for p in also), words

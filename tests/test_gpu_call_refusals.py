@@ -1,6 +1,11 @@
-"""The call checks the burst chain's blocks share (csrc/call_checks.h) through the real C ABI, one table row per entry
-point -- vit, reed and ldpc (rows), burst and ofdm (windows), mod and ofdmmod (frames) -- at the shapes of the blocks' own
-test_refusals_launch_nothing.  Each shared rule refuses one bad call with its return code and the WHOLE message: the
+"""The call checks the blocks share (csrc/call_checks.h) through the real C ABI, one table row per entry point -- vit, reed
+and ldpc (rows), burst and ofdm (windows), mod and ofdmmod (frames) at the shapes of the blocks' own
+test_refusals_launch_nothing; chan, ddc, psd, iir, polar, beam and cov (streams) and the four that keep their own
+sequence (combine, corr, mvdr, eig) at the smallest shapes they accept, their good call held to a fresh handle's bits.
+A stride that would wrap a byte range is sent only to the entry points that have always refused it (the burst chain,
+polar); for the others the rule is asserted on the host, through the functions the entry points call
+(tests/host/test_call_checks.cpp), since a build without it would launch the call.
+Each shared rule refuses one bad call with its return code and the WHOLE message: the
 prefix and the block's nouns are wired per entry point, and only the whole text tells a swap.  The outputs are poisoned
 before the refused calls and bit-identical after them; then one good call gives the block's plan bit for bit (burst and
 ofdm, whose plans are float64 twins held to a tolerance by their own tests: a fresh handle through the wrapper).  The
@@ -319,7 +324,250 @@ def _ofdmmod(api, L):
     return e
 
 
-ENTRIES = {"vit_process_stream": _vit, "reed_encode_stream": _reed_enc, "reed_process_stream": _reed, "ldpc_encode_stream": _ldpc_enc,
+STR = ("pi", "n_in", "in_stride", "po", "ostride")
+WRAPPED = "%s: the strides take a byte range to 2^62"
+BELOW_2_31 = "%s: n_in = %d must be below 2^31 per call"
+
+
+def _n31(granule):
+    """The smallest multiple of a block's granule that is not below 2^31."""
+    return -(-T31 // granule) * granule
+
+
+def _fresh(api, L, e, new, sizes):
+    """The good call of entry e on a new handle, into poisoned outputs of its own: their words."""
+    f = new()
+    fresh = [_poisoned(api, n) for n in sizes]
+    k = C.c_size_t(0)
+    assert e.call(k, hh=f._h, **dict(zip(e.out_names, (d.ptr for d in fresh)))) == L.SFE_OK and k.value == e.counted
+    api.sync()
+    return [_words(d) for d in fresh]
+
+
+def _check_fresh(api, L, e, new, written):
+    """e.check: every output holds what a fresh handle writes, bit for bit -- `written` words each, and poison behind."""
+    def check():
+        want = _fresh(api, L, e, new, [w + 64 for w in written])
+        for d, w, n in zip(e.outs, want, written):
+            got = _words(d)
+            assert np.array_equal(got, w) and (got[:n] != POISON).all() and (got[n:] == POISON).all()
+    e.check = check
+
+
+def _streams(api, L, who, new, x, n, in_rows, need, need_noun, out_rows, osz, elements, counted, named, n31, extra):
+    """A member of the streams family: in_rows rows of n cf32 samples (x: the float32 words as uploaded), one good call with
+    in_stride = n and out_stride = need.  new(): a handle of this shape; n31: the n_in of the 2^31 rule (None: the block
+    has no such rule, and the call would be launched); extra: the block's own rows."""
+    h = new()
+    d_in = api.DeviceArray.from_numpy(np.concatenate([x, np.zeros(64, F32)]))
+    in_b, out_b = in_rows * n * 8, out_rows * need * osz
+    d_out = _poisoned(api, out_b // 4 + 64)
+    g = dict(pi=d_in.ptr, n_in=n, in_stride=n, po=d_out.ptr, ostride=need)
+    al = ALIGN % (who, elements)
+    bad = [(dict(pi=None), -1, NULL % who), (dict(po=None), -1, NULL % who),
+           (dict(ostride=need - 1), -6, "%s: out_stride %d < %s%d" % (who, need - 1, need_noun, need)),
+           (dict(in_stride=n - 1), -1, "%s: in_stride %d < n_in %d" % (who, n - 1, n) + (" with %d streams" % in_rows if named else "")),
+           (dict(pi=d_in.ptr + 4), -1, al), (dict(po=d_out.ptr + osz // 2), -1, al),
+           (dict(po=d_in.ptr + in_b - osz), -1, IN_OUT % who), (dict(pi=d_out.ptr + 8 * ((out_b - 1) // 8)), -1, IN_OUT % who)] + extra
+    if n31:
+        bad.append((dict(n_in=n31, in_stride=n31, ostride=n31), -1, BELOW_2_31 % (who, n31)))
+    e = Entry(L, who, h, STR, g, [d_out], bad, counted, None, keep=(d_in,))
+    e.out_names = ("po",)
+    _check_fresh(api, L, e, new, [out_b // 4])
+    return e
+
+
+CF_U8 = "cf32 8 B, u8 (I,Q) pairs 2 B"
+
+
+def _chan(api, L):
+    """M 4, D 4 (and a handle of D 2), 64 outputs, two streams.  chan has no 2^31 rule: such a call is never sent."""
+    M, n, who = 4, 256, "chan_process_stream"
+    taps = synth.lowpass_taps(4 * M, 1.0 / M)
+    half = api.Chan(taps, M, 2, n_streams=2)
+    e = _streams(api, L, who, lambda: api.Chan(taps, M, 4, n_streams=2), synth.synth_cf32(2 * n), n, 2, 64, "n_out ", 2 * M, 8, CF_U8, 64, True, None,
+                 [(dict(n_in=n + 2, in_stride=n + 2), -1, "chan_process_stream: n_in = 258 is not a multiple of decim = 4"),
+                  (dict(hh=half._h, n_in=n + 1, in_stride=n + 1), -1, "chan_process_stream: n_in = 257 is not a multiple of decim = 2"),
+                  (dict(hh=half._h), -6, "chan_process_stream: out_stride 64 < n_out 128")])
+    e.keep += (half,)
+    return e
+
+
+def _ddc(api, L):
+    """D 3, K 2, 64 outputs, two streams.  2^31 is no multiple of 3: the rule is sent the next multiple."""
+    D, n, who = 3, 192, "ddc_process_stream"
+    taps = synth.lowpass_taps(8 * D, 0.5 / D)
+    return _streams(api, L, who, lambda: api.Ddc(taps, D, [0.125, -0.3], n_streams=2), synth.synth_cf32(2 * n), n, 2, 64, "n_out ", 4, 8,
+                    "cf32 8 B, real float 4 B, u8 (I,Q) pairs 2 B", 64, True, _n31(D),
+                    [(dict(n_in=n + 1, in_stride=n + 1), -1, "ddc_process_stream: n_in = 193 is not a multiple of decim = 3")])
+
+
+def _psd(api, L):
+    """N 256, hop 128, n_avg 2, eight segments: four rows, two streams."""
+    N, hop, n, who = 256, 128, 1024, "psd_process_stream"
+    w = np.hanning(N).astype(F32)
+    return _streams(api, L, who, lambda: api.Psd(w, hop, 2, n_streams=2), synth.synth_cf32(2 * n), n, 2, 4 * N, "n_rows * n_fft = ", 2, 4,
+                    CF_U8 + ", float32 rows 4 B", 4, True, _n31(hop),
+                    [(dict(n_in=n + 1, in_stride=n + 1), -1, "psd_process_stream: n_in = 1025 is not a multiple of hop = 128")])
+
+
+def _iir(api, L):
+    """One block, two streams."""
+    sos = synth.iir_dc_blocker(0.995)
+    n, who = api.iir_plan(sos)[0], "iir_process_stream"
+    return _streams(api, L, who, lambda: api.Iir(sos, n_streams=2), synth.synth_cf32(2 * n), n, 2, n, "n_in = ", 2, 8, CF_U8 + ", float32 4 B", n, True,
+                    _n31(n), [(dict(n_in=n + 1, in_stride=n + 1, ostride=n + 1), -1,
+                               "iir_process_stream: n_in = %d is not a multiple of the block = %d" % (n + 1, n))])
+
+
+def _polar(api, L):
+    """FM, two streams of 64 samples.  polar refused a wrapped byte range before the family was shared, so it is sent both."""
+    n, who = 64, "polar_process_stream"
+    return _streams(api, L, who, lambda: api.Polar(L.POLAR_FM, 0.5, n_streams=2), synth.synth_cf32(2 * n), n, 2, n, "n_in = ", 2, 4,
+                    CF_U8 + ", float32 4 B", n, True, T31,
+                    [(dict(in_stride=1 << 61), -1, WRAPPED % who), (dict(ostride=1 << 62), -1, WRAPPED % who)])
+
+
+def _beam(api, L):
+    """S 2, B 2, M 1, 64 samples."""
+    n, who = 64, "beam_process_stream"
+    W = np.array([[1.0, 0.5j], [0.25 - 0.5j, -1.0]], np.complex64)
+    return _streams(api, L, who, lambda: api.Beam(W), synth.synth_cf32(2 * n), n, 2, n, "n_in = ", 2, 8, CF_U8, n, False, T31, [])
+
+
+def _cov(api, L):
+    """S 2, M 1, n_avg = the chunk, two rows of (2 S)^2 floats."""
+    who = "cov_process_stream"
+    T = api.cov_plan(2, 1, 64)[0]
+    n = 2 * T
+    return _streams(api, L, who, lambda: api.Cov(2, 1, T), synth.synth_cf32(2 * n), n, 2, 32, "n_rows * (2 n_in_streams)^2 = ", 1, 4,
+                    CF_U8 + ", float32 rows 4 B", 2, False, _n31(T),
+                    [(dict(n_in=n + 1, in_stride=n + 1), -1, "cov_process_stream: n_in = %d is not a multiple of the chunk = %d" % (n + 1, T))])
+
+
+def _combine(api, L):
+    """M 4, D 4, two streams of 64 instants: its own sequence, with the TX10 and 2^31 rules between the shared ones."""
+    M, D, n, who = 4, 4, 64, "combine_process_stream"
+    taps = synth.lowpass_taps(4 * M, 1.0 / M)
+    new = lambda: api.Combiner(taps, M, D, n_streams=2)
+    h, ht = new(), new()
+    ht.set_output_format(L.FMT_TX10)
+    no, in_b, out_b = n * D, 2 * M * n * 8, 2 * n * D * 8
+    d_in = api.DeviceArray.from_numpy(np.concatenate([synth.synth_cf32(2 * M * n), np.zeros(64, F32)]))
+    d_out = _poisoned(api, out_b // 4 + 64)
+    g = dict(pi=d_in.ptr, n_in=n, in_stride=n, po=d_out.ptr, ostride=no)
+    al = ALIGN % (who, "cf32 8 B")
+    bad = [(dict(pi=None), -1, NULL % who), (dict(po=None), -1, NULL % who),
+           (dict(ostride=no - 1), -6, "combine_process_stream: out_stride 255 < n_out 256"),
+           (dict(in_stride=n - 1), -1, "combine_process_stream: in_stride 63 < n_in 64"),
+           (dict(hh=ht._h, ostride=no + 1), -1, "combine_process_stream: out_stride 257 must be even with SFE_FMT_TX10 (whole 5-byte groups per stream)"),
+           (dict(pi=d_in.ptr + 4), -1, al), (dict(po=d_out.ptr + 4), -1, al),
+           (dict(n_in=1 << 29, in_stride=1 << 29, ostride=T31), -1,
+            "combine_process_stream: a stream's input (4 x 536870912) or output (2147483648) reaches 2^31 samples"),
+           (dict(po=d_in.ptr + in_b - 8), -1, IN_OUT % who), (dict(pi=d_out.ptr + out_b - 8), -1, IN_OUT % who)]
+    e = Entry(L, who, h, STR, g, [d_out], bad, no, None, keep=(d_in, ht))
+    e.out_names = ("po",)
+    _check_fresh(api, L, e, new, [out_b // 4])
+    return e
+
+
+def _corr(api, L):
+    """Templates of 257 samples, a block of two transform advances, two blocks, two streams: two peak outputs, one metric."""
+    K, B, blocks, who = 2, 2 * 3840, 2, "corr_process_stream"
+    n, rows = blocks * B, 2 * K
+    t = np.stack([synth.synth_cf32(257, ch=100 + k).view(np.complex64) for k in range(K)])
+    t = (np.where(t.real >= 0, 1.0, -1.0) + 1j * np.where(t.imag >= 0, 1.0, -1.0)).astype(np.complex64)
+    new = lambda: api.Corr(t, B, 1e-6, n_streams=2)
+    d_in = api.DeviceArray.from_numpy(np.concatenate([synth.synth_cf32(2 * n), np.zeros(64, F32)]))
+    written = [rows * blocks, rows * blocks, rows * n]
+    d_val, d_idx, d_met = (_poisoned(api, w + 64) for w in written)
+    g = dict(pi=d_in.ptr, n_in=n, in_stride=n, pv=d_val.ptr, px=d_idx.ptr, pstride=blocks, pm=d_met.ptr, mstride=n)
+    al = ALIGN % (who, "cf32 8 B, u8 (I,Q) pairs 2 B, outputs 4 B")
+    n31 = _n31(B)
+    bad = [(dict(n_in=n + 1, in_stride=n + 1), -1, "corr_process_stream: n_in = 15361 is not a multiple of block = 7680"),
+           (dict(n_in=n31, in_stride=n31, pstride=n31 // B, mstride=n31), -1, BELOW_2_31 % (who, n31)),
+           (dict(pi=None), -1, NULL % who), (dict(pv=None), -1, NULL % who), (dict(px=None), -1, NULL % who),
+           (dict(pstride=blocks - 1), -6, "corr_process_stream: peak_stride 1 < n_blocks = 2"),
+           (dict(mstride=n - 1), -6, "corr_process_stream: metric_stride 15359 < n_in = 15360"),
+           (dict(in_stride=n - 1), -1, "corr_process_stream: in_stride 15359 < n_in 15360 with 2 streams"),
+           (dict(pi=d_in.ptr + 4), -1, al), (dict(pv=d_val.ptr + 2), -1, al), (dict(px=d_idx.ptr + 1), -1, al), (dict(pm=d_met.ptr + 3), -1, al),
+           (dict(pv=d_in.ptr + 8 * 2 * n - 4), -1, IN_OUT % who), (dict(px=d_in.ptr), -1, IN_OUT % who), (dict(pm=d_in.ptr + 8), -1, IN_OUT % who),
+           (dict(pi=d_met.ptr + 8 * ((4 * rows * n - 1) // 8)), -1, IN_OUT % who),
+           (dict(px=d_val.ptr + 4 * (rows * blocks - 1)), -1, OUT_OUT % who), (dict(pm=d_idx.ptr), -1, OUT_OUT % who),
+           (dict(pv=d_met.ptr + 4 * (rows * n - 1)), -1, OUT_OUT % who)]
+    e = Entry(L, who, new(), ("pi", "n_in", "in_stride", "pv", "px", "pstride", "pm", "mstride"), g, [d_val, d_idx, d_met], bad, blocks, None,
+              keep=(d_in,))
+    e.out_names = ("pv", "px", "pm")
+    _check_fresh(api, L, e, new, written)
+    return e
+
+
+def _grams(rows, n2, seed):
+    """rows symmetric positive definite matrices of order n2, float32, as one band's input."""
+    a = np.random.default_rng(seed).standard_normal((rows, n2, 3 * n2))
+    return (a @ a.transpose(0, 2, 1) / (3 * n2) + np.eye(n2)).astype(F32).ravel()
+
+
+STEER = np.array([[1.0, 1.0j]], np.complex64)       # S 2, B 1, one band
+
+
+def _mvdr(api, L):
+    """S 2, B 1, M 1, two rows: several optional outputs under one compound SFE_ERANGE sentence."""
+    who, rows, gram, mat = "mvdr_process_stream", 2, 16, 8
+    new = lambda: api.Mvdr(STEER, False, 1e-3)
+    d_g = api.DeviceArray.from_numpy(np.concatenate([_grams(rows, 4, 41), np.zeros(64, F32)]))
+    written = [rows * mat, rows, rows]
+    d_R, d_p, d_s = (_poisoned(api, w + 64) for w in written)
+    g = dict(pg=d_g.ptr, n_rows=rows, in_stride=rows * gram, pR=d_R.ptr, ostride=mat, pp=d_p.ptr, pstride=1, ps=d_s.ptr, sstride=1)
+    al = ALIGN % (who, "float32 and int32 4 B")
+    short = ("mvdr_process_stream: out_stride %d < n_bands * 4 n_beams n_in = 8, power_stride %d < n_bands * n_beams = 1 or "
+             "status_stride %d < n_bands = 1")
+    bad = [(dict(n_rows=1 << 27, in_stride=T31), -1, "mvdr_process_stream: n_rows = 134217728 must be below 2^31 / (2 n_in)^2 = 134217728 per call"),
+           (dict(pg=None), -1, NULL % who), (dict(pR=None), -1, NULL % who),
+           (dict(ostride=mat - 1), -6, short % (7, 1, 1)), (dict(pstride=0), -6, short % (8, 0, 1)), (dict(sstride=0), -6, short % (8, 1, 0)),
+           (dict(in_stride=rows * gram - 1), -1, "mvdr_process_stream: in_stride 31 < n_rows * (2 n_in)^2 = 32"),
+           (dict(pg=d_g.ptr + 2), -1, al), (dict(pR=d_R.ptr + 2), -1, al), (dict(pp=d_p.ptr + 1), -1, al), (dict(ps=d_s.ptr + 3), -1, al),
+           (dict(pR=d_g.ptr + 4 * (rows * gram - 1)), -1, IN_OUT % who), (dict(pp=d_g.ptr), -1, IN_OUT % who), (dict(ps=d_g.ptr + 4), -1, IN_OUT % who),
+           (dict(pg=d_R.ptr + 4 * (rows * mat - 1)), -1, IN_OUT % who)]
+    e = Entry(L, who, new(), ("pg", "n_rows", "in_stride", "pR", "ostride", "pp", "pstride", "ps", "sstride"), g, [d_R, d_p, d_s], bad, rows, None,
+              keep=(d_g,))
+    e.out_names = ("pR", "pp", "ps")
+    _check_fresh(api, L, e, new, written)
+    return e
+
+
+def _eig(api, L):
+    """S 2, B 1, M 1, one eigen-beam, two rows."""
+    who, rows, gram, n2, mat = "eig_process_stream", 2, 16, 4, 8
+    new = lambda: api.Eig(STEER, False, 2, 1)
+    d_g = api.DeviceArray.from_numpy(np.concatenate([_grams(rows, 4, 42), np.zeros(64, F32)]))
+    written = [rows * n2, rows, rows * mat, rows]
+    d_v, d_n, d_e, d_s = (_poisoned(api, w + 64) for w in written)
+    g = dict(pg=d_g.ptr, n_rows=rows, in_stride=rows * gram, pv=d_v.ptr, vstride=n2, pn=d_n.ptr, nstride=1, pe=d_e.ptr, estride=mat, ps=d_s.ptr,
+             sstride=1)
+    al = ALIGN % (who, "float32 and int32 4 B")
+    short = ("eig_process_stream: values_stride %d < n_bands * 2 n_in = 4, null_stride %d < n_bands * n_beams = 1, "
+             "vectors_stride %d < n_bands * 4 n_vec n_in = 8 or status_stride %d < n_bands = 1")
+    bad = [(dict(n_rows=1 << 27, in_stride=T31), -1, "eig_process_stream: n_rows = 134217728 must be below 2^31 / (2 n_in)^2 = 134217728 per call"),
+           (dict(pg=None), -1, NULL % who), (dict(pv=None), -1, NULL % who),
+           (dict(vstride=n2 - 1), -6, short % (3, 1, 8, 1)), (dict(nstride=0), -6, short % (4, 0, 8, 1)),
+           (dict(estride=mat - 1), -6, short % (4, 1, 7, 1)), (dict(sstride=0), -6, short % (4, 1, 8, 0)),
+           (dict(in_stride=rows * gram - 1), -1, "eig_process_stream: in_stride 31 < n_rows * (2 n_in)^2 = 32"),
+           (dict(pg=d_g.ptr + 2), -1, al), (dict(pv=d_v.ptr + 1), -1, al), (dict(pn=d_n.ptr + 2), -1, al), (dict(pe=d_e.ptr + 3), -1, al),
+           (dict(ps=d_s.ptr + 3), -1, al),
+           (dict(pv=d_g.ptr + 4 * (rows * gram - 1)), -1, IN_OUT % who), (dict(pn=d_g.ptr), -1, IN_OUT % who), (dict(pe=d_g.ptr + 4 * 8), -1, IN_OUT % who),
+           (dict(ps=d_g.ptr + 4), -1, IN_OUT % who), (dict(pg=d_e.ptr + 4 * (rows * mat - 1)), -1, IN_OUT % who)]
+    order = ("pg", "n_rows", "in_stride", "pv", "vstride", "pn", "nstride", "pe", "estride", "ps", "sstride")
+    e = Entry(L, who, new(), order, g, [d_v, d_n, d_e, d_s], bad, rows, None, keep=(d_g,))
+    e.out_names = ("pv", "pn", "pe", "ps")
+    _check_fresh(api, L, e, new, written)
+    return e
+
+
+ENTRIES = {"chan_process_stream": _chan, "ddc_process_stream": _ddc, "psd_process_stream": _psd, "iir_process_stream": _iir,
+           "polar_process_stream": _polar, "beam_process_stream": _beam, "cov_process_stream": _cov, "combine_process_stream": _combine,
+           "corr_process_stream": _corr, "mvdr_process_stream": _mvdr, "eig_process_stream": _eig,
+           "vit_process_stream": _vit, "reed_encode_stream": _reed_enc, "reed_process_stream": _reed, "ldpc_encode_stream": _ldpc_enc,
            "ldpc_process_stream": _ldpc, "burst_process_stream": _burst, "ofdm_process_stream": _ofdm, "mod_process_stream": _mod,
            "ofdmmod_process_stream": _ofdmmod}
 
