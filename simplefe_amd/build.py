@@ -40,7 +40,7 @@ TICKET_SOURCES = ("fir_fft.hip", "poly_fft.hip")
 # not part of the kernel-source hash
 HOST_SOURCES = ("api.hip", "api_plans.hip", "api_fir.hip", "api_rs.hip", "api_pipe.hip", "api_chan.hip", "api_combine.hip", "api_ddc.hip",
                 "api_psd.hip", "api_corr.hip", "api_iir.hip", "api_beam.hip", "api_cov.hip", "api_mvdr.hip", "api_eig.hip", "api_burst.hip", "api_vit.hip", "api_mod.hip", "api_polar.hip", "api_occ.hip", "api_reed.hip", "api_ldpc.hip", "api_ofdm.hip", "api_ofdmmod.hip", "group.hip", "host.h", "block.h",
-                "call_checks.h", "beam_view.h", "vit_code.h", "rs_plan.h")
+                "call_checks.h", "beam_view.h", "vit_code.h", "rs_plan.h", "fir_plan.h")
 
 
 def sources(diag=False):

@@ -1,5 +1,7 @@
-// api_fir.hip -- the FIR handle behind sfe_fir_t (blkconv, libdsp/blkconv.cxx:34-122): spectrum tables and tap partitions,
-// the data-movement variants, carried state, and the sfe_dsp_fir_* entry points.  Host code only.
+// api_fir.hip -- the FIR handle behind sfe_fir_t (blkconv, libdsp/blkconv.cxx:34-122): the upload of the spectrum tables,
+// the data-movement variants, a bulk call, the host round trips, and the sfe_dsp_fir_* entry points.  What a handle works
+// out before it uploads or launches -- tap partitions, the tables' arithmetic -- is fir_plan.h's; the checks of a call's
+// buffers are call_checks.h's; the history epilogue and load_history are block.h's.  Host code only.
 #include "host.h"
 
 namespace sfe {
@@ -8,113 +10,14 @@ namespace sfe {
 
 Fir *as_fir(void *h) { return as_handle<Fir>(h, "FIR"); }
 
-// the tables of the 4096-point kernel for `parts` partitions at overlap `ovl`; the rest of the shape is the handle's
-static int fir_build_tables(const Fir *f, const float *taps, int parts, int ovl, FirTables &t)
+// the tables of the 4096-point kernel (fir_plan.h) on the device
+int FirTables::upload(const FirShape &sh, const float *taps)
 {
-    const int N = FFT_N;
-    // spectrum of each zero-padded tap partition in double precision, scaled by 1/N (blkconv.cxx:50
-    // folds the same 1/fft_len into its multiply), permuted to the kernel's F3 thread order:
-    // thread t (k1 = t&15, k2 = t>>4), register k0 -> bin k2 + 16 k1 + 256 k0.
-    // Partition p holds taps [p*ovl, (p+1)*ovl) (a single partition: all n_taps <= ovl+1 of them).
-    std::vector<double> c(N / 2), sn(N / 2);
-    for (int m = 0; m < N / 2; m++) {
-        c[m] = cos(-2.0 * M_PI * m / N);
-        sn[m] = sin(-2.0 * M_PI * m / N);
-    }
-    // in-place radix-2 decimation-in-time FFT in double precision (forward sign): table construction
-    // only, so that a filter of many partitions does not cost N * n_taps trigonometric multiplies
-    auto fft = [&](std::vector<double> &re, std::vector<double> &im) {
-        for (int i = 1, j = 0; i < N; i++) {
-            int bit = N >> 1;
-            for (; j & bit; bit >>= 1) j ^= bit;
-            j ^= bit;
-            if (i < j) {
-                std::swap(re[i], re[j]);
-                std::swap(im[i], im[j]);
-            }
-        }
-        for (int len = 2; len <= N; len <<= 1) {
-            const int half = len >> 1, step = N / len;
-            for (int base = 0; base < N; base += len)
-                for (int k = 0; k < half; k++) {
-                    const double wr = c[k * step], wi = sn[k * step];
-                    const int a = base + k, b = a + half;
-                    const double xr = re[b] * wr - im[b] * wi, xi = re[b] * wi + im[b] * wr;
-                    re[b] = re[a] - xr;
-                    im[b] = im[a] - xi;
-                    re[a] += xr;
-                    im[a] += xi;
-                }
-        }
-    };
-    // one set of spectra per tap vector: one for all channels, or (per_channel) channel by channel, [set][partition][k0][t]
-    const int n_sets = f->per_channel ? f->n_channels : 1;
-    std::vector<v2f> hs((size_t)n_sets * parts * 16 * 256), tw1(7 * 256), tw2(7 * 16);
-    std::vector<double> hr(N), hi(N);
-    for (int set = 0; set < n_sets; set++) {
-    const float *tp = taps + (size_t)set * f->n_taps * (f->taps_complex ? 2 : 1);
-    for (int p = 0; p < parts; p++) {
-        const int first = parts == 1 ? 0 : p * ovl;
-        const int count = parts == 1 ? f->n_taps : (f->n_taps - first < ovl ? f->n_taps - first : ovl);
-        for (int n = 0; n < N; n++) {
-            hr[n] = n < count ? (f->taps_complex ? tp[2 * (first + n)] : tp[first + n]) / (double)N : 0.0;
-            hi[n] = n < count && f->taps_complex ? tp[2 * (first + n) + 1] / (double)N : 0.0;
-        }
-        fft(hr, hi);
-        for (int t = 0; t < 256; t++)
-            for (int k0 = 0; k0 < 16; k0++) {
-                const int bin = (t >> 4) + 16 * (t & 15) + 256 * k0;
-                hs[(((size_t)set * parts + p) * 16 + k0) * 256 + t] = (v2f){(float)hr[bin], (float)hi[bin]};
-            }
-    }
-    }
-    // twiddle bases: row k (1..3) = W^(e k), row k+3 = W^(4 e k); the kernel forms
-    // W^(e (4a+b)) as row[a+3] * row[b]
-    for (int k = 1; k < 4; k++)
-        for (int t = 0; t < 256; t++) {
-            const double a = -2.0 * M_PI * (double)(t * k) / 4096.0;
-            tw1[k * 256 + t] = (v2f){(float)cos(a), (float)sin(a)};
-            tw1[(k + 3) * 256 + t] = (v2f){(float)cos(4.0 * a), (float)sin(4.0 * a)};
-        }
-    for (int k = 1; k < 4; k++)
-        for (int n0 = 0; n0 < 16; n0++) {
-            const double a = -2.0 * M_PI * (double)(n0 * k) / 256.0;
-            tw2[k * 16 + n0] = (v2f){(float)cos(a), (float)sin(a)};
-            tw2[(k + 3) * 16 + n0] = (v2f){(float)cos(4.0 * a), (float)sin(4.0 * a)};
-        }
-    int rc;
-    if ((rc = t.hs.upload(hs)) != SFE_OK || (rc = t.tw1.upload(tw1)) != SFE_OK || (rc = t.tw2.upload(tw2)) != SFE_OK) return rc;
-    return t.ticket.alloc_zero(FIR_TICKET_GROUPS_MAX * 128 / sizeof(unsigned));
-}
-
-// How a tap count is cut for the 4096-point kernel.  One launch with overlap hl costs ~1/(4096-hl) per
-// output sample; P launches over partitions of `ovl` taps cost P/(4096-ovl) plus the read-modify-
-// write of the output for every launch after the first (8 more bytes per sample: ~1/4 of a launch's
-// traffic).  E.g. 3841 taps: one launch advances 256 samples per transform (16x the 256-tap work);
-// two partitions of 2048 advance 2048 (2.25x).  Returns false beyond FIR_MAX_PARTS partitions.
-constexpr int FIR_MAX_PARTS = 1024;       // ~3.9 million taps; 32 KiB of spectrum per partition
-static bool fir_choose_partition(int n_taps, int *ovl, int *parts)
-{
-    const int need = n_taps > 1 ? n_taps - 1 : 1;
-    double best = 1e300;
-    *parts = 0;
-    const int hl1 = ((need + 255) / 256) * 256;
-    if (hl1 < FFT_N) {
-        best = 1.0 / (FFT_N - hl1);
-        *ovl = hl1;
-        *parts = 1;
-    }
-    for (int o = 256; o < FFT_N; o += 256) {
-        const int P = (n_taps + o - 1) / o;
-        if (P < 2 || P > FIR_MAX_PARTS) continue;
-        const double cost = (P + 0.25 * (P - 1)) / (FFT_N - o);
-        if (cost < best) {
-            best = cost;
-            *ovl = o;
-            *parts = P;
-        }
-    }
-    return *parts > 0;
+    std::vector<v2f> w1, w2;
+    fir_twiddles(w1, w2);
+    int rc = hs.upload(fir_spectra<v2f>(sh, taps));
+    if (rc == SFE_OK) rc = tw1.upload(w1);
+    return rc != SFE_OK ? rc : tw2.upload(w2);
 }
 
 // A stream that is being captured into a hipGraph: the launches recorded now will be REPLAYED with the same
@@ -162,9 +65,7 @@ static std::map<FirVarKey, int> g_fir_var_cache;
 
 static FirVarKey fir_var_key(const Fir *f, const FirFftArgs &a)
 {
-    int sc = 0;
-    for (unsigned long long v = (unsigned long long)a.nblk * f->n_channels; v > 1; v >>= 1) sc++;
-    return FirVarKey{f->device, f->n_channels, sc, f->ovl, f->per_channel};
+    return FirVarKey{f->device, f->n_channels, fir_size_class(a.nblk, f->n_channels), f->ovl, f->per_channel};
 }
 
 static bool fir_has_variants(const Fir *f, const FirFftArgs &a)
@@ -255,7 +156,7 @@ static void fir_fill_args(const Fir *f, FirFftArgs &a, const void *d_in, void *d
     a.advance = FFT_N - f->ovl;
     a.hist_len = f->hl;
     a.nblk = ((long long)n + a.advance - 1) / a.advance;
-    a.ticket = f->tab.ticket;
+    a.ticket = f->ticket;
     a.total = 0;
     a.tgroups = 0;
     a.hs_stride = f->per_channel ? (long long)f->parts * 16 * 256 : 0;
@@ -263,27 +164,6 @@ static void fir_fill_args(const Fir *f, FirFftArgs &a, const void *d_in, void *d
     a.hs = f->tab.hs;
     a.shift = 0;
     a.hist_out = nullptr;
-}
-
-// Behind a call's launches: the state the NEXT call starts from.  `fused`: the main launch already wrote
-// it into hist.next().  A handle one of whose calls sits in a hipGraph keeps its state in hist.cur()
-// for good -- the graph names that buffer -- so an eager call on such a handle copies the new state back
-// instead of flipping (CarriedPair::carry; ADVICE r3: a replay after an eager call used to read the stale buffer).
-static int fir_carry_state(Fir *f, const void *d_in, size_t n, size_t in_stride, bool fused, bool capturing, hipStream_t s)
-{
-    const int width = f->data_complex ? 2 : 1;
-    if (capturing) {
-        // in place, behind everything that read the old history: with n >= hl the kernel reads `in` only
-        f->captured = true;
-        return launch_history_update(d_in, (long long)n, (long long)in_stride, f->hist.cur(), f->hist.cur(), f->hl,
-                                     width, f->n_channels, s, f->in_u8);
-    }
-    if (!fused) {
-        int rc = launch_history_update(d_in, (long long)n, (long long)in_stride, f->hist.cur(), f->hist.next(),
-                                       f->hl, width, f->n_channels, s, f->in_u8);
-        if (rc != SFE_OK) return rc;
-    }
-    return f->hist.carry(f->captured, s);
 }
 
 int fir_run(Fir *f, const void *d_in, void *d_out, size_t n, size_t in_stride,
@@ -327,45 +207,65 @@ int fir_run(Fir *f, const void *d_in, void *d_out, size_t n, size_t in_stride,
         }
         const PolyTiledPlan *pl = get_tiled_plan(f->plans, f->h_taps, 1, f->n_taps, 1, 0, &rc);
         if (rc != SFE_OK) return rc;
+        const PolyIo io{d_in, d_out, (long long)n, (long long)in_stride, (long long)out_stride};
         if (pl) {
             PolyTiledArgs ta;
-            ta.in = d_in;
-            ta.out = d_out;
-            ta.hist = f->hist.cur();
+            fill_io(ta, f, io);
             ta.G = pl->d_G;
             ta.Gt = pl->d_Gt;
-            ta.n_in = (long long)n;
-            ta.in_stride = (long long)in_stride;
-            ta.out_stride = (long long)out_stride;
             ta.n_out = (long long)n;
-            ta.hl = f->hl;
             ta.Lp = pl->Lp;
             ta.e_max = pl->e_max;
             rc = launch_poly_tiled(*pl, ta, f->data_complex, 0, 0, f->n_channels, s);
         } else {
             PolyArgs a;
             memset(&a, 0, sizeof(a));
-            a.in = d_in;
-            a.out = d_out;
-            a.hist = f->hist.cur();
+            fill_io(a, f, io);
             a.taps = f->d_taps;
-            a.n_in = (long long)n;
-            a.in_stride = (long long)in_stride;
-            a.out_stride = (long long)out_stride;
-            a.hl = f->hl;
             a.U = 1;
             a.plen = f->n_taps;
-            a.pos0 = 0;
             a.step = 1;
             a.n_out = (long long)n;
             rc = launch_poly_int(a, f->data_complex, 0, 0, f->n_channels, s);
         }
     }
     if (rc != SFE_OK) return rc;
-    return fir_carry_state(f, d_in, n, in_stride, hist_fused, capturing, s);
+    return carry_history(f->hist, f->captured, d_in, n, in_stride, f->hl, f->data_complex ? 2 : 1, f->n_channels, f->in_u8, hist_fused, capturing, s);
 }
 
-int fir_create_impl(const float *taps, int n_taps, int taps_complex, int data_complex,
+// the checks of a bulk call's buffers (call_checks.h: channels), behind the entry point's null rule: sfe_dsp_fir_process_stream
+// and, over the same buffers, sfe_dsp_fir_calibrate
+static int fir_check_buffers(const char *who, const Fir *f, const void *d_in, const void *d_out, size_t n, size_t in_stride, size_t out_stride)
+{
+    static const ChannelNouns nouns{"channel stride smaller than n", "cf32 8 B, f32 4 B, u8 (I,Q) pairs 2 B; 10-bit output: none", true};
+    // bytes per element as the kernels address them
+    const size_t isz = f->in_u8 ? (f->data_complex ? 2 : 1) : (f->data_complex ? 8 : 4);
+    return check_channels(who, nouns, (size_t)f->n_channels, d_in, n, in_stride, isz, d_out, n, out_stride, f->out_complex ? 8 : 4, f->out_tx10 != 0);
+}
+
+// One host round trip on the handle's own stream: m samples that sit in the pinned buffer `h`, and the wait for their
+// outputs.  Zero-copy (m <= zc_max, where the kernel reads its input once: parts == 1): the kernel reads `h` and writes the
+// pinned `h_zc` itself -- one launch and one wait; else staged: copy in, launch, copy back into `h`, wait.  *res: where
+// the outputs are.
+static int fir_round_trip(Fir *f, size_t m, void *h, void *h_zc, void *d_in, void *d_out, const void **res)
+{
+    const bool zc = f->parts == 1 && h_zc && m <= f->zc_max;
+    if (!zc) SFE_HIP(hipMemcpyAsync(d_in, h, m * (f->data_complex ? 8 : 4), hipMemcpyHostToDevice, f->stream));
+    const int rc = fir_run(f, zc ? h : d_in, zc ? h_zc : d_out, m, m, m, f->stream);
+    if (rc != SFE_OK) return rc;
+    if (!zc) SFE_HIP(hipMemcpyAsync(h, d_out, m * (f->out_complex ? 8 : 4), hipMemcpyDeviceToHost, f->stream));
+    SFE_HIP(hipStreamSynchronize(f->stream));
+    *res = zc ? h_zc : h;
+    return SFE_OK;
+}
+
+// the spectra a handle's taps give for `parts` partitions at overlap `ovl`
+static FirShape fir_shape(const Fir *f, int parts, int ovl)
+{
+    return FirShape{f->n_taps, f->taps_complex, f->per_channel ? f->n_channels : 1, parts, ovl};
+}
+
+static int fir_create_impl(const float *taps, int n_taps, int taps_complex, int data_complex,
                            int n_channels, int block_hint, int device, int per_channel, sfe_fir_t *out)
 {
     if (!out) return SFE_EINVAL;
@@ -396,12 +296,13 @@ int fir_create_impl(const float *taps, int n_taps, int taps_complex, int data_co
         set_error("fir_create_per_channel: %d taps exceed %d partitions of the 4096-point kernel", n_taps, FIR_MAX_PARTS);
         return SFE_ERANGE;
     }
-    if (f->fft_ok) f->hl = f->parts * f->ovl;                       // history the slowest partition reaches back to
-    else f->hl = ((n_taps - 1 + 255) / 256) * 256;                  // beyond FIR_MAX_PARTS partitions: direct kernel only
+    f->hl = fir_history_len(n_taps);
     int rc = f->stream.create();
     if (rc != SFE_OK) return rc;
     f->h_taps_all.assign(taps, taps + (size_t)n_taps * (taps_complex ? 2 : 1) * (per_channel ? n_channels : 1));
-    if (f->fft_ok && (rc = fir_build_tables(f.get(), taps, f->parts, f->ovl, f->tab)) != SFE_OK) return rc;
+    if (f->fft_ok && ((rc = f->tab.upload(fir_shape(f.get(), f->parts, f->ovl), taps)) != SFE_OK ||
+                      (rc = f->ticket.alloc_zero(FIR_TICKET_GROUPS_MAX * 128 / sizeof(unsigned))) != SFE_OK))
+        return rc;
     if (!f->taps_complex && !f->per_channel) {
         f->h_taps.assign(taps, taps + n_taps);
         if ((rc = f->d_taps.upload(f->h_taps)) != SFE_OK) return rc;
@@ -478,21 +379,10 @@ int sfe_dsp_fir_process_block(sfe_fir_t h)
         return SFE_ESTATE;
     }
     SFE_ON_DEVICE(f->device);
-    const size_t in_b = (size_t)f->blk * (f->data_complex ? 8 : 4);
-    const size_t out_b = (size_t)f->blk * (f->out_complex ? 8 : 4);
-    if (f->parts == 1 && (size_t)f->blk <= f->zc_max) {
-        int rc = fir_run(f, f->h_buf, f->h_blk_out, (size_t)f->blk, (size_t)f->blk, (size_t)f->blk, f->stream);
-        if (rc != SFE_OK) return rc;
-        SFE_HIP(hipStreamSynchronize(f->stream));
-        memcpy(f->h_buf, f->h_blk_out, out_b);
-        return SFE_OK;
-    }
-    SFE_HIP(hipMemcpyAsync(f->d_blk_in, f->h_buf, in_b, hipMemcpyHostToDevice, f->stream));
-    int rc = fir_run(f, f->d_blk_in, f->d_blk_out, (size_t)f->blk, (size_t)f->blk, (size_t)f->blk, f->stream);
-    if (rc != SFE_OK) return rc;
-    SFE_HIP(hipMemcpyAsync(f->h_buf, f->d_blk_out, out_b, hipMemcpyDeviceToHost, f->stream));
-    SFE_HIP(hipStreamSynchronize(f->stream));
-    return SFE_OK;
+    const void *res = nullptr;
+    const int rc = fir_round_trip(f, (size_t)f->blk, f->h_buf, f->h_blk_out, f->d_blk_in, f->d_blk_out, &res);
+    if (rc == SFE_OK && res != f->h_buf) memcpy(f->h_buf, res, (size_t)f->blk * (f->out_complex ? 8 : 4));
+    return rc;
 }
 
 int sfe_dsp_fir_process_stream(sfe_fir_t h, const void *d_in, void *d_out, size_t n,
@@ -503,31 +393,8 @@ int sfe_dsp_fir_process_stream(sfe_fir_t h, const void *d_in, void *d_out, size_
         set_error("fir_process_stream: null handle or buffer");
         return SFE_EINVAL;
     }
-    if (f->n_channels > 1 && (in_stride < n || out_stride < n)) {
-        set_error("fir_process_stream: channel stride smaller than n");
-        return SFE_EINVAL;
-    }
-    // bytes per element as the kernels address them
-    const size_t isz = f->in_u8 ? (f->data_complex ? 2 : 1) : (f->data_complex ? 8 : 4);
-    const size_t osz = f->out_complex ? 8 : 4;
-    if ((reinterpret_cast<uintptr_t>(d_in) & (isz - 1)) ||
-        (reinterpret_cast<uintptr_t>(d_out) & (f->out_tx10 ? 0 : osz - 1))) {
-        set_error("fir_process_stream: buffers must be aligned to their element (cf32 8 B, f32 4 B, u8 (I,Q) pairs 2 B; 10-bit output: none)");
-        return SFE_EINVAL;
-    }
-    if (f->out_tx10 && f->n_channels > 1 && ((out_stride * (f->out_complex ? 2 : 1)) & 3)) {
-        set_error("fir_process_stream: 10-bit output packs 4 floats per group: out_stride must keep channels on group boundaries");
-        return SFE_EINVAL;
-    }
-    {
-        const size_t in_b = ((size_t)(f->n_channels - 1) * in_stride + n) * isz;
-        const size_t out_b = f->out_tx10 ? (((size_t)(f->n_channels - 1) * out_stride + n) * (f->out_complex ? 2 : 1) / 4 + 1) * 5
-                                         : ((size_t)(f->n_channels - 1) * out_stride + n) * osz;
-        if (ranges_overlap(d_in, in_b, d_out, out_b)) {
-            set_error("fir_process_stream: input and output ranges overlap (in-place operation is not supported)");
-            return SFE_EINVAL;
-        }
-    }
+    const int rc = fir_check_buffers("fir_process_stream", f, d_in, d_out, n, in_stride, out_stride);
+    if (rc != SFE_OK) return rc;
     SFE_ON_DEVICE(f->device);
     return fir_run(f, d_in, d_out, n, in_stride, out_stride, (hipStream_t)stream);
 }
@@ -563,50 +430,18 @@ int sfe_dsp_fir_process_host(sfe_fir_t h, const void *in, void *out, size_t n)
     for (size_t off = 0; off < n; off += CH) {
         const size_t m = n - off < CH ? n - off : CH;
         memcpy(f->stage.h, ip + off * in_e, m * in_e);
-        if (f->parts == 1 && f->stage.h_out && m <= f->zc_max) {          // small call: no DMA copies
-            int rc = fir_run(f, f->stage.h, f->stage.h_out, m, m, m, f->stream);
-            if (rc != SFE_OK) return rc;
-            SFE_HIP(hipStreamSynchronize(f->stream));
-            memcpy(op + off * out_e, f->stage.h_out, m * out_e);
-            continue;
-        }
-        SFE_HIP(hipMemcpyAsync(f->stage.d_in, f->stage.h, m * in_e, hipMemcpyHostToDevice, f->stream));
-        int rc = fir_run(f, f->stage.d_in, f->stage.d_out, m, m, m, f->stream);
+        const void *res = nullptr;
+        const int rc = fir_round_trip(f, m, f->stage.h, f->stage.h_out, f->stage.d_in, f->stage.d_out, &res);
         if (rc != SFE_OK) return rc;
-        SFE_HIP(hipMemcpyAsync(f->stage.h, f->stage.d_out, m * out_e, hipMemcpyDeviceToHost, f->stream));
-        SFE_HIP(hipStreamSynchronize(f->stream));
-        memcpy(op + off * out_e, f->stage.h, m * out_e);
+        memcpy(op + off * out_e, res, m * out_e);
     }
     return SFE_OK;
 }
 
-
-// Carried state from a halo: the stream is about to continue at a sample whose predecessors are
-// d_prev[0 .. n_prev) (float32, the handle's element type, per channel at `stride`) -- e.g. the
-// first call of a span when one long stream is cut across GPUs (blkconv.cxx:105-109: what the
-// reference carries in m_overlap is determined by exactly these n_taps-1 input samples).
+// carried state from a halo (block.h: load_history)
 int sfe_dsp_fir_load_history(sfe_fir_t h, const void *d_prev, size_t n_prev, size_t stride, sfe_stream_t stream)
 {
-    Fir *f = as_fir(h);
-    if (!f || (n_prev && !d_prev)) {
-        set_error("fir_load_history: null handle or buffer");
-        return SFE_EINVAL;
-    }
-    if (f->n_channels > 1 && stride < n_prev) {
-        set_error("fir_load_history: channel stride smaller than n_prev");
-        return SFE_EINVAL;
-    }
-    if (reinterpret_cast<uintptr_t>(d_prev) & (f->data_complex ? 7 : 3)) {
-        set_error("fir_load_history: buffer must be aligned to its element");
-        return SFE_EINVAL;
-    }
-    SFE_ON_DEVICE(f->device);
-    hipStream_t s = (hipStream_t)stream;
-    SFE_HIP(hipMemsetAsync(f->hist.cur(), 0, f->hist_bytes(), s));        // shorter halos: zeros in front
-    if (!n_prev) return SFE_OK;
-    int rc = launch_history_update(d_prev, (long long)n_prev, (long long)stride, f->hist.cur(), f->hist.next(), f->hl,
-                                   f->data_complex ? 2 : 1, f->n_channels, s, 0);
-    return rc != SFE_OK ? rc : f->hist.carry(f->captured, s);
+    return load_history("fir_load_history", as_fir(h), d_prev, n_prev, stride, (hipStream_t)stream);
 }
 
 int sfe_dsp_fir_set_input_format(sfe_fir_t h, int fmt)
@@ -632,8 +467,7 @@ int sfe_dsp_fir_set_input_format(sfe_fir_t h, int fmt)
 // handle is re-planned as ONE partition: new spectrum table, new (zeroed) history.  ADVICE r2.
 static int fir_replan_single(Fir *f)
 {
-    const int need = f->n_taps > 1 ? f->n_taps - 1 : 1;
-    const int hl1 = ((need + 255) / 256) * 256;
+    const int hl1 = fir_single_overlap(f->n_taps);
     if (hl1 >= FFT_N) return SFE_ESTATE;
     if (f->started || f->captured) {
         // the re-plan zeroes the carried state and frees buffers a captured graph names
@@ -645,7 +479,7 @@ static int fir_replan_single(Fir *f)
     // build the new plan beside the old one and move it in only when all of it exists: a failure leaves the handle as it was
     FirTables tab;
     CarriedPair hist;
-    int rc = fir_build_tables(f, f->h_taps_all.data(), 1, hl1, tab);
+    int rc = tab.upload(fir_shape(f, 1, hl1), f->h_taps_all.data());        // (the work counters are the handle's and stay: zero between launches)
     if (rc == SFE_OK) rc = hist.alloc_zero((size_t)f->n_channels * hl1 * (f->data_complex ? 8 : 4));
     if (rc != SFE_OK) return rc;
     f->tab = std::move(tab);        // (the old tables and history go with the locals)
@@ -718,10 +552,8 @@ int sfe_dsp_fir_calibrate(sfe_fir_t h, const void *d_in, void *d_out, size_t n, 
         set_error("fir_calibrate: null handle or buffer");
         return SFE_EINVAL;
     }
-    if (f->n_channels > 1 && (in_stride < n || out_stride < n)) {
-        set_error("fir_calibrate: channel stride smaller than n");
-        return SFE_EINVAL;
-    }
+    int rc = fir_check_buffers("fir_calibrate", f, d_in, d_out, n, in_stride, out_stride);      // it launches over them
+    if (rc != SFE_OK) return rc;
     if (!f->fft_ok || f->algo == SFE_FIR_ALGO_DIRECT) return SFE_OK;    // the direct kernel has one form
     SFE_ON_DEVICE(f->device);
     hipStream_t s = (hipStream_t)stream;
@@ -732,7 +564,7 @@ int sfe_dsp_fir_calibrate(sfe_fir_t h, const void *d_in, void *d_out, size_t n, 
     FirFftArgs a;
     fir_fill_args(f, a, d_in, d_out, n, in_stride, out_stride);      // hist_out stays null: the stream does not advance
     int best = FIR_VAR_REG;
-    int rc = fir_calibrate(f, a, s, &best);
+    rc = fir_calibrate(f, a, s, &best);
     if (rc == SFE_OK && chosen) *chosen = best;
     return rc;
 }
@@ -765,7 +597,7 @@ int sfe_dsp_fir_reset(sfe_fir_t h)
     SFE_HIP(hipDeviceSynchronize());
     const int rc = f->hist.zero();
     if (rc != SFE_OK) return rc;
-    if (f->tab.ticket) SFE_HIP(hipMemset(f->tab.ticket, 0, FIR_TICKET_GROUPS_MAX * 128));
+    if (f->ticket) SFE_HIP(hipMemset(f->ticket, 0, FIR_TICKET_GROUPS_MAX * 128));
     f->started = false;         // `captured` stays: a graph made before the reset still names hist.cur()
     return SFE_OK;
 }

@@ -25,26 +25,8 @@ static int rs_ensure_out(Rs *r, size_t n)
     return r->d_out.reserve(n * e, rs_doubled(r->d_out.cap / e, n) * e);
 }
 
-// where a call's samples lie, and the seven fields every polyphase kernel's arguments open with (common.h: Poly*Args)
-struct RsIo {
-    const void *in;
-    void *out;
-    long long n_in, in_stride, out_stride;
-};
-template <class A>
-static void fill_io(A &a, const Rs *r, const RsIo &io)
-{
-    a.in = io.in;
-    a.out = io.out;
-    a.hist = r->hist.cur();
-    a.n_in = io.n_in;
-    a.in_stride = io.in_stride;
-    a.out_stride = io.out_stride;
-    a.hl = r->hl;
-}
-
 // the generic kernels' arguments (launch_poly_int, launch_poly_sched): the caller adds the law -- pos0 / step or the schedule
-static PolyArgs rs_poly_args(const Rs *r, const RsIo &io)
+static PolyArgs rs_poly_args(const Rs *r, const PolyIo &io)
 {
     PolyArgs a;
     memset(&a, 0, sizeof(a));
@@ -211,15 +193,14 @@ int sfe_dsp_rs_process(sfe_rs_t h, const float *in, int n_in, float *out, int ou
     if (n > 0) {
         SFE_HIP(hipMemcpyAsync(sc.pos.d, sc.pos.h, (size_t)n * sizeof(long long), hipMemcpyHostToDevice, r->stream));
         SFE_HIP(hipMemcpyAsync(sc.mu.d, sc.mu.h, (size_t)n * sizeof(float), hipMemcpyHostToDevice, r->stream));
-        PolyArgs a = rs_poly_args(r, RsIo{r->d_in, r->d_out->p, n_in, n_in, n});
+        PolyArgs a = rs_poly_args(r, PolyIo{r->d_in, r->d_out->p, n_in, n_in, n});
         a.n_out = n;
         a.sched_pos = sc.pos.d;
         a.sched_mu = sc.mu.d;
         rc = launch_poly_sched(a, r->data_complex, 1, 1, r->stream);
         if (rc != SFE_OK) return rc;
     }
-    rc = launch_history_update(r->d_in, n_in, n_in, r->hist.cur(), r->hist.next(), r->hl, r->data_complex ? 2 : 1, 1, r->stream);
-    if (rc == SFE_OK) rc = r->hist.carry(r->captured, r->stream);
+    rc = carry_history(r->hist, r->captured, r->d_in, (size_t)n_in, (size_t)n_in, r->hl, r->data_complex ? 2 : 1, 1, 0, false, false, r->stream);
     if (rc != SFE_OK) return rc;
     if (n > 0) SFE_HIP(hipMemcpyAsync(r->h_stage->p, r->d_out->p, (size_t)n * r->esz(), hipMemcpyDeviceToHost, r->stream));
     SFE_HIP(hipStreamSynchronize(r->stream));
@@ -273,7 +254,7 @@ int sfe_dsp_rs_process_stream(sfe_rs_t h, const void *d_in, size_t n_in, size_t 
 namespace {
 
 struct RsCall {                 // the call's arguments, past its checks
-    RsIo io;
+    PolyIo io;
     size_t n_in, out_cap;
     float rate, stepf;          // stepf = fl(rate * U)
     hipStream_t s;
@@ -292,24 +273,12 @@ int rs_check_call(const Rs *r, const void *d_in, size_t n_in, size_t in_stride, 
         set_error("rs_process_stream: null buffer");
         return SFE_EINVAL;
     }
-    if (r->n_channels > 1 && (in_stride < n_in || out_stride < out_cap)) {
-        // out_cap outputs per channel may be written: a smaller stride would let channels overwrite each other
-        set_error("rs_process_stream: channel stride smaller than the channel (in_stride >= n_in, out_stride >= out_cap)");
-        return SFE_EINVAL;
-    }
+    // out_cap outputs per channel may be written: a smaller stride would let channels overwrite each other
+    static const ChannelNouns nouns{"channel stride smaller than the channel (in_stride >= n_in, out_stride >= out_cap)",
+                                    "cf32 8 B, f32 4 B, u8 (I,Q) pairs 2 B", false};
     const size_t isz = r->in_u8 ? (r->data_complex ? 2 : 1) : (size_t)r->esz();
-    const size_t osz = (size_t)r->esz();
-    if ((reinterpret_cast<uintptr_t>(d_in) & (isz - 1)) || (reinterpret_cast<uintptr_t>(d_out) & (osz - 1))) {
-        set_error("rs_process_stream: buffers must be aligned to their element (cf32 8 B, f32 4 B, u8 (I,Q) pairs 2 B)");
-        return SFE_EINVAL;
-    }
-    const size_t in_b = ((size_t)(r->n_channels - 1) * in_stride + n_in) * isz;
-    const size_t out_b = ((size_t)(r->n_channels - 1) * out_stride + out_cap) * osz;
-    if (ranges_overlap(d_in, in_b, d_out, out_b)) {
-        set_error("rs_process_stream: input and output ranges overlap");
-        return SFE_EINVAL;
-    }
-    return SFE_OK;
+    return check_channels("rs_process_stream", nouns, (size_t)r->n_channels, d_in, n_in, in_stride, isz, d_out, out_cap, out_stride, (size_t)r->esz(),
+                          false);
 }
 
 // ---- integer-valued step: one of the kernels of the closed form
@@ -480,26 +449,25 @@ int rs_launch_gen(Rs *r, const RsCall &c, const RsPlan<SegChunk> &plan)
         !(r->fft_mode > 0 || r->in_u8 || (c.n_in >= ((size_t)1 << 16) && gen_pays)))
         return SFE_ESTATE;
     if (!r->gen_tried) {
-        // spectra of the U phase filters (taps[i U + j], i < plen; one zero behind so that the overlap the FIR
-        // planner picks covers plen samples, not plen - 1) through fir_build_tables: one "channel" per phase
+        // spectra of the U phase filters (taps[i U + j], i < plen) from the FIR's table builder (fir_plan.h), one tap set per
+        // phase, where the FIR planner serves a filter of plen + 1 taps -- one more, so that the overlap it picks covers plen
+        // samples, not plen - 1 -- with one launch.  That one more tap is a zero: the spectra are those of the plen taps, and
+        // h_taps_pm's rows are the sets as they lie.
         r->gen_tried = true;
-        std::vector<float> rows((size_t)r->U * (r->plen + 1), 0.0f);
-        for (int j = 0; j < r->U; j++)
-            for (int i = 0; i < r->plen; i++) rows[(size_t)j * (r->plen + 1) + i] = r->h_taps_pm[(size_t)j * r->plen + i];
-        sfe_fir_t gh = nullptr;
-        if (fir_create_impl(rows.data(), r->plen + 1, 0, 1, r->U, 0, r->device, 1, &gh) == SFE_OK) {
-            r->gen_tables.reset(static_cast<Fir *>(gh));
-            if (r->gen_tables->parts != 1) r->gen_tables.reset();
-        }
+        int ovl = 0, parts = 0;
+        FirTables tab;
+        if (fir_choose_partition(r->plen + 1, &ovl, &parts) && parts == 1 &&
+            tab.upload(FirShape{r->plen, 0, r->U, 1, ovl}, r->h_taps_pm.data()) == SFE_OK)
+            r->gen_tables = std::move(tab);
     }
-    if (!r->gen_tables) return SFE_ESTATE;
+    if (!r->gen_tables.hs) return SFE_ESTATE;
     const std::vector<SegChunk> &chunks = plan.chunks;
     PolyGenArgs ga;
     memset(&ga, 0, sizeof(ga));
     fill_io(ga, r, c.io);
-    ga.hs = r->gen_tables->tab.hs;
-    ga.tw1 = r->gen_tables->tab.tw1;
-    ga.tw2 = r->gen_tables->tab.tw2;
+    ga.hs = r->gen_tables.hs;
+    ga.tw1 = r->gen_tables.tw1;
+    ga.tw2 = r->gen_tables.tw2;
     ga.segs = r->segs->d;
     ga.chunks = r->chunks->d;
     ga.U = r->U;
@@ -620,19 +588,8 @@ static int rs_process_stream_impl(sfe_rs_t h, const void *d_in, size_t n_in, siz
     bool hist_fused = false;
     rc = int_step ? rs_run_int_step(r, c, n_out, &hist_fused) : rs_run_general(r, c, n_out);
     if (rc != SFE_OK) return rc;
-    if (c.capturing) {        // in place behind the main launch: with n_in >= hl the kernel reads `in` only; the time state did not move
-        r->captured = true;
-        return launch_history_update(d_in, (long long)n_in, (long long)in_stride, r->hist.cur(),
-                                     r->hist.cur(), r->hl, r->data_complex ? 2 : 1, r->n_channels, s, r->in_u8);
-    }
-    if (!hist_fused) {
-        rc = launch_history_update(d_in, (long long)n_in, (long long)in_stride, r->hist.cur(),
-                                   r->hist.next(), r->hl, r->data_complex ? 2 : 1, r->n_channels, s, r->in_u8);
-        if (rc != SFE_OK) return rc;
-    }
-    // a handle one of whose calls sits in a hipGraph keeps its history in hist.cur(), the buffer the graph
-    // names: eager calls copy the new history back instead of flipping (fir_carry_state has the reasoning)
-    return r->hist.carry(r->captured, s);
+    // (a captured call: the time state did not move)
+    return carry_history(r->hist, r->captured, d_in, n_in, in_stride, r->hl, r->data_complex ? 2 : 1, r->n_channels, r->in_u8, hist_fused, c.capturing, s);
 }
 
 extern "C" {
@@ -640,26 +597,7 @@ extern "C" {
 // ---- cutting one stream into spans -------------------------
 int sfe_dsp_rs_load_history(sfe_rs_t h, const void *d_prev, size_t n_prev, size_t stride, sfe_stream_t stream)
 {
-    Rs *r = as_rs(h);
-    if (!r || (n_prev && !d_prev)) {
-        set_error("rs_load_history: null handle or buffer");
-        return SFE_EINVAL;
-    }
-    if (r->n_channels > 1 && stride < n_prev) {
-        set_error("rs_load_history: channel stride smaller than n_prev");
-        return SFE_EINVAL;
-    }
-    if (reinterpret_cast<uintptr_t>(d_prev) & (size_t)(r->esz() - 1)) {
-        set_error("rs_load_history: buffer must be aligned to its element");
-        return SFE_EINVAL;
-    }
-    SFE_ON_DEVICE(r->device);
-    hipStream_t s = (hipStream_t)stream;
-    SFE_HIP(hipMemsetAsync(r->hist.cur(), 0, r->hist.bytes, s));
-    if (!n_prev) return SFE_OK;
-    int rc = launch_history_update(d_prev, (long long)n_prev, (long long)stride, r->hist.cur(), r->hist.next(), r->hl,
-                                   r->data_complex ? 2 : 1, r->n_channels, s, 0);
-    return rc != SFE_OK ? rc : r->hist.carry(r->captured, s);
+    return load_history("rs_load_history", as_rs(h), d_prev, n_prev, stride, (hipStream_t)stream);
 }
 
 int sfe_dsp_rs_get_state(sfe_rs_t h, sfe_rs_timestate *state)

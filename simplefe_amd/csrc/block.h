@@ -1,9 +1,11 @@
 // block.h -- what every handle of libsfe_dsp.so is built from: owners of its device memory, pinned host memory (Buf; the
-// grow-only GrowScratch and Grown), streams and events, the carried pair, the device scope of a create, the handle cast,
+// grow-only GrowScratch and Grown), streams and events, the carried pair (with the history epilogue and load_history of
+// the FIR and resample / decimate handles), the device scope of a create, the handle cast,
 // the table of the unit circle, the opening of every process_stream and the format setter.  The checks of a call's buffers need no HIP and live in call_checks.h, which
-// this includes: the pieces (Span, span_bytes, refuse_*), the one check each of four families of blocks -- rows
+// this includes: the pieces (Span, span_bytes, refuse_*), the one check each of five families of blocks -- rows
 // (api_vit.hip, api_reed.hip, api_ldpc.hip), windows (api_burst.hip, api_ofdm.hip), frames (api_mod.hip, api_ofdmmod.hip),
-// streams (api_chan.hip, api_ddc.hip, api_psd.hip, api_iir.hip, api_polar.hip, api_beam.hip, api_cov.hip) -- and the byte
+// streams (api_chan.hip, api_ddc.hip, api_psd.hip, api_iir.hip, api_polar.hip, api_beam.hip, api_cov.hip), channels
+// (api_fir.hip, api_rs.hip) -- and the byte
 // ranges of the four that keep their own sequence (api_combine.hip, api_corr.hip, api_mvdr.hip, api_eig.hip).  The FIR, resampler and pipe handles (host.h, api_pipe.hip) and every block's api_*.hip use it.  HOST CODE
 // ONLY; host.h includes it.  A handle's struct names its magic as `static constexpr uint32_t MAGIC` and carries `magic` and
 // `device`.
@@ -144,6 +146,50 @@ struct CarriedPair {
         return SFE_OK;
     }
 };
+
+// ---- the carried history of the FIR and resample / decimate handles: [n_channels][hl] samples of `width` floats
+// Behind a call's launches: the state the NEXT call starts from.  `fused`: the main launch already wrote it into
+// hist.next().  A captured call (`capturing`) is REPLAYED with the same arguments, so it updates the history IN PLACE,
+// behind everything that read the old one -- with n >= hl the carry-over kernel reads `in` only -- and marks the handle:
+// a handle one of whose calls sits in a hipGraph keeps its state in hist.cur() for good -- the graph names that buffer --
+// so an eager call on such a handle copies the new state back instead of flipping (CarriedPair::carry; a replay after an
+// eager call used to read the stale buffer).
+inline int carry_history(CarriedPair &hist, bool &captured, const void *d_in, size_t n, size_t in_stride, int hl, int width, int n_channels,
+                         int in_u8, bool fused, bool capturing, hipStream_t s)
+{
+    if (capturing) captured = true;
+    if (capturing || !fused) {
+        const int rc = launch_history_update(d_in, (long long)n, (long long)in_stride, hist.cur(), capturing ? hist.cur() : hist.next(), hl, width,
+                                             n_channels, s, in_u8);
+        if (rc != SFE_OK || capturing) return rc;
+    }
+    return hist.carry(captured, s);
+}
+
+// sfe_dsp_fir_load_history / sfe_dsp_rs_load_history over as_handle's result.  Carried state from a halo: the stream is
+// about to continue at a sample whose predecessors are d_prev[0 .. n_prev) (float32, the handle's element type, per
+// channel at `stride`) -- e.g. the first call of a span when one long stream is cut across GPUs (blkconv.cxx:105-109:
+// what the reference carries in m_overlap is determined by exactly these input samples).
+template <class H>
+int load_history(const char *who, H *p, const void *d_prev, size_t n_prev, size_t stride, hipStream_t s)
+{
+    if (!p || (n_prev && !d_prev)) {
+        set_error("%s: null handle or buffer", who);
+        return SFE_EINVAL;
+    }
+    if (p->n_channels > 1 && stride < n_prev) {
+        set_error("%s: channel stride smaller than n_prev", who);
+        return SFE_EINVAL;
+    }
+    int rc = refuse_misaligned(who, "cf32 8 B, f32 4 B", {Span{d_prev, 0, p->data_complex ? (size_t)8 : (size_t)4}});
+    if (rc != SFE_OK) return rc;
+    SFE_ON_DEVICE(p->device);
+    SFE_HIP(hipMemsetAsync(p->hist.cur(), 0, p->hist.bytes, s));        // shorter halos: zeros in front
+    if (!n_prev) return SFE_OK;
+    rc = launch_history_update(d_prev, (long long)n_prev, (long long)stride, p->hist.cur(), p->hist.next(), p->hl, p->data_complex ? 2 : 1,
+                               p->n_channels, s, 0);
+    return rc != SFE_OK ? rc : p->hist.carry(p->captured, s);
+}
 
 // Scratch of one call that only grows: the one allocation (and device sync) a process_stream may make, when a larger
 // call than any before arrives.  Calls already enqueued read the old one: they finish before it is freed.

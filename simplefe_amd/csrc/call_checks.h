@@ -1,8 +1,8 @@
 // call_checks.h -- the argument checks a process_stream makes before it launches anything: what stands between a caller's
 // bad stride and an out-of-bounds kernel.  The pieces every block uses (Span, span_bytes, refuse_*), the rules of the burst
 // chain's windows and frames (check_starts, check_place), one check per family of blocks: rows (vit, reed, ldpc), windows
-// (burst, ofdm), frames (mod, ofdmmod), streams (chan, ddc, psd, iir, polar, beam, cov), and the byte ranges of the four entry
-// points that fit no family (combine, corr, mvdr, eig).  Every byte range comes from span_bytes, so a stride that would wrap
+// (burst, ofdm), frames (mod, ofdmmod), streams (chan, ddc, psd, iir, polar, beam, cov), channels (fir, fir_calibrate, rs),
+// and the byte ranges of the four entry points that fit no family (combine, corr, mvdr, eig).  Every byte range comes from span_bytes, so a stride that would wrap
 // one is refused, never multiplied out.  HOST CODE ONLY, plain C++17 and no HIP: block.h includes it, and
 // tests/host/test_call_checks.cpp compiles it alone.  `who` is the message prefix ("vit_process_stream") throughout; what
 // else differs between the blocks of a family -- their nouns -- comes in as words, never as a format.
@@ -295,6 +295,42 @@ inline int check_streams(const char *who, const StreamNouns &nn, const void *d_i
     const Span in{d_in, in_b, isz}, out{d_out, out_b, osz};
     if ((rc = refuse_misaligned(who, nn.elements, {in, out})) != SFE_OK || (rc = refuse_overlap(who, in, {out})) != SFE_OK) return rc;
     *go = true;
+    return SFE_OK;
+}
+
+// ---- channels: the FIR and resample / decimate handles read n_channels rows of n elements (isz bytes each) and write
+// n_channels rows of up to `cap` elements of osz bytes (FIR: cap = n), or, tx10, of the 5-byte groups that hold 4 floats
+// each: fir_process_stream, fir_calibrate, rs_process_stream, behind the entry point's own null rule (and rs's rate rule).
+// One channel's strides are not looked at.  The stride rule's sentence is the entry point's own, whole; so is the tail of
+// the overlap sentence.
+struct ChannelNouns {
+    const char *stride;                 // "channel stride smaller than n"
+    const char *elements;               // refuse_misaligned's
+    bool in_place;                      // the overlap sentence is refuse_overlap's, "(in-place operation is not supported)" included
+};
+inline int check_channels(const char *who, const ChannelNouns &nn, size_t n_channels, const void *d_in, size_t n, size_t in_stride, size_t isz,
+                          const void *d_out, size_t cap, size_t out_stride, size_t osz, bool tx10)
+{
+    if (n_channels > 1 && (in_stride < n || out_stride < cap)) {
+        set_error("%s: %s", who, nn.stride);
+        return SFE_EINVAL;
+    }
+    size_t in_b = 0, out_b = 0;         // (tx10: out_b counts floats first)
+    if (!span_bytes(n_channels - 1, in_stride, n, isz, &in_b) || !span_bytes(n_channels - 1, out_stride, cap, tx10 ? osz / 4 : osz, &out_b))
+        return refuse_2_62(who);
+    if (tx10) out_b = (out_b / 4 + 1) * 5;
+    const Span in{d_in, in_b, isz}, out{d_out, out_b, tx10 ? (size_t)1 : osz};
+    int rc = refuse_misaligned(who, nn.elements, {in, out});
+    if (rc != SFE_OK) return rc;
+    if (tx10 && n_channels > 1 && ((out_stride * (osz / 4)) & 3)) {
+        set_error("%s: 10-bit output packs 4 floats per group: out_stride must keep channels on group boundaries", who);
+        return SFE_EINVAL;
+    }
+    if (nn.in_place) return refuse_overlap(who, in, {out});
+    if (ranges_overlap(in.p, in.bytes, out.p, out.bytes)) {
+        set_error("%s: input and output ranges overlap", who);
+        return SFE_EINVAL;
+    }
     return SFE_OK;
 }
 

@@ -2,14 +2,18 @@
 // the plan caches, and the helpers that cross files.  HOST CODE ONLY (no kernels; not part of the kernel-source hash).
 //   api.hip          errors, devices, memory, timers, the synthetic stream, the wire-format converters
 //   api_plans.hip    folding (U, step, pos0) into the polyphase kernels' tap tables and spectra
-//   api_fir.hip      the FIR handle: tables, partitions, variants, carried state, sfe_dsp_fir_*
+//   api_fir.hip      the FIR handle: upload of the tables, variants, the host round trips, sfe_dsp_fir_*
+//   fir_plan.h       what api_fir.hip works out before it uploads or launches, without HIP: the tap partitions, the single-transform
+//                    overlap, the spectrum tables and twiddle bases, the variant key's size class (included below;
+//                    tests/host/test_fir_plan.cpp); api_rs.hip builds the general-rate kernel's tables from it too
 //   api_rs.hip       the resample / decimate handle: a call's checks, kernel choice, plan upload, carried state, sfe_dsp_rs_*
 //   rs_plan.h        what api_rs.hip works out before it launches, without HIP: the integer-step closed form, the general-rate
 //                    plan and its run memo, the walks over a plan (included below; tests/host/test_rs_plan.cpp)
 //   api_pipe.hip     the pinned host pipe over either handle, sfe_dsp_*_pipe_*
 //   group.hip        channel blocks over several devices, sfe_dsp_*_group_* (over the public C ABI only)
 //   block.h          what every handle is built from: owners of device and pinned memory (grow-only ones too), streams and events,
-//                    the carried pair, create's device scope, the handle cast, process_stream's refusals (included below)
+//                    the carried pair, the history epilogue and load_history of the two handles here, create's device scope, the
+//                    handle cast, process_stream's refusals (call_checks.h) (included below)
 //   api_<block>.hip  the streaming blocks over block.h: chan, combine, ddc, psd, corr, iir, beam, cov, mvdr, eig, burst, vit, mod
 #pragma once
 #include <math.h>
@@ -31,11 +35,14 @@
 
 #include "common.h"
 #include "block.h"
+#include "fir_plan.h"
 #include "rs_plan.h"
 #include "segtile.h"
 #include "timelaw.h"
 
 namespace sfe {
+
+static_assert(FIR_PLAN_N == FFT_N, "fir_plan.h plans for the kernels' transform length");
 
 // ---- plan caches (api_plans.hip): (step, pos0) -> the plan the kernels read (common.h: raw pointers) beside the owners of
 // its N device tables; a plan without tables marks a shape that has no such kernel
@@ -57,9 +64,9 @@ const PolyMfmaPlan *get_mfma_plan(MfmaCache &cache, const std::vector<float> &ta
                                   int *rc);
 
 // ---- the FIR handle (api_fir.hip)
-struct FirTables {              // what fir_build_tables makes for one (parts, ovl): replaced as a whole by a re-plan
+struct FirTables {              // fir_plan.h's spectra and twiddle bases on the device: replaced as a whole by a re-plan
     DevBuf<v2f> hs, tw1, tw2;
-    DevBuf<unsigned> ticket;    // work counter of the persistent FFT kernel (zero between launches)
+    int upload(const FirShape &sh, const float *taps);
 };
 struct FirStage {               // sfe_dsp_fir_process_host: chunked pinned + device staging, made by its first call
     PinnedBuf<char> h, h_out;
@@ -82,6 +89,7 @@ struct Fir {
     bool fft_ok = false;
     Stream stream;              // (first of the owners: destroyed after the buffers)
     FirTables tab;
+    DevBuf<unsigned> ticket;    // work counters of the persistent FFT kernel (zero between launches)
     DevBuf<float> d_taps;       // real taps for the direct kernel
     std::vector<float> h_taps;  // host copy (direct-kernel plan)
     std::vector<float> h_taps_all;   // every tap as given at create (complex pairs / per-channel rows included): re-planning
@@ -101,8 +109,6 @@ struct Fir {
     size_t hist_bytes() const { return (size_t)n_channels * hl * (data_complex ? 8 : 4); }
 };
 Fir *as_fir(void *h);
-int fir_create_impl(const float *taps, int n_taps, int taps_complex, int data_complex, int n_channels, int block_hint, int device,
-                    int per_channel, sfe_fir_t *out);
 int fir_run(Fir *f, const void *d_in, void *d_out, size_t n, size_t in_stride, size_t out_stride, hipStream_t s);
 
 // ---- the resample / decimate handle (api_rs.hip)
@@ -122,9 +128,9 @@ struct Rs {
     MfmaCache mfma_plans;
     FftPlanCache fft_plans;
     DevBuf<unsigned> d_ticket;             // work counters of the transform-domain kernel
-    std::unique_ptr<Fir> gen_tables;       // general rate in the transform domain (poly_gen.hip): the U phases' spectra and the
-                                           // twiddle bases, built by the FIR's own table builder (one "channel" per phase)
-    bool gen_tried = false;
+    FirTables gen_tables;                  // general rate in the transform domain (poly_gen.hip): the U phases' spectra and the
+                                           // twiddle bases, from the FIR's own table builder (one tap set per phase); empty
+    bool gen_tried = false;                // where a phase is longer than one transform overlaps, or until the first such call
     CarriedPair hist;
     bool captured = false;                 // a call of this handle sits in a hipGraph that names hist.cur() (see CarriedPair::carry)
     sfe_rs_timestate ts = {0, 0.0f, 0};
@@ -156,6 +162,25 @@ struct Rs {
     int esz() const { return data_complex ? 8 : 4; }
 };
 Rs *as_rs(void *h);
+
+// where a call's samples lie, and the seven fields every polyphase kernel's arguments open with (common.h: Poly*Args);
+// H: either handle
+struct PolyIo {
+    const void *in;
+    void *out;
+    long long n_in, in_stride, out_stride;
+};
+template <class A, class H>
+void fill_io(A &a, const H *h, const PolyIo &io)
+{
+    a.in = io.in;
+    a.out = io.out;
+    a.hist = h->hist.cur();
+    a.n_in = io.n_in;
+    a.in_stride = io.in_stride;
+    a.out_stride = io.out_stride;
+    a.hl = h->hl;
+}
 
 // poly_rt_dma.hip (round 5): the runtime-shape tiled kernel for odd input steps, its tile fetched by LDS-DMA.  SFE_ESTATE: the shape or
 // the buffers are outside what it takes -- the caller runs launch_poly_tiled.  (Declared here, not in common.h: host-side plumbing.)

@@ -3,11 +3,13 @@
 // header is the only library file included -- it needs no HIP -- and set_error is this program's own.  Pointers are made-up
 // integers: nothing is dereferenced.  Every expected message is written out here as the entry point worded it before the
 // checks were shared; none is composed from the code under test.  The refusal of a stride that would wrap a byte range
-// is asserted here for every entry point that gained it (the streams family; combine, corr, mvdr and eig through the
+// is asserted here for every entry point that gained it (the streams and channels families; combine, corr, mvdr and eig through the
 // functions that compute their ranges): on a GPU a build that forgot it would launch the call.
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
+
+#include <utility>
 
 #include "../../simplefe_amd/csrc/call_checks.h"
 
@@ -751,6 +753,121 @@ static void test_streams_all()
     }
 }
 
+// ---- channels: the FIR handle's two entry points and the resampler's, behind their own null rules.  The sentences are the
+// entry points' as they read before the family was shared; the 2^62 rule is the one they gained.
+static const ChannelNouns FIR_NOUNS{"channel stride smaller than n", "cf32 8 B, f32 4 B, u8 (I,Q) pairs 2 B; 10-bit output: none", true};
+static const ChannelNouns RS_NOUNS{"channel stride smaller than the channel (in_stride >= n_in, out_stride >= out_cap)",
+                                   "cf32 8 B, f32 4 B, u8 (I,Q) pairs 2 B", false};
+struct ChannelCase {
+    const char *who;
+    const ChannelNouns *nn;
+    size_t n, cap, isz, osz;
+    const char *stride, *wrapped, *misaligned, *in_out;
+};
+
+static void test_channels(const ChannelCase &c)
+{
+    const size_t n = c.n, cap = c.cap, C3 = 3, in_b = C3 * n * c.isz, out_b = C3 * cap * c.osz;
+    const uintptr_t IN = 0x100000, OUT = 0x200000;
+    auto call = [&](size_t ch, uintptr_t in, size_t n_, size_t is, uintptr_t out, size_t cap_, size_t os) {
+        return check_channels(c.who, *c.nn, ch, P(in), n_, is, c.isz, P(out), cap_, os, c.osz, false);
+    };
+    CHECK(call(C3, IN, n, n, OUT, cap, cap), SFE_OK, "");
+    // the stride rule, for several channels only, ahead of the 2^62 rule
+    CHECK(call(C3, IN, n, n - 1, OUT, cap, T62), SFE_EINVAL, c.stride);
+    CHECK(call(C3, IN, n, T62, OUT, cap, cap - 1), SFE_EINVAL, c.stride);
+    CHECK(call(1, IN, n, 0, OUT, cap, 0), SFE_OK, "");
+    CHECK(call(1, IN, n, T62, OUT, cap, SIZE_MAX), SFE_OK, "");             // one channel: the strides move nothing
+    // the 2^62 rule, ahead of the alignment rule: each range at 2^62 bytes and at the last element below; the three ways to wrap
+    CHECK(call(2, IN + 1, n, T62 / c.isz - n, OUT, cap, cap), SFE_EINVAL, c.wrapped);
+    CHECK(call(2, IN, n, T62 / c.isz - n - 1, IN - 2 * cap * c.osz, cap, cap), SFE_OK, "");
+    CHECK(call(2, IN, n, T62, OUT, cap, cap), SFE_EINVAL, c.wrapped);                   // * elem overflows (or reaches 2^62)
+    CHECK(call(2, IN, n, SIZE_MAX, OUT, cap, cap), SFE_EINVAL, c.wrapped);              // + tail overflows
+    CHECK(call(C3, IN, n, T63, OUT, cap, cap), SFE_EINVAL, c.wrapped);                  // rows * stride overflows
+    CHECK(call(2, IN + 1, n, n, OUT, cap, T62 / c.osz - cap), SFE_EINVAL, c.wrapped);
+    CHECK(call(2, IN - 2 * n * c.isz, n, n, IN, cap, T62 / c.osz - cap - 1), SFE_OK, "");
+    CHECK(call(2, IN, n, n, OUT, cap, T62), SFE_EINVAL, c.wrapped);
+    CHECK(call(2, IN, n, n, OUT, cap, SIZE_MAX), SFE_EINVAL, c.wrapped);
+    CHECK(call(C3, IN, n, n, OUT, cap, T63), SFE_EINVAL, c.wrapped);
+    CHECK(call(1, IN, T62 / c.isz, 0, OUT, cap, 0), SFE_EINVAL, c.wrapped);             // one channel: the samples themselves
+    CHECK(call(1, IN, n, 0, OUT, T62 / c.osz, 0), SFE_EINVAL, c.wrapped);
+    CHECK(call(1, IN, T62 / c.isz - 1, 0, IN - 8 * cap, cap, 0), SFE_OK, "");
+    // the alignment rule ahead of the overlap rule
+    if (c.isz > 1) CHECK(call(C3, IN + c.isz / 2, n, n, IN, cap, cap), SFE_EINVAL, c.misaligned);
+    else CHECK(call(C3, IN + 1, n, n, OUT, cap, cap), SFE_OK, "");
+    CHECK(call(C3, IN, n, n, IN + c.osz / 2, cap, cap), SFE_EINVAL, c.misaligned);
+    if (c.isz == 2) CHECK(call(C3, IN + 2, n, n, OUT, cap, cap), SFE_OK, "");
+    // the overlap rule, to the element, and the strides count
+    CHECK(call(C3, IN, n, n, IN + ((in_b - 1) & ~(c.osz - 1)), cap, cap), SFE_EINVAL, c.in_out);
+    CHECK(call(C3, IN, n, n, IN + ((in_b + c.osz - 1) & ~(c.osz - 1)), cap, cap), SFE_OK, "");
+    CHECK(call(C3, IN, n, n, IN - out_b, cap, cap), SFE_OK, "");
+    CHECK(call(C3, IN, n, n, IN - out_b + c.osz, cap, cap), SFE_EINVAL, c.in_out);
+    CHECK(call(C3, IN, n, 2 * n, IN + 8 * ((5 * n * c.isz - 1) / 8), cap, cap), SFE_EINVAL, c.in_out);
+    CHECK(call(C3, IN, n, 2 * n, IN + 8 * ((5 * n * c.isz + 7) / 8), cap, cap), SFE_OK, "");
+    CHECK(call(C3, IN, n, n, IN - (4 * cap + cap) * c.osz + c.osz, cap, 2 * cap), SFE_EINVAL, c.in_out);
+    CHECK(call(C3, IN, n, n, IN - (4 * cap + cap) * c.osz, cap, 2 * cap), SFE_OK, "");
+}
+
+// the FIR's 10-bit output: 4 floats in 5 bytes, one group more than the floats fill; `width` floats per sample
+static void test_channels_tx10(const char *who, size_t isz, size_t width, const char *groups, const char *wrapped, const char *misaligned,
+                               const char *in_out)
+{
+    const size_t n = 1000, osz = 4 * width;
+    const uintptr_t IN = 0x100000, OUT = 0x200000;
+    auto call = [&](size_t ch, uintptr_t in, size_t is, uintptr_t out, size_t os) {
+        return check_channels(who, FIR_NOUNS, ch, P(in), n, is, isz, P(out), n, os, osz, true);
+    };
+    CHECK(call(3, IN, n, OUT + 1, n), SFE_OK, "");                      // bytes out: no alignment
+    if (isz > 1) CHECK(call(3, IN + isz / 2, n, OUT, n + 1), SFE_EINVAL, misaligned);       // ahead of the group rule
+    // channels on group boundaries: out_stride * width a multiple of 4, ahead of the overlap rule; one channel: any stride
+    CHECK(call(3, IN, n, IN, n + 1), SFE_EINVAL, groups);
+    if (width == 1) CHECK(call(3, IN, n, OUT, n + 2), SFE_EINVAL, groups);
+    else CHECK(call(3, IN, n, OUT, n + 2), SFE_OK, "");
+    CHECK(call(3, IN, n, OUT, n + 4), SFE_OK, "");
+    CHECK(call(1, IN, n, OUT, n + 1), SFE_OK, "");
+    // the range: ((channels - 1) * out_stride + n) * width floats, a group of 5 bytes for every 4 and one more
+    for (size_t ch : {(size_t)1, (size_t)3}) {
+        const size_t os = n + 24, bytes = (((ch - 1) * os + n) * width / 4 + 1) * 5;
+        if (isz == 1) {
+            CHECK(call(ch, OUT + bytes, n, OUT, os), SFE_OK, "");
+            CHECK(call(ch, OUT + bytes - 1, n, OUT, os), SFE_EINVAL, in_out);
+        }
+        CHECK(call(ch, OUT + ((bytes + 7) & ~(size_t)7), n, OUT, os), SFE_OK, "");
+        CHECK(call(ch, OUT + ((bytes - 1) & ~(size_t)7), n, OUT, os), SFE_EINVAL, in_out);
+        CHECK(call(ch, IN, n, IN + ch * n * isz, os), SFE_OK, "");
+        CHECK(call(ch, IN, n, IN + ch * n * isz - 1, os), SFE_EINVAL, in_out);
+    }
+    // the floats of the range reach 2^62
+    CHECK(call(2, IN, n, OUT, T62 / width - n), SFE_EINVAL, wrapped);
+    CHECK(call(2, OUT + 0x10000, n, OUT, T62 / width - n - 4), SFE_EINVAL, in_out);      // below it: a range that long lies over all that follows
+    CHECK(call(3, IN, n, OUT, T63), SFE_EINVAL, wrapped);
+}
+
+static void test_channels_all()
+{
+    for (const char *who : {"fir_process_stream", "fir_calibrate"}) {
+        char stride[128], wrapped[128], misaligned[192], in_out[160], groups[192];
+        snprintf(stride, sizeof stride, "%s: channel stride smaller than n", who);
+        snprintf(wrapped, sizeof wrapped, "%s: the strides take a byte range to 2^62", who);
+        snprintf(misaligned, sizeof misaligned, "%s: buffers must be aligned to their element (cf32 8 B, f32 4 B, u8 (I,Q) pairs 2 B; 10-bit output: none)",
+                 who);
+        snprintf(in_out, sizeof in_out, "%s: input and output ranges overlap (in-place operation is not supported)", who);
+        snprintf(groups, sizeof groups, "%s: 10-bit output packs 4 floats per group: out_stride must keep channels on group boundaries", who);
+        // cf32 -> cf32, f32 -> cf32 (complex taps), f32 -> f32, u8 pairs -> cf32, u8 -> f32
+        for (auto sz : {std::pair<size_t, size_t>{8, 8}, {4, 8}, {4, 4}, {2, 8}, {1, 4}})
+            test_channels(ChannelCase{who, &FIR_NOUNS, 1024, 1024, sz.first, sz.second, stride, wrapped, misaligned, in_out});
+        for (auto sz : {std::pair<size_t, size_t>{8, 2}, {4, 1}, {2, 2}, {1, 1}}) test_channels_tx10(who, sz.first, sz.second, groups, wrapped, misaligned, in_out);
+    }
+    // the resampler: out_cap outputs per channel may be written; its own, shorter overlap sentence
+    for (auto sz : {std::pair<size_t, size_t>{8, 8}, {4, 4}, {2, 8}, {1, 4}})
+        for (size_t cap : {(size_t)1024, (size_t)520, (size_t)3000})
+            test_channels(ChannelCase{"rs_process_stream", &RS_NOUNS, 1024, cap, sz.first, sz.second,
+                                      "rs_process_stream: channel stride smaller than the channel (in_stride >= n_in, out_stride >= out_cap)",
+                                      "rs_process_stream: the strides take a byte range to 2^62",
+                                      "rs_process_stream: buffers must be aligned to their element (cf32 8 B, f32 4 B, u8 (I,Q) pairs 2 B)",
+                                      "rs_process_stream: input and output ranges overlap"});
+}
+
 // ---- the four entry points that keep their own sequence: their byte ranges, at ordinary and at wrapping strides
 static void test_own_ranges()
 {
@@ -808,6 +925,7 @@ int main()
     test_windows_all();
     test_frames_all();
     test_streams_all();
+    test_channels_all();
     test_own_ranges();
     if (g_fails) {
         printf("call checks: %d of %d FAILED\n", g_fails, g_checks);

@@ -2,7 +2,7 @@
 is plain C++ and includes nothing from HIP, so a stand-alone program (tests/host/test_call_checks.cpp) compiles it alone
 with the host compiler under -fsanitize=address,undefined and asserts the return code and the whole message of every
 rule at its boundary values -- span_bytes, the overlap tests, the starts and placement rules, the one check of each
-family (rows, windows, frames, streams) with every entry point's own words, and the byte ranges of combine, corr, mvdr
+family (rows, windows, frames, streams, channels) with every entry point's own words, and the byte ranges of combine, corr, mvdr
 and eig at strides that would wrap them.  Then the build's bookkeeping.
 No GPU."""
 import os

@@ -9,7 +9,10 @@ Each shared rule refuses one bad call with its return code and the WHOLE message
 prefix and the block's nouns are wired per entry point, and only the whole text tells a swap.  The outputs are poisoned
 before the refused calls and bit-identical after them; then one good call gives the block's plan bit for bit (burst and
 ofdm, whose plans are float64 twins held to a tolerance by their own tests: a fresh handle through the wrapper).  The
-format setters that are one rule each get a row too.  Every bad call is refused on the host before any launch.  `-m gpu`."""
+format setters that are one rule each get a row too.  The FIR and the resample / decimate handles have a table of their
+own below (the channel family: fir_process_stream, fir_calibrate, rs_process_stream; and the two load_history): these gained
+the refusal of a wrapped stride, and fir_calibrate its alignment and overlap rules, together with the rows, so those are
+sent too.  Every bad call is refused on the host before any launch.  `-m gpu`."""
 import ctypes as C
 
 import numpy as np
@@ -594,6 +597,162 @@ def test_shared_rules_refuse_with_the_entry_points_words(api, L, name):
         if code == L.SFE_OK:
             assert e.call(k, **over) == L.SFE_OK, (over, lib.sfe_dsp_last_error())
     api.sync()
+
+
+# ---- the FIR and the resample / decimate handles: the channel family, and the two load_history entry points.  Their argument
+# lists differ from the blocks' (no counter, or a rate in front of it), so they have a table of their own: 2 channels of
+# n = 1024 cf32, 17 real taps; the resampler at U = 1, rate 2, blksize 4096; load_history with n_prev = 16.
+CH_N, CH_PREV = 1024, 16
+CH_ALIGN = "cf32 8 B, f32 4 B, u8 (I,Q) pairs 2 B"
+FIR_STRIDE = "%s: channel stride smaller than n"
+FIR_NULL = "%s: null handle or buffer"
+TX10_GROUPS = "%s: 10-bit output packs 4 floats per group: out_stride must keep channels on group boundaries"
+
+
+class Channels:
+    """One entry point of the two handles: new() a handle of the row's shape, call(h, **a) the entry point over it, the good
+    call's arguments, the refused calls as (overrides, return code, whole message), and run(h, d_out) what leaves the good
+    call's bits in d_out (for load_history: the good call, then a process_stream), `words` float32 words of them."""
+
+    def __init__(self, new, call, good, bad, d_out, words, run=None, keep=()):
+        self.new, self.call, self.good, self.bad, self.d_out, self.words, self.keep = new, call, good, bad, d_out, words, keep
+        self.run = run or (lambda h, d_out: call(h, **dict(good, po=d_out.ptr)))
+
+
+def _fir_rows(api, L, who, call):
+    """fir_process_stream and fir_calibrate: the same buffers, the same rules, their own prefix."""
+    n = CH_N
+    taps = synth.lowpass_taps(17, 0.2)
+    new = lambda: api.Fir(taps, data_complex=True, n_channels=2)
+    ht = new()
+    ht.set_output_format(L.FMT_TX10)
+    d_in = api.DeviceArray.from_numpy(np.concatenate([synth.synth_cf32(2 * n), np.zeros(64, F32)]))
+    d_out = _poisoned(api, 4 * n + 64)
+    good = dict(pi=d_in.ptr, po=d_out.ptr, n=n, istride=n, ostride=n)
+    al = ALIGN % (who, CH_ALIGN + "; 10-bit output: none")
+    bad = [(dict(hh=None), -1, FIR_NULL % who), (dict(pi=None), -1, FIR_NULL % who), (dict(po=None), -1, FIR_NULL % who),
+           (dict(istride=n - 1), -1, FIR_STRIDE % who), (dict(ostride=n - 1), -1, FIR_STRIDE % who),
+           (dict(istride=1 << 61), -1, WRAPPED % who), (dict(ostride=1 << 62), -1, WRAPPED % who),
+           (dict(istride=(1 << 64) - 1), -1, WRAPPED % who),
+           (dict(pi=d_in.ptr + 4), -1, al), (dict(po=d_out.ptr + 4), -1, al),
+           (dict(hh=ht._h, ostride=n + 1), -1, TX10_GROUPS % who),
+           (dict(po=d_in.ptr + 8 * (2 * n - 1)), -1, IN_OUT % who), (dict(pi=d_out.ptr + 8 * (2 * n - 1)), -1, IN_OUT % who),
+           (dict(hh=ht._h, po=d_in.ptr + 8 * 2 * n - 1), -1, IN_OUT % who)]
+    return Channels(new, call, good, bad, d_out, 4 * n, keep=(d_in, ht))
+
+
+def _fir_stream(api, L):
+    fn = L.load().sfe_dsp_fir_process_stream
+    return _fir_rows(api, L, "fir_process_stream", lambda h, hh=0, **a: fn(h._h if hh == 0 else hh, a["pi"], a["po"], a["n"], a["istride"],
+                                                                               a["ostride"], None))
+
+
+def _fir_calibrate(api, L):
+    fn = L.load().sfe_dsp_fir_calibrate
+    v = C.c_int(0)
+    e = _fir_rows(api, L, "fir_calibrate", lambda h, hh=0, **a: fn(h._h if hh == 0 else hh, a["pi"], a["po"], a["n"], a["istride"], a["ostride"],
+                                                                   None, C.byref(v)))
+    e.bad.append((dict(n=0), -1, FIR_NULL % "fir_calibrate"))
+    return e
+
+
+def _rs_stream(api, L):
+    n, cap, who = CH_N, CH_N // 2, "rs_process_stream"          # rate 2 from a fresh state: n / 2 outputs
+    taps = synth.lowpass_taps(17, 0.2)
+    new = lambda: api.Rs(taps, 1, 4096, data_complex=True, n_channels=2)
+    fn = L.load().sfe_dsp_rs_process_stream
+    k = C.c_size_t(7)
+
+    def call(h, hh=0, **a):
+        k.value = 7
+        rc = fn(h._h if hh == 0 else hh, a["pi"], a["n"], a["istride"], a["po"], a["cap"], a["ostride"], a["rate"], C.byref(k), None)
+        assert k.value == (n // 2 if rc == L.SFE_OK else 0)
+        return rc
+
+    d_in = api.DeviceArray.from_numpy(np.concatenate([synth.synth_cf32(2 * n), np.zeros(64, F32)]))
+    d_out = _poisoned(api, 4 * cap + 64)
+    good = dict(pi=d_in.ptr, po=d_out.ptr, n=n, istride=n, cap=cap, ostride=cap, rate=2.0)
+    al = ALIGN % (who, CH_ALIGN)
+    stride = "rs_process_stream: channel stride smaller than the channel (in_stride >= n_in, out_stride >= out_cap)"
+    overlap = "rs_process_stream: input and output ranges overlap"
+    bad = [(dict(rate=0.5), -1, "rs_process_stream: rate 0.5 not accepted by this mode"),
+           (dict(pi=None), -1, NULL % who), (dict(po=None), -1, NULL % who),
+           (dict(istride=n - 1), -1, stride), (dict(ostride=cap - 1), -1, stride),
+           (dict(istride=1 << 61), -1, WRAPPED % who), (dict(ostride=1 << 62), -1, WRAPPED % who), (dict(ostride=(1 << 64) - 1), -1, WRAPPED % who),
+           (dict(pi=d_in.ptr + 4), -1, al), (dict(po=d_out.ptr + 4), -1, al),
+           (dict(po=d_in.ptr + 8 * (2 * n - 1)), -1, overlap), (dict(pi=d_out.ptr + 8 * (2 * cap - 1)), -1, overlap)]
+    return Channels(new, call, good, bad, d_out, 4 * cap, keep=(d_in,))
+
+
+def _load_history(api, L, who, new, process, words):
+    """n_prev = 16 samples in front of the stream; the state they leave shows in the process_stream behind them."""
+    n = CH_N
+    fn = getattr(L.load(), "sfe_dsp_" + who)
+    d_prev = api.DeviceArray.from_numpy(np.concatenate([synth.synth_cf32(2 * CH_PREV, ch=7), np.zeros(64, F32)]))
+    d_in = api.DeviceArray.from_numpy(np.concatenate([synth.synth_cf32(2 * n), np.zeros(64, F32)]))
+    d_out = _poisoned(api, 4 * n + 64)
+    good = dict(pp=d_prev.ptr, n_prev=CH_PREV, stride=CH_PREV)
+    call = lambda h, hh=0, **a: fn(h._h if hh == 0 else hh, a["pp"], a["n_prev"], a["stride"], None)
+    bad = [(dict(hh=None), -1, FIR_NULL % who), (dict(pp=None), -1, FIR_NULL % who),
+           (dict(stride=CH_PREV - 1), -1, "%s: channel stride smaller than n_prev" % who),
+           (dict(pp=d_prev.ptr + 4), -1, ALIGN % (who, "cf32 8 B, f32 4 B"))]
+
+    def run(h, out):
+        assert call(h, **good) == L.SFE_OK
+        return process(h, d_in, out, n)
+
+    e = Channels(new, call, good, bad, d_out, words, run, keep=(d_prev, d_in))
+    e.process = lambda h, out: process(h, d_in, out, n)
+    return e
+
+
+def _fir_load_history(api, L):
+    taps = synth.lowpass_taps(17, 0.2)
+    fn = L.load().sfe_dsp_fir_process_stream
+    return _load_history(api, L, "fir_load_history", lambda: api.Fir(taps, data_complex=True, n_channels=2),
+                         lambda h, d_in, out, n: fn(h._h, d_in.ptr, out.ptr, n, n, n, None), 4 * CH_N)
+
+
+def _rs_load_history(api, L):
+    taps = synth.lowpass_taps(17, 0.2)
+    fn = L.load().sfe_dsp_rs_process_stream
+    k = C.c_size_t(0)
+    return _load_history(api, L, "rs_load_history", lambda: api.Rs(taps, 1, 4096, data_complex=True, n_channels=2),
+                         lambda h, d_in, out, n: fn(h._h, d_in.ptr, n, n, out.ptr, n // 2, n // 2, 2.0, C.byref(k), None), 2 * CH_N)
+
+
+CHANNELS = {"fir_process_stream": _fir_stream, "fir_calibrate": _fir_calibrate, "rs_process_stream": _rs_stream,
+            "fir_load_history": _fir_load_history, "rs_load_history": _rs_load_history}
+
+
+@pytest.mark.parametrize("name", list(CHANNELS))
+def test_fir_and_rs_refuse_with_the_entry_points_words(api, L, name):
+    """Each rule of the channel family (csrc/call_checks.h: check_channels) and of load_history (csrc/block.h) refuses one
+    bad call with its code and whole message, the wrapped strides and fir_calibrate's alignment and overlap rules among
+    them; nothing is written and no state moves; then the good call gives a fresh handle's bits."""
+    e = CHANNELS[name](api, L)
+    lib = L.load()
+    h = e.new()
+    d_out = e.d_out
+    for over, code, text in e.bad:
+        assert e.call(h, **dict(e.good, **over)) == code, (over, lib.sfe_dsp_last_error())
+        assert lib.sfe_dsp_last_error() == text.encode(), (over, lib.sfe_dsp_last_error())
+    api.sync()
+    assert (_words(d_out) == POISON).all(), "a refused call wrote"
+    fresh = _poisoned(api, len(_words(d_out)))
+    if name.endswith("load_history"):
+        # the refused calls left the carried state alone: the stream behind them starts from zeros, as a new handle's does
+        untouched = _poisoned(api, len(_words(d_out)))
+        assert e.process(h, untouched) == L.SFE_OK and e.process(e.new(), fresh) == L.SFE_OK
+        api.sync()
+        assert np.array_equal(_words(untouched), _words(fresh))
+        h = e.new()
+    assert e.run(h, d_out) == L.SFE_OK and e.run(e.new(), fresh) == L.SFE_OK
+    api.sync()
+    got = _words(d_out)
+    assert np.array_equal(got, _words(fresh)) and (got[:e.words] != POISON).all() and (got[e.words:] == POISON).all()
+    if name.endswith("load_history"):       # and the halo counts: not the bits of a stream that starts from zeros
+        assert not np.array_equal(got, _words(untouched))
 
 
 def _setters(api):
