@@ -1935,6 +1935,101 @@ int sfe_dsp_ofdmmod_process_stream(sfe_ofdmmod_t h, const void *d_in, size_t in_
                                    sfe_stream_t stream);
 int sfe_dsp_ofdmmod_destroy(sfe_ofdmmod_t h);
 
+/* ------------------------------------------------- QAM mapper and soft demapper
+ * One handle, two directions, like sfe_dsp_reed_* and sfe_dsp_ldpc_*.  map: rows of coded bytes on
+ * the device -- what sfe_dsp_ldpc_encode_stream, sfe_dsp_vit_* or sfe_dsp_reed_* wrote -- become
+ * rows of cf32 constellation points, laid out as sfe_dsp_ofdmmod_*'s SYMBOLS mode reads them.
+ * demap: rows of cf32 equalised symbols, laid out as sfe_dsp_ofdm_* writes them, become rows of
+ * float32 max-log LLRs, laid out as SFE_VIT_IN_SOFT of sfe_dsp_ldpc_* and sfe_dsp_vit_* reads them,
+ * each symbol weighted, where the handle says so, by |H|^2 read from sfe_dsp_ofdm_*'s d_chan where
+ * it lies.  Both directions take an optional bit interleaver per row.  Rows are independent;
+ * nothing is carried.
+ * Shape, fixed at create: order M in {2, 4, 16, 64, 256}, bps = log2 M; amp finite and > 0; scale
+ * finite and > 0; n_sym in [1, 2^24] symbols per row, B = n_sym bps bits per row; perm [B] uint32,
+ * a permutation of [0, B) validated at create, or NULL for the identity; csi_period in [0, 4096],
+ * 0 for no channel weighting, else csi_len in [1, 65536] and csi_index [csi_period] uint32, each
+ * < csi_len (behind sfe_dsp_ofdm_*: csi_period = Nd, csi_len = N, csi_index[i] = the FFT bin of
+ * data bin i).  There is no setter and no state.  Anything else is SFE_EINVAL with a message that
+ * starts with "qam: ", on any machine, before the device is touched.
+ * Constellation: an axis carries m bits, m = bps / 2 for M >= 4; for M = 2, m = 1 on I only, Q is
+ * +0 on map and ignored on demap.  The axis word w = (b_0 .. b_(m-1)), b_0 first (as a number: b_0
+ * its most significant bit), has the odd integer u(w) = (1 - 2 b_0) A(b_1 ..), A() = 1,
+ * A(b, rest) = 2^(len(rest)+1) - (1 - 2b) A(rest): Gray along the axis, b_0 = 0 the positive half;
+ * for m = 2 the words 11, 10, 00, 01 stand at -3, -1, +1, +3.  The level table is
+ * lev[w] = float32(amp d_M u(w)), d_2 = 1 and d_M = sqrt(3 / (2 (M - 1))) = 1 / sqrt(K_M) with the
+ * integer K_M = 2 (M - 1) / 3 (2, 10, 42, 170) for M >= 4: formed in float64 from the float32 amp
+ * as amp u(w) / sqrt(K_M) and rounded once, so that M = 4 is exactly sfe_dsp_mod_*'s and
+ * sfe_dsp_ofdmmod_*'s Gray QPSK.  At most 16 entries, made at create.
+ * Bits: symbol q of a row carries the symbol-bit positions t = q bps + c, c < bps: c < m is I-axis
+ * bit c, c >= m is Q-axis bit c - m.  Position t holds coded bit perm[t].  Coded bit v is bit
+ * 7 - (v mod 8) of byte floor(v / 8) of the row: MSB-first, the layout
+ * sfe_dsp_ldpc_encode_stream, sfe_dsp_vit_* and sfe_dsp_reed_* write.  A row reads ceil(B / 8)
+ * bytes.
+ * Map: the cf32 at d_sym + row*out_stride + q is (lev[w_I], lev[w_Q]): table words.
+ * Demap, stated operation by operation in simplefe_amd/csrc/qam_law.h, which the kernel and the
+ * host plan both compile, every operation one IEEE float32 operation and nothing contracted.  For
+ * the symbol z at d_sym + row*in_stride + q:
+ *   weight   no CSI: w = scale.  CSI: h = d_csi[row*csi_stride + csi_index[q mod csi_period]],
+ *            g = fmaf(h.i, h.i, h.r h.r), w = scale g.
+ *   per axis value y (z.r or z.i) and axis bit c: for every word v, e_v = t t with t = y - lev[v];
+ *            D0 = min of e_v over the words whose bit c is 0, D1 over those whose bit c is 1 (min
+ *            is exact, so its order cannot show); r = w (D1 - D0).  r > 0 favours bit 0: the sign
+ *            of sfe_dsp_vit_* and sfe_dsp_ldpc_*.
+ *   store    r as float32 at d_soft + row*out_stride + perm[t].
+ * Promised: the same call gives the same bits on every run; a row's output depends on that row,
+ * its csi row and the handle only -- never on the row number, the count, addresses or strides; the
+ * device's words EQUAL sfe_dsp_qam_plan's for every input whose intermediate values are zero or
+ * normal numbers (otherwise the words are written and nothing is said of them); exactly the B
+ * floats (demap) or n_sym cf32 (map) of each row are written, nothing between rows, to the byte;
+ * the exact case: order 2, amp 1, scale 1, no CSI, the symbol 0.5+0j gives r exactly 2. */
+#define SFE_QAM_MAP 0
+#define SFE_QAM_DEMAP 1
+typedef void *sfe_qam_t;  /* opaque: one mapper / demapper; it owns its tables on the device and nothing in it changes after create */
+/* Host-only (no GPU): validates what create validates and reports bps and the bytes a row of
+ * coded bits holds, ceil(B / 8) (each pointer may be NULL); then, with in != NULL, runs n_rows rows
+ * by the law above into out, exactly as stated: the reference of the device's bits.  direction
+ * SFE_QAM_MAP: in is bytes (in_stride in bytes), out cf32 (out_stride in cf32), csi is ignored.
+ * SFE_QAM_DEMAP: in is cf32 (in_stride in cf32), csi cf32 rows at csi_stride (required exactly
+ * when csi_period > 0), out float32 (out_stride in floats).  Host buffers need no alignment.  A
+ * stride below its row (ceil(B / 8) bytes, n_sym cf32, csi_len cf32, B floats) is SFE_ERANGE. */
+int sfe_dsp_qam_plan(int order, float amp, float scale, size_t n_sym, const uint32_t *perm,
+                     int csi_period, int csi_len, const uint32_t *csi_index, int direction,
+                     const void *in, size_t in_stride, const void *csi, size_t csi_stride,
+                     size_t n_rows, void *out, size_t out_stride, int *bps, size_t *row_bytes);
+/*   perm, csi_index   copied
+ * Arguments are checked before the device is touched: SFE_EINVAL for a bad one on any machine,
+ * SFE_ENODEV without a GPU. */
+int sfe_dsp_qam_create(int order, float amp, float scale, size_t n_sym, const uint32_t *perm,
+                       int csi_period, int csi_len, const uint32_t *csi_index, int device,
+                       sfe_qam_t *out);
+/* Row r reads ceil(B / 8) bytes at d_bytes + r*in_stride (bytes) and writes n_sym cf32 at
+ * d_sym + r*out_stride (cf32).  *n_out = n_rows; n_rows = 0 is a no-op.  A stride below its row
+ * is SFE_ERANGE; a null buffer, a d_sym that is not 8-byte aligned (coded bytes need no
+ * alignment), n_rows >= 2^31, a stride that takes a buffer's byte range to 2^62, a call of 2^31
+ * workgroups or more (one per 2048 symbols of a row) and an output byte range that overlaps the
+ * input's are SFE_EINVAL; every refusal carries a message that starts with "qam_map_stream: " and
+ * nothing is launched.  Asynchronous on `stream`; one kernel launch and nothing else: allocates
+ * nothing, does not synchronise the host, and may be captured into a graph.  Behind
+ * sfe_dsp_ldpc_encode_stream its d_code and out_stride, in front of sfe_dsp_ofdmmod_* (SYMBOLS
+ * mode, whose amp then multiplies) its d_in and in_stride, are the whole glue. */
+int sfe_dsp_qam_map_stream(sfe_qam_t h, const void *d_bytes, size_t in_stride, size_t n_rows,
+                           void *d_sym, size_t out_stride, size_t *n_out, sfe_stream_t stream);
+/* Row r reads n_sym cf32 at d_sym + r*in_stride (cf32) and, on a handle with csi_period > 0,
+ * csi_len cf32 at d_csi + r*csi_stride (cf32); it writes B floats at d_soft + r*out_stride
+ * (floats).  d_csi is required exactly when the handle has csi_period > 0 and refused otherwise.
+ * *n_out = n_rows; n_rows = 0 is a no-op.  A stride below its row is SFE_ERANGE; a null buffer,
+ * misaligned buffers (cf32 8 bytes, floats 4), n_rows >= 2^31, a stride that takes a buffer's
+ * byte range to 2^62, a call of 2^31 workgroups or more and an output byte range that overlaps an
+ * input's are SFE_EINVAL; every refusal carries a message that starts with "qam_demap_stream: "
+ * and nothing is launched.  Asynchronous, one launch, no allocation, no host synchronisation,
+ * capturable.  Behind sfe_dsp_ofdm_* (zero-forcing output) its d_out, out_stride, d_chan and
+ * n_fft, in front of sfe_dsp_ldpc_* or sfe_dsp_vit_* (SFE_VIT_IN_SOFT) their d_in and in_stride,
+ * are the whole glue. */
+int sfe_dsp_qam_demap_stream(sfe_qam_t h, const void *d_sym, size_t in_stride, const void *d_csi,
+                             size_t csi_stride, size_t n_rows, void *d_soft, size_t out_stride,
+                             size_t *n_out, sfe_stream_t stream);
+int sfe_dsp_qam_destroy(sfe_qam_t h);
+
 #ifdef __cplusplus
 }
 #endif

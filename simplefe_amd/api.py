@@ -1993,6 +1993,125 @@ class OfdmMod(_Block):
         return np.ascontiguousarray(raw) if tx10 else np.ascontiguousarray(raw).view(np.complex64)
 
 
+def _qam_shape(order, amp, scale, n_sym, perm, csi_index, csi_len):
+    """(the leading arguments of sfe_dsp_qam_plan / _create, the arrays they point into)."""
+    perm = None if perm is None else np.ascontiguousarray(perm, dtype=np.uint32).ravel()
+    idx = None if csi_index is None else np.ascontiguousarray(csi_index, dtype=np.uint32).ravel()
+    head = (int(order), float(amp), float(scale), int(n_sym), None if perm is None else perm.ctypes.data,
+            0 if idx is None else idx.size, int(csi_len), None if idx is None else idx.ctypes.data)
+    return head, (perm, idx)
+
+
+def qam_plan(order, n_sym, amp=1.0, scale=1.0, perm=None, csi_index=None, csi_len=0, data=None, sym=None, csi=None):
+    """sfe_dsp_qam_plan (host only, no GPU): validates and, without data and sym, returns (bps, the bytes of a row of coded
+    bits).  With data -- (n_rows, >= row bytes) uint8 coded bytes, MSB-first -- it maps: returns (n_rows, n_sym) complex64.
+    With sym -- (n_rows, >= n_sym) complex64 -- and, on a shape with csi_index, csi -- (n_rows, >= csi_len) complex64 -- it
+    demaps: returns (n_rows, n_sym * bps) float32 max-log soft values, positive for bit 0.  These are the device's bits.
+    perm: uint32 [n_sym * bps], position t holds coded bit perm[t]; csi_index: uint32 [csi_period], each below csi_len.
+    Raises SfeError on arguments the block refuses."""
+    head, _alive = _qam_shape(order, amp, scale, n_sym, perm, csi_index, csi_len)
+    L, bps, nb = _l.load(), C.c_int(0), C.c_size_t(0)
+    tail = (C.byref(bps), C.byref(nb))
+    check(L.sfe_dsp_qam_plan(*head, _l.QAM_MAP, None, 0, None, 0, 0, None, 0, *tail))
+    if data is None and sym is None:
+        return bps.value, nb.value
+    n_sym = int(n_sym)
+    if data is not None:
+        d = np.asarray(data, dtype=np.uint8)
+        d = np.ascontiguousarray(d.reshape(1, -1) if d.ndim == 1 else d)
+        out = np.empty((d.shape[0], n_sym), np.complex64)
+        check(L.sfe_dsp_qam_plan(*head, _l.QAM_MAP, d.ctypes.data if d.size else None, d.shape[1], None, 0, d.shape[0],
+                                 out.ctypes.data if out.size else None, n_sym, *tail))
+        return out
+    z = np.asarray(sym, dtype=np.complex64)
+    z = np.ascontiguousarray(z.reshape(1, -1) if z.ndim == 1 else z)
+    h = None
+    if csi is not None:
+        h = np.asarray(csi, dtype=np.complex64)
+        h = np.ascontiguousarray(h.reshape(1, -1) if h.ndim == 1 else h)
+        if h.shape[0] != z.shape[0]:
+            raise ValueError("qam_plan: csi has %d rows for %d rows of symbols" % (h.shape[0], z.shape[0]))
+    out = np.empty((z.shape[0], n_sym * bps.value), np.float32)
+    check(L.sfe_dsp_qam_plan(*head, _l.QAM_DEMAP, z.ctypes.data if z.size else None, z.shape[1], None if h is None else h.ctypes.data,
+                             0 if h is None else h.shape[1], z.shape[0], out.ctypes.data if out.size else None, n_sym * bps.value, *tail))
+    return out
+
+
+class Qam(_Block):
+    """QAM mapper and soft demapper (sfe_dsp_qam_*): map_stream turns rows of coded bytes on the device -- what
+    Ldpc.encode_stream wrote -- into rows of cf32 constellation points of order 2, 4, 16, 64 or 256 for OfdmMod's SYMBOLS
+    mode; demap_stream turns rows of cf32 equalised symbols -- a row of Ofdm's zero-forcing output -- into rows of float32
+    max-log soft values for Ldpc / Vit in VIT_IN_SOFT mode, each symbol weighted by scale * |H|^2 read from Ofdm's d_chan
+    through csi_index where one is given.  perm is an optional bit interleaver per row.  The device's bits are qam_plan's."""
+    _prefix = "qam"
+
+    def __init__(self, order, n_sym, amp=1.0, scale=1.0, perm=None, csi_index=None, csi_len=0, device=0):
+        head, _alive = _qam_shape(order, amp, scale, n_sym, perm, csi_index, csi_len)
+        self.order, self.n_sym = int(order), int(n_sym)
+        self.csi_period, self.csi_len = head[5], int(csi_len) if head[5] else 0
+        self._create(*head, device)
+        self.bps, self.n_bytes = qam_plan(order, n_sym, amp, scale)
+        self.n_bits = self.n_sym * self.bps         # floats a row of soft values holds
+
+    def map_stream(self, d_bytes, n_rows, d_sym, in_stride=None, out_stride=None, stream=None):
+        """d_*: DeviceArray or raw device pointers.  Row r reads n_bytes bytes at d_bytes + r*in_stride (bytes; default
+        n_bytes) and writes n_sym cf32 at d_sym + r*out_stride (cf32; default n_sym).  Returns n_rows."""
+        k = C.c_size_t(0)
+        check(self._fn("map_stream")(self._h, self._ptr(d_bytes), self.n_bytes if in_stride is None else int(in_stride), int(n_rows),
+                                     self._ptr(d_sym), self.n_sym if out_stride is None else int(out_stride), C.byref(k), stream))
+        return k.value
+
+    def demap_stream(self, d_sym, n_rows, d_soft, d_csi=None, in_stride=None, csi_stride=None, out_stride=None, stream=None):
+        """d_*: DeviceArray or raw device pointers.  Row r reads n_sym cf32 at d_sym + r*in_stride (cf32; default n_sym) and,
+        on a handle with csi_index, csi_len cf32 at d_csi + r*csi_stride (cf32; default csi_len); it writes n_bits floats at
+        d_soft + r*out_stride (floats; default n_bits).  Returns n_rows."""
+        k = C.c_size_t(0)
+        check(self._fn("demap_stream")(self._h, self._ptr(d_sym), self.n_sym if in_stride is None else int(in_stride), self._ptr(d_csi),
+                                       self.csi_len if csi_stride is None else int(csi_stride), int(n_rows), self._ptr(d_soft),
+                                       self.n_bits if out_stride is None else int(out_stride), C.byref(k), stream))
+        return k.value
+
+    def reset(self):
+        raise AttributeError("Qam has no reset: it carries no state")
+
+    def map(self, data):
+        """Host convenience, computed on the GPU: data is (n_rows, >= n_bytes) uint8; returns what qam_plan returns."""
+        d = np.asarray(data, dtype=np.uint8)
+        d = np.ascontiguousarray(d.reshape(1, -1) if d.ndim == 1 else d)
+        nr = d.shape[0]
+        held = [DeviceArray.from_bytes(d), DeviceArray(max(1, 2 * nr * self.n_sym))]
+        try:
+            if nr:
+                self.map_stream(held[0], nr, held[1], in_stride=d.shape[1])
+            out = held[1].to_numpy(2 * nr * self.n_sym).view(np.complex64).reshape(nr, self.n_sym)
+        finally:
+            for x in held:
+                x.free()
+        return np.ascontiguousarray(out)
+
+    def demap(self, sym, csi=None):
+        """Host convenience, computed on the GPU: sym is (n_rows, >= n_sym) complex64, csi (n_rows, >= csi_len) complex64 on a
+        handle with csi_index; returns what qam_plan returns."""
+        z = np.asarray(sym, dtype=np.complex64)
+        z = np.ascontiguousarray(z.reshape(1, -1) if z.ndim == 1 else z)
+        nr = z.shape[0]
+        held = [DeviceArray.from_numpy(z.view(np.float32)), DeviceArray(max(1, nr * self.n_bits))]
+        try:
+            d_csi, cs = None, None
+            if csi is not None:
+                h = np.asarray(csi, dtype=np.complex64)
+                h = np.ascontiguousarray(h.reshape(1, -1) if h.ndim == 1 else h)
+                d_csi, cs = DeviceArray.from_numpy(h.view(np.float32)), h.shape[1]
+                held.append(d_csi)
+            if nr:
+                self.demap_stream(held[0], nr, held[1], d_csi, in_stride=z.shape[1], csi_stride=cs)
+            out = held[1].to_numpy(nr * self.n_bits).reshape(nr, self.n_bits)
+        finally:
+            for x in held:
+                x.free()
+        return np.ascontiguousarray(out)
+
+
 def rs_plan(state, upsample, n_in, out_len, rate):
     """Host-only replay of one process() call's time law (sfe_dsp_rs_plan).
     state: lib.TimeState (updated in place).  Returns (rel_pos int32[], mu float32[])."""

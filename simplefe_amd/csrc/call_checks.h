@@ -187,6 +187,44 @@ inline int check_rows(const char *who, const RowNouns &nn, size_t n, const void 
     return SFE_OK;
 }
 
+// ---- typed rows (qam): the rows family where every buffer has an element of its own -- per item one row of `in_row`
+// elements of isz bytes, where d_side is given one row of `side_row` elements of ssz bytes beside it, and one row of `out_row`
+// elements of osz bytes out; the strides count elements.  An element of one byte needs no alignment.  The SFE_ERANGE
+// sentence reads "in_stride S < the R <in_row>, <side_name> S < the R <side_row>, or out_stride S < the R <out_row>".
+struct TypedRowNouns {
+    const char *count;                  // "n_rows"
+    const char *in_row, *side_name, *side_row, *out_row;    // "cf32 of a row", "csi_stride", "cf32 of a csi row", "floats of a row"
+    const char *elements;               // refuse_misaligned's
+};
+inline int check_typed_rows(const char *who, const TypedRowNouns &nn, size_t n, const void *d_in, size_t in_stride, size_t in_row, size_t isz,
+                            const void *d_side, size_t side_stride, size_t side_row, size_t ssz, const void *d_out, size_t out_stride,
+                            size_t out_row, size_t osz, bool *go)
+{
+    *go = false;
+    if (n >= ((size_t)1 << 31)) {
+        set_error("%s: %s = %zu must be below 2^31 per call", who, nn.count, n);
+        return SFE_EINVAL;
+    }
+    if (n == 0) return SFE_OK;
+    int rc = refuse_null(who, {d_in, d_out});
+    if (rc != SFE_OK) return rc;
+    if (in_stride < in_row || (d_side && side_stride < side_row) || out_stride < out_row) {
+        set_error("%s: in_stride %zu < the %zu %s, %s %zu < the %zu %s, or out_stride %zu < the %zu %s", who, in_stride, in_row, nn.in_row,
+                  nn.side_name, side_stride, d_side ? side_row : (size_t)0, nn.side_row, out_stride, out_row, nn.out_row);
+        return SFE_ERANGE;
+    }
+    size_t in_b = 0, si_b = 0, ou_b = 0;
+    if (!span_bytes(n - 1, in_stride, in_row, isz, &in_b) || (d_side && !span_bytes(n - 1, side_stride, side_row, ssz, &si_b)) ||
+        !span_bytes(n - 1, out_stride, out_row, osz, &ou_b))
+        return refuse_2_62(who);
+    const Span in{d_in, in_b, isz}, si{d_side, si_b, ssz}, ou{d_out, ou_b, osz};
+    if ((rc = refuse_misaligned(who, nn.elements, {in, si, ou})) != SFE_OK || (rc = refuse_overlap(who, in, {ou})) != SFE_OK ||
+        (rc = refuse_overlap(who, si, {ou})) != SFE_OK)
+        return rc;
+    *go = true;
+    return SFE_OK;
+}
+
 // ---- windows: a receiver that cuts n_bursts windows from each of S streams of n_in samples (isz bytes each) at indices and
 // behind gates that are optional, and writes a row of `row` cf32 (`row_name`, for the message) per window, with an optional
 // row of chan_row cf32 (ofdm's channel; d_chan null elsewhere), a record of rec_floats and a status.

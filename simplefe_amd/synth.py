@@ -1452,3 +1452,67 @@ def ofdm_reference(x, o, n_fft, cp, advance, n_train, n_data, kind, train, pilot
     Z = Z / (h2 if out_mode == 1 else np.abs(H[data][None, :]) ** 2)
     rec = np.array([eps, h2, p.min() / h2, perr, np.angle(phi[0]) / (2 * np.pi), np.angle(phi[-1]) / (2 * np.pi), 0.0, 0.0], np.float32)
     return Z.astype(np.complex64), H.astype(np.complex64), rec, 0
+
+
+# ---- the QAM mapper and soft demapper (sfe_dsp_qam_*)
+def qam_axis_words(m):
+    """(u, bits): the odd integers u(w) of the 2^m axis words w = (b_0 .. b_(m-1)), b_0 the most significant bit of w, by the
+    law's recursion, and the words' bits (2^m, m)."""
+    def A(bits):
+        return 1 if not bits else 2 ** len(bits) - (1 - 2 * bits[0]) * A(bits[1:])
+    bits = [[(w >> (m - 1 - c)) & 1 for c in range(m)] for w in range(1 << m)]
+    return np.array([(1 - 2 * b[0]) * A(b[1:]) for b in bits], np.int64), np.array(bits, np.uint8)
+
+
+def qam_levels(order, amp=1.0):
+    """The level table of the law, float32 [2^m]: float32(amp u(w) / sqrt(K)), K = 1 for order 2, else 2 (order - 1) / 3,
+    formed in float64 from the float32 amp and rounded once."""
+    bps = {2: 1, 4: 2, 16: 4, 64: 6, 256: 8}[int(order)]
+    m = 1 if bps == 1 else bps // 2
+    K = 1 if order == 2 else 2 * (int(order) - 1) // 3
+    u, _ = qam_axis_words(m)
+    return (np.float64(np.float32(amp)) * u.astype(np.float64) / np.sqrt(np.float64(K))).astype(np.float32)
+
+
+def qam_points(order, amp=1.0):
+    """(points complex128 [M], bits uint8 [M, bps]): every point of the constellation, its components the float32 levels,
+    and the bps bits it carries in the order of the symbol-bit positions (I-axis bits first)."""
+    lev = qam_levels(order, amp).astype(np.float64)
+    bps = {2: 1, 4: 2, 16: 4, 64: 6, 256: 8}[int(order)]
+    m = 1 if bps == 1 else bps // 2
+    _, ab = qam_axis_words(m)
+    if bps == 1:
+        return lev.astype(np.complex128), ab
+    wi, wq = np.divmod(np.arange(1 << bps), 1 << m)
+    return lev[wi] + 1j * lev[wq], np.concatenate([ab[wi], ab[wq]], axis=1)
+
+
+def qam_reference(sym, order, amp=1.0, scale=1.0, perm=None, csi=None, csi_index=None):
+    """The max-log soft values of sfe_dsp_qam_* in float64, by brute force over all M points of the constellation and with
+    no per-axis shortcut: for symbol z of a row and each of its bps bits, D0 and D1 are the least |z - p|^2 over the points p
+    whose bit is 0 and 1, r = w (D1 - D0), w = scale, or scale |h|^2 with h = csi[row, csi_index[q mod len(csi_index)]].
+    The float at perm[t] is symbol-bit position t's.  sym (n_rows, n_sym) complex; returns (n_rows, n_sym bps) float64."""
+    z = np.atleast_2d(np.asarray(sym)).astype(np.complex128)
+    pts, bits = qam_points(order, amp)
+    bps = bits.shape[1]
+    nr, ns = z.shape
+    w = np.full((nr, ns), float(np.float32(scale)))
+    if csi_index is not None:
+        idx = np.asarray(csi_index, np.int64).ravel()
+        h = np.atleast_2d(np.asarray(csi)).astype(np.complex128)[:, idx[np.arange(ns) % idx.size]]
+        w = w * (h.real ** 2 + h.imag ** 2)
+    out = np.empty((nr, ns, bps))
+    step = max(1, (1 << 22) // pts.size)
+    for r in range(nr):
+        for a in range(0, ns, step):
+            d = np.abs(z[r, a:a + step, None] - pts[None, :]) ** 2
+            for c in range(bps):
+                one = bits[:, c] == 1
+                out[r, a:a + step, c] = w[r, a:a + step] * (d[:, one].min(axis=1) - d[:, ~one].min(axis=1))
+    out = out.reshape(nr, ns * bps)
+    if perm is not None:
+        p = np.asarray(perm, np.int64).ravel()
+        scattered = np.empty_like(out)
+        scattered[:, p] = out
+        out = scattered
+    return out
