@@ -2030,6 +2030,141 @@ int sfe_dsp_qam_demap_stream(sfe_qam_t h, const void *d_sym, size_t in_stride, c
                              size_t *n_out, sfe_stream_t stream);
 int sfe_dsp_qam_destroy(sfe_qam_t h);
 
+/* ------------------------------------------------- 2-(G)FSK burst modem
+ * One handle, two directions, like sfe_dsp_qam_*.  mod: per burst, ceil(n_bits / 8) coded bytes on
+ * the device -- what sfe_dsp_ldpc_encode_stream, sfe_dsp_vit_* or sfe_dsp_reed_* wrote -- become
+ * one continuous-phase, constant-envelope frame behind a preamble, placed in an output stream as
+ * sfe_dsp_mod_* places its frames.  demod: per burst, a window of a stream that starts where
+ * sfe_dsp_corr_*'s peak says goes through a quadrature discriminator and a matched filter; timing,
+ * deviation and carrier offset are fitted on the preamble, and the data symbols come out as float32
+ * soft values (positive for bit 0, the sign of sfe_dsp_vit_* and sfe_dsp_ldpc_*) and, where asked,
+ * as packed hard bits (what sfe_dsp_reed_* and this block's mod read).  Nothing is carried.  M = 2
+ * only: 4-level FSK needs a sequence detector and is not built.
+ * Shape, fixed at create: sps in [2, 64]; the frequency pulse g [n_taps] real float32, finite,
+ * 1 <= n_taps <= 64 sps, Q = ceil(n_taps / sps); the modulation index h finite and > 0; amp finite
+ * and > 0; preamble bits pre [n_pre = Lp] bytes of 0 or 1, Lp in [2, 1024]; n_bits in [1, 32768];
+ * N = Lp + n_bits symbols; the matched filter m [n_mf] real float32, finite, n_mf in [1, 256], its
+ * sum (formed in float64) > 0; delay in [1, 2^20]; the timing range R in [0, 64]; scale finite and
+ * > 0; min_gate finite; n_streams >= 1; out_fmt SFE_FMT_F32 or SFE_FMT_TX10.  Anything else is
+ * SFE_EINVAL with a message that starts with "fsk: ", on any machine, before the device is touched.
+ * The law is stated operation by operation in simplefe_amd/csrc/fsk_law.h, which the kernels and
+ * the host plan both compile: every multiply that feeds an add an explicit fmaf, everything else
+ * one IEEE float32 operation or exact integer arithmetic mod 2^32 as uint32, nothing contracted.
+ * A symbol's level is a = 1 - 2c for its bit c.
+ * Integer phase: G[j] = rint(h g[j] 2^31), formed in float64 and rounded once; C[0] = 0,
+ * C[j+1] = C[j] + G[j], Gsum = C[n_taps].  Create refuses a sum of the G that is <= 0 as a signed
+ * sum, and any residue r with sum over q of |G[q sps + r]| >= 2^30: that sum is the instantaneous
+ * frequency, kept under a quarter turn per sample so that the discriminator has room for a carrier
+ * offset.  A frame has F = (N + Q - 1) sps + 1 samples -- the last symbol's last phase increment
+ * ends on the final one -- and P[i] = sum over k < N of a_k C[clamp(i - k sps, 0, n_taps)], exact,
+ * so the order of summation cannot show.
+ * fsk_cis(p): q = ((p + 2^29) >> 30) & 3, r = (int32)(p - (q << 30)) in [-2^29, 2^29),
+ * t = (float)r 2^-29, z = t t; s = t S(z), c = 1 + z Cc(z) by fmaf chains (four coefficients each,
+ * the last constant of the cosine's chain exactly 1); rotated by q: (c, s), (-s, c), (-c, -s),
+ * (s, -c).  fsk_cis(k 2^30) is exactly (+-1, +-0) or (+-0, +-1), and each component is within
+ * 2 ulp(1) = 2.39e-7 of float64 cos / sin for every one of the 2^32 phases.
+ * Modulator: y[i] = (amp c, amp s) of fsk_cis(P[i]), one product per component.  Payload bit t of
+ * burst b is bit 7 - (t mod 8) of byte floor(t / 8) at d_bytes + b*in_stride: MSB-first; pad bits
+ * are ignored.  Placement is sfe_dsp_mod_*'s with this F: a call defines every sample of
+ * [0, n_out), a sample in no frame is +0, the refusals for start_base, start_step and n_out are
+ * the same.  TX10 bytes are exactly sfe_dsp_tx_f32_to_10bit's of the F32 output, groups aligned to
+ * the stream, not to frames.
+ * Demodulator: burst b of stream s starts at o = start_base + b*start_step + idx; d_idx, d_gate
+ * and statuses 2 and 3 are sfe_dsp_burst_*'s.
+ *   reach    [o + delay - R - 1, o + delay + R + (N - 1) sps + n_mf) of the stream's samples; not
+ *            inside [0, n_in): status 3.  A gate below min_gate, or a NaN gate: status 2.  Neither
+ *            reads a sample.
+ *   v        v[i] = the FM detector of sfe_dsp_polar_* (polar_law.h, gain 1) of x[o + i] and its
+ *            predecessor; u8 input is converted as sfe_dsp_rx_u8_to_f32 converts it.
+ *   u        u(i) = sum over j < n_mf of m[j] v[i + j], an fmaf chain from +0 in increasing j.
+ *   e        the expected response of the preamble, made at create in float64 from the integer
+ *            pulse so that inter-symbol interference inside the preamble does not bias the fit:
+ *            D[i] = sum over k < Lp of a_k G[i - k sps] (data symbols taken as 0),
+ *            U = (sum of G / sps) sum m, e[k] = float32(sum_j m[j] D[delay + k sps + j - 1] / U);
+ *            se = sum e, see = sum e^2, den = Lp see - se^2 formed in float64 and rounded once;
+ *            create refuses den not > 0.  A long run of one level then reads w = a.
+ *   fit      for tau = -R .. R, u_k = u(delay + tau + k sps), S1 = sum u_k and Se = sum e_k u_k
+ *            (the products rounded first), both PAIRWISE TREES: padded with +0 to the next power
+ *            of two, at each level s[k] = s[2k] + s[2k+1].  num = fmaf((float)Lp, Se, -(se S1)).
+ *            tau^ is the tau of the greatest num, the lowest among equals; a NaN never wins.
+ *            dev = num / den, dc = (S1 - dev se) / (float)Lp, f = dc 0x1.45f306p-3f in turns per
+ *            sample.  The residual is the same tree over (u_k - fmaf(dev, e_k, dc))^2 and
+ *            q = resid / ((dev dev) see).
+ *   output   for k = Lp .. N - 1: w = (u(delay + tau^ + k sps) - dc) / dev, r = scale w, float32 at
+ *            d_soft + (s*n_bursts + b)*soft_stride + (k - Lp).  With d_bits, bit (r < 0) is packed
+ *            MSB-first into ceil(n_bits / 8) bytes at d_bits + (s*n_bursts + b)*bits_stride, pad
+ *            bits 0.  The record is 8 float32: tau^, f, dev, q, then +0 four times.  Status 0.
+ *   failure  status 1: a non-finite sample in the reach, every num NaN, or a dev that is not > 0
+ *            and finite.  For status 1, 2 or 3 the soft values are +0, the bytes 0, the record
+ *            quiet NaN in words 0-3 and +0 in words 4-7.
+ * Promised: the same call gives the same bits on every run; a frame depends on its bytes and the
+ * handle only; a burst's outputs depend on its reach and the handle only -- never on b, s,
+ * n_bursts, addresses, strides or overlapping windows; u8 input gives the bits of the cf32 path on
+ * the converted samples; the device's F32 words, TX10 bytes, soft values, packed bits, records and
+ * statuses EQUAL sfe_dsp_fsk_plan's for every finite input whose partial sums are zero or normal
+ * numbers; nothing outside the named slots is written. */
+#define SFE_FSK_MOD 0
+#define SFE_FSK_DEMOD 1
+typedef void *sfe_fsk_t;  /* opaque: one modem; it owns its tables on the device and nothing in it changes after create but the input format */
+/* Host-only (no GPU): validates what create validates and reports N, F, e [n_pre] and den (each
+ * pointer may be NULL); then runs one direction by the law above, exactly as stated: the reference
+ * of the device's bits.  SFE_FSK_MOD: in is the payload bytes, in_len their stride in bytes
+ * (SFE_ERANGE below ceil(n_bits / 8)); out is the whole stream of n_out samples, cf32 or TX10
+ * groups; the placement is checked even without out.  SFE_FSK_DEMOD: in is ONE stream of in_len
+ * cf32 samples; idx and gate are host arrays of n_bursts entries or NULL; out takes n_bits float32
+ * per burst, bits (or NULL) ceil(n_bits / 8) bytes per burst, record (or NULL) 8 float32 per burst,
+ * status (or NULL) one int per burst, all contiguous; n_out is ignored. */
+int sfe_dsp_fsk_plan(int sps, const float *pulse, int n_taps, float h, float amp,
+                     const uint8_t *pre, int n_pre, int n_bits, const float *mf, int n_mf,
+                     int delay, int range, float scale, float min_gate, int out_fmt, int direction,
+                     const void *in, size_t in_len, const uint32_t *idx, const float *gate,
+                     size_t n_bursts, int64_t start_base, int64_t start_step, void *out,
+                     size_t n_out, uint8_t *bits, float *record, int *status, int *n_sym,
+                     int *frame_len, float *e, float *den);
+/*   pulse, pre, mf   copied
+ * Arguments are checked before the device is touched: SFE_EINVAL for a bad one on any machine,
+ * SFE_ENODEV without a GPU. */
+int sfe_dsp_fsk_create(int sps, const float *pulse, int n_taps, float h, float amp,
+                       const uint8_t *pre, int n_pre, int n_bits, const float *mf, int n_mf,
+                       int delay, int range, float scale, float min_gate, int out_fmt,
+                       int n_streams, int device, sfe_fsk_t *out);
+/* The demodulator's input: SFE_FMT_F32 (cf32, the default) or SFE_FMT_U8 ((I,Q) byte pairs).
+ * Takes effect from the next call; a captured call keeps the format it was captured with.  It is
+ * the handle's only setter. */
+int sfe_dsp_fsk_set_input_format(sfe_fsk_t h, int fmt);
+/* Burst b reads ceil(n_bits / 8) bytes at d_bytes + b*in_stride (bytes) and its F samples start at
+ * sample start_base + b*start_step of the n_out samples at d_out (cf32, or 5-byte groups of two
+ * samples with SFE_FMT_TX10); the call writes all n_out samples.  *n_written = n_out.  The checks
+ * and their codes are sfe_dsp_mod_process_stream's, word for word, with the prefix
+ * "fsk_mod_stream: "; nothing is launched on a refusal.  Asynchronous on `stream`; one kernel
+ * launch and nothing else: allocates nothing, does not synchronise the host, carries no state, and
+ * may be captured into a graph.  Behind sfe_dsp_ldpc_encode_stream or sfe_dsp_reed_* their output
+ * and its stride are the whole glue. */
+int sfe_dsp_fsk_mod_stream(sfe_fsk_t h, const void *d_bytes, size_t in_stride, size_t n_bursts,
+                           int64_t start_base, int64_t start_step, void *d_out, size_t n_out,
+                           size_t *n_written, sfe_stream_t stream);
+/* Stream s is the n_in samples at d_in + s*in_stride (samples of the input format); d_idx (uint32,
+ * + s*idx_stride + b), d_gate (float32, + s*gate_stride + b), d_bits, d_rec (+ (s*n_bursts + b)*8
+ * float32) and d_status (int32, + s*status_stride + b) may each be NULL.  *n_out = n_bursts;
+ * n_bursts = 0 is a no-op.  soft_stride < n_bits, bits_stride < ceil(n_bits / 8) (with d_bits) and
+ * status_stride < n_bursts (with d_status) are SFE_ERANGE; a null d_in or d_soft, misaligned
+ * buffers (cf32 8 bytes, u8 pairs 2, the 4-byte kinds 4; packed bits need none), n_in >= 2^31,
+ * n_streams * n_bursts >= 2^31, in_stride < n_in with several streams, starts that leave int64, a
+ * stride that takes a buffer's byte range to 2^62, and outputs that overlap an input or one
+ * another are SFE_EINVAL; every refusal carries a message that starts with "fsk_demod_stream: "
+ * and nothing is launched.  Asynchronous, one launch, no allocation, no host synchronisation, no
+ * state, capturable.  Behind sfe_dsp_corr_* (one template: the plan's modulated preamble)
+ * d_peak_idx and d_peak_val as they lie are d_idx and d_gate, and start_step is the correlator's
+ * block; in front of sfe_dsp_vit_* or sfe_dsp_ldpc_* (SFE_VIT_IN_SOFT) d_soft and soft_stride, in
+ * front of sfe_dsp_reed_* d_bits and bits_stride, are the whole glue. */
+int sfe_dsp_fsk_demod_stream(sfe_fsk_t h, const void *d_in, size_t n_in, size_t in_stride,
+                             const void *d_idx, size_t idx_stride, const void *d_gate,
+                             size_t gate_stride, size_t n_bursts, int64_t start_base,
+                             int64_t start_step, void *d_soft, size_t soft_stride, void *d_bits,
+                             size_t bits_stride, void *d_rec, void *d_status, size_t status_stride,
+                             size_t *n_out, sfe_stream_t stream);
+int sfe_dsp_fsk_destroy(sfe_fsk_t h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2112,6 +2112,162 @@ class Qam(_Block):
         return np.ascontiguousarray(out)
 
 
+def _fsk_shape(sps, pulse, h, pre, n_bits, mf, delay, rng, amp, scale, min_gate, out_fmt):
+    """(the leading arguments of sfe_dsp_fsk_plan / _create, the arrays they point into)."""
+    g = np.ascontiguousarray(np.asarray(pulse, dtype=np.float32).ravel())
+    p = np.ascontiguousarray(np.asarray(pre, dtype=np.uint8).ravel())
+    m = np.ascontiguousarray(np.asarray(mf, dtype=np.float32).ravel())
+    head = (int(sps), g.ctypes.data if g.size else None, g.size, float(h), float(amp), p.ctypes.data if p.size else None, p.size, int(n_bits),
+            m.ctypes.data if m.size else None, m.size, int(delay), int(rng), float(scale), float(min_gate), int(out_fmt))
+    return head, (g, p, m)
+
+
+def fsk_plan(sps, pulse, h, pre, n_bits, mf, delay, rng, amp=1.0, scale=1.0, min_gate=0.0, out_fmt=_l.FMT_F32, data=None, n_out=0,
+             start_base=0, start_step=0, n_bursts=None, x=None, idx=None, gate=None, want_bits=True):
+    """sfe_dsp_fsk_plan (host only, no GPU): validates and, without data and x, returns (N symbols per burst, F samples per
+    frame, e (n_pre,) float32, den) -- after checking the placement too where n_out or n_bursts is given.  With data --
+    (n_bursts, >= ceil(n_bits / 8)) uint8 payload bytes, MSB-first -- it modulates: returns the stream of n_out samples,
+    complex64 (n_out,), or the (n_out / 2) * 5 uint8 bytes of the transmit wire format with FMT_TX10.  With x -- the complex
+    samples of ONE stream -- it demodulates n_bursts bursts: returns (soft (n_bursts, n_bits) float32, bits (n_bursts,
+    ceil(n_bits / 8)) uint8 or None, record (n_bursts, 8) float32, status (n_bursts,) int32); idx (uint32) and gate (float32)
+    are host arrays of n_bursts entries or None; n_bursts defaults to len(idx), else 1.  These are the device's bits.
+    Raises SfeError on arguments the block refuses."""
+    head, _alive = _fsk_shape(sps, pulse, h, pre, n_bits, mf, delay, rng, amp, scale, min_gate, out_fmt)
+    L, N, F, den = _l.load(), C.c_int(0), C.c_int(0), C.c_float(0.0)
+    e = np.zeros(max(head[6], 1), np.float32)
+    tail = (C.byref(N), C.byref(F), e.ctypes.data, C.byref(den))
+    if data is None and x is None:
+        check(L.sfe_dsp_fsk_plan(*head, _l.FSK_MOD, None, 0, None, None, int(n_bursts or 0), int(start_base), int(start_step), None, int(n_out),
+                                 None, None, None, *tail))
+        return N.value, F.value, e[:head[6]].copy(), den.value
+    if data is not None:
+        d = np.asarray(data, dtype=np.uint8)
+        d = np.ascontiguousarray(d.reshape(1, -1) if d.ndim == 1 else d)
+        nb = d.shape[0] if n_bursts is None else int(n_bursts)
+        n_out = max(int(n_out), 0)
+        out = np.empty(n_out // 2 * 5, np.uint8) if out_fmt == _l.FMT_TX10 else np.empty(n_out, np.complex64)
+        check(L.sfe_dsp_fsk_plan(*head, _l.FSK_MOD, d.ctypes.data if d.size else None, d.shape[1] if d.size else 0, None, None, nb, int(start_base),
+                                 int(start_step), out.ctypes.data if out.size else None, n_out, None, None, None, *tail))
+        return out
+    x = np.ascontiguousarray(np.asarray(x, dtype=np.complex64).ravel())
+    if idx is not None:
+        idx = np.ascontiguousarray(idx, dtype=np.uint32).ravel()
+    if gate is not None:
+        gate = np.ascontiguousarray(gate, dtype=np.float32).ravel()
+    nb = int(n_bursts) if n_bursts is not None else (idx.size if idx is not None else 1)
+    for name, v in (("idx", idx), ("gate", gate)):
+        if v is not None and v.size != nb:
+            raise ValueError("fsk_plan: %s has %d entries for %d bursts" % (name, v.size, nb))
+    nbits = max(int(n_bits), 0)
+    soft, rec, st = np.empty((nb, nbits), np.float32), np.empty((nb, 8), np.float32), np.empty(nb, np.int32)
+    by = np.empty((nb, (nbits + 7) // 8), np.uint8) if want_bits else None
+    check(L.sfe_dsp_fsk_plan(*head, _l.FSK_DEMOD, x.ctypes.data if x.size else None, x.size, None if idx is None else idx.ctypes.data,
+                             None if gate is None else gate.ctypes.data, nb, int(start_base), int(start_step), soft.ctypes.data if soft.size else None,
+                             0, None if by is None else by.ctypes.data, rec.ctypes.data, st.ctypes.data, *tail))
+    return soft, by, rec, st
+
+
+class Fsk(_Block):
+    """2-(G)FSK burst modem (sfe_dsp_fsk_*): mod turns per burst ceil(n_bits / 8) coded bytes on the device -- what
+    Ldpc.encode_stream or Reed.encode_stream wrote -- into one continuous-phase frame behind a preamble, placed in an output
+    stream as Mod places its frames; demod turns per burst a window of a stream that starts where Corr's peak says into
+    float32 soft values for Vit / Ldpc in VIT_IN_SOFT mode and, where asked, packed hard bits for Reed, with a record (tau, f,
+    dev, q, 0, 0, 0, 0) and a status.  The device's bits are fsk_plan's."""
+    _prefix = "fsk"
+
+    def __init__(self, sps, pulse, h, pre, n_bits, mf, delay, rng, amp=1.0, scale=1.0, min_gate=0.0, out_fmt=_l.FMT_F32, n_streams=1, device=0):
+        head, _alive = _fsk_shape(sps, pulse, h, pre, n_bits, mf, delay, rng, amp, scale, min_gate, out_fmt)
+        self.sps, self.n_bits, self.n_pre, self.out_fmt, self.n_streams = int(sps), int(n_bits), head[6], int(out_fmt), int(n_streams)
+        self.n_bytes = (max(self.n_bits, 0) + 7) // 8
+        self.in_u8 = False
+        self._create(*head, self.n_streams, device)
+        self.n_sym, self.frame_len, self.e, self.den = fsk_plan(sps, pulse, h, pre, n_bits, mf, delay, rng, amp, scale, min_gate, out_fmt)
+
+    def set_input_format(self, fmt):
+        """The demodulator's input: lib.FMT_F32 (cf32) or lib.FMT_U8 ((I,Q) byte pairs, converted on load)."""
+        self._set_input_format(fmt)
+
+    def mod(self, d_bytes, n_bursts, d_out, n_out, start_base=0, start_step=0, in_stride=None, stream=None):
+        """d_*: DeviceArray or raw device pointers.  Burst b reads n_bytes bytes at d_bytes + b*in_stride (bytes; default
+        n_bytes) and its frame_len samples start at sample start_base + b*start_step of the n_out samples at d_out (cf32, or
+        5-byte groups of two samples with FMT_TX10); the call writes all n_out samples.  Returns n_out."""
+        k = C.c_size_t(0)
+        check(self._fn("mod_stream")(self._h, self._ptr(d_bytes), self.n_bytes if in_stride is None else int(in_stride), int(n_bursts),
+                                     int(start_base), int(start_step), self._ptr(d_out), int(n_out), C.byref(k), stream))
+        return k.value
+
+    def demod(self, d_in, n_in, n_bursts, d_soft, d_bits=None, d_idx=None, d_gate=None, d_rec=None, d_status=None, start_base=0, start_step=0,
+              in_stride=None, idx_stride=None, gate_stride=None, soft_stride=None, bits_stride=None, status_stride=None, stream=None):
+        """d_*: DeviceArray or raw device pointers.  Burst b of stream s starts at start_base + b*start_step + the uint32 at
+        d_idx + s*idx_stride + b (0 without d_idx) of the n_in samples at d_in + s*in_stride, is gated by the float32 at d_gate +
+        s*gate_stride + b, and writes n_bits float32 at d_soft + (s*n_bursts + b)*soft_stride, n_bytes packed bytes at d_bits +
+        (s*n_bursts + b)*bits_stride, 8 float32 at d_rec + (s*n_bursts + b)*8 and an int32 at d_status + s*status_stride + b.
+        in_stride defaults to n_in, soft_stride to n_bits, bits_stride to n_bytes and the other strides to n_bursts.  Returns
+        n_bursts."""
+        nb = int(n_bursts)
+        k = C.c_size_t(0)
+        check(self._fn("demod_stream")(
+            self._h, self._ptr(d_in), int(n_in), int(n_in) if in_stride is None else int(in_stride), self._ptr(d_idx),
+            nb if idx_stride is None else int(idx_stride), self._ptr(d_gate), nb if gate_stride is None else int(gate_stride), nb, int(start_base),
+            int(start_step), self._ptr(d_soft), self.n_bits if soft_stride is None else int(soft_stride), self._ptr(d_bits),
+            self.n_bytes if bits_stride is None else int(bits_stride), self._ptr(d_rec), self._ptr(d_status),
+            nb if status_stride is None else int(status_stride), C.byref(k), stream))
+        return k.value
+
+    def reset(self):
+        raise AttributeError("Fsk has no reset: it carries no state")
+
+    def modulate(self, data, n_out, start_base=0, start_step=0):
+        """Host convenience, computed on the GPU: data is (n_bursts, n_bytes) uint8; returns what fsk_plan returns."""
+        d = np.asarray(data, dtype=np.uint8)
+        d = np.ascontiguousarray(d.reshape(1, -1) if d.ndim == 1 else d)
+        tx10 = self.out_fmt == _l.FMT_TX10
+        nbytes = int(n_out) // 2 * 5 if tx10 else 8 * int(n_out)
+        held = [DeviceArray.from_bytes(d), DeviceArray(max(1, (nbytes + 3) // 4))]
+        try:
+            self.mod(held[0], d.shape[0], held[1], n_out, start_base, start_step, in_stride=d.shape[1])
+            raw = held[1].to_numpy().view(np.uint8)[:nbytes]
+        finally:
+            for x in held:
+                x.free()
+        return np.ascontiguousarray(raw) if tx10 else np.ascontiguousarray(raw).view(np.complex64)
+
+    def demodulate(self, x, idx=None, gate=None, n_bursts=None, start_base=0, start_step=0):
+        """Host convenience, computed on the GPU: x is (n_streams, n) complex -- or, with FMT_U8, (n_streams, 2n) uint8 (I,Q)
+        pairs -- idx (uint32) and gate (float32) are (n_streams, n_bursts) or None; returns (soft (n_streams, n_bursts, n_bits)
+        float32, bits (n_streams, n_bursts, n_bytes) uint8, record (n_streams, n_bursts, 8) float32, status (n_streams,
+        n_bursts) int32)."""
+        S, nbit, nby = self.n_streams, self.n_bits, self.n_bytes
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(S, -1)
+        if gate is not None:
+            gate = np.ascontiguousarray(gate, dtype=np.float32).reshape(S, -1)
+        nb = int(n_bursts) if n_bursts is not None else (idx.shape[1] if idx is not None else (gate.shape[1] if gate is not None else 1))
+        d_in, n = self._upload_input(x)
+        held = [d_in]
+        try:
+            d_idx = d_gate = None
+            if idx is not None:
+                d_idx = DeviceArray.from_numpy(idx.view(np.float32).ravel())
+                held.append(d_idx)
+            if gate is not None:
+                d_gate = DeviceArray.from_numpy(gate.ravel())
+                held.append(d_gate)
+            d_soft, d_by = DeviceArray(max(1, S * nb * nbit)), DeviceArray(max(1, (S * nb * nby + 3) // 4))
+            d_rec, d_st = DeviceArray(max(1, S * nb * 8)), DeviceArray(max(1, S * nb))
+            held += [d_soft, d_by, d_rec, d_st]
+            if nb:
+                self.demod(d_in, n, nb, d_soft, d_by, d_idx, d_gate, d_rec, d_st, start_base, start_step)
+            soft = d_soft.to_numpy(S * nb * nbit).reshape(S, nb, nbit)
+            by = d_by.to_numpy().view(np.uint8)[:S * nb * nby].reshape(S, nb, nby)
+            rec = d_rec.to_numpy(S * nb * 8).reshape(S, nb, 8)
+            st = d_st.to_numpy(S * nb).view(np.int32).reshape(S, nb)
+        finally:
+            for d in held:
+                d.free()
+        return np.ascontiguousarray(soft), np.ascontiguousarray(by), np.ascontiguousarray(rec), np.ascontiguousarray(st)
+
+
 def rs_plan(state, upsample, n_in, out_len, rate):
     """Host-only replay of one process() call's time law (sfe_dsp_rs_plan).
     state: lib.TimeState (updated in place).  Returns (rel_pos int32[], mu float32[])."""

@@ -109,6 +109,17 @@ inline int check_starts(const char *who, int64_t start_base, int64_t start_step,
     return SFE_OK;
 }
 
+// S streams of n_in samples lie in_stride apart (the windows family, and fsk's demodulator, whose outputs fit no family);
+// one stream's stride is not looked at
+inline int refuse_short_streams(const char *who, size_t S, size_t in_stride, size_t n_in)
+{
+    if (S > 1 && in_stride < n_in) {
+        set_error("%s: in_stride %zu < n_in %zu with %d streams", who, in_stride, n_in, (int)S);
+        return SFE_EINVAL;
+    }
+    return SFE_OK;
+}
+
 // ---- frames of F samples laid into a stream of n_out (mod, ofdmmod; their plans too): where they lie.  even_starts: a
 // frame starts on a 5-byte group of the TX10 wire format.
 inline int check_place(const char *who, int F, bool tx10, bool even_starts, size_t n_bursts, int64_t start_base, int64_t start_step,
@@ -246,10 +257,7 @@ inline int check_windows(const char *who, const char *row_name, size_t S, size_t
         set_error("%s: out_stride %zu < %s = %zu or status_stride %zu < n_bursts = %zu", who, out_stride, row_name, row, status_stride, n_bursts);
         return SFE_ERANGE;
     }
-    if (S > 1 && in_stride < n_in) {
-        set_error("%s: in_stride %zu < n_in %zu with %d streams", who, in_stride, n_in, (int)S);
-        return SFE_EINVAL;
-    }
+    if ((rc = refuse_short_streams(who, S, in_stride, n_in)) != SFE_OK) return rc;
     if ((rc = check_starts(who, start_base, start_step, n_bursts)) != SFE_OK) return rc;
     const size_t rows = S * n_bursts;
     size_t in_b = 0, ix_b = 0, ga_b = 0, ou_b = 0, st_b = 0;

@@ -35,6 +35,34 @@ struct ModArgs {
     uint8_t pos[MOD_TABLE];     // kept position i of a period: (t mod P) << 2 | j
 };
 
+// ---- the store path of a pair of neighbouring samples i0, i0 + 1 of the stream, shared with fsk.hip.  cf32: 16 bytes where
+// the pair's address allows it, else two 8-byte stores; `two` false: y0 alone.  TX10: i0 is even and the pair is one 5-byte
+// group of the stream, quantised as sfe_dsp_tx_f32_to_10bit does.
+__device__ __forceinline__ unsigned mod_q10(float x) { return (unsigned)((int)(short)(int)(x * 511.0f) + 512) & 0x3FFu; }
+
+template <bool TX10>
+__device__ __forceinline__ void mod_store_pair(void *out, long long i0, v2f y0, v2f y1, bool two)
+{
+    if (TX10) {
+        const unsigned u0 = mod_q10(y0.x), u1 = mod_q10(y0.y), u2 = mod_q10(y1.x), u3 = mod_q10(y1.y);
+        const unsigned w = ((u0 >> 8) | ((u1 >> 8) << 2) | ((u2 >> 8) << 4) | ((u3 >> 8) << 6)) | ((u0 & 0xFFu) << 8) |
+                           ((u1 & 0xFFu) << 16) | ((u2 & 0xFFu) << 24);
+        unsigned char *p = static_cast<unsigned char *>(out) + (i0 >> 1) * 5;
+        __builtin_memcpy(p, &w, 4);
+        p[4] = (unsigned char)u3;
+    } else {
+        v2f *p = static_cast<v2f *>(out) + i0;
+        if (!two) {
+            p[0] = y0;
+        } else if ((reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+            *reinterpret_cast<v4f *>(p) = v4f{y0.x, y0.y, y1.x, y1.y};
+        } else {
+            p[0] = y0;
+            p[1] = y1;
+        }
+    }
+}
+
 // One call: one launch over every tile of the stream.  Shapes and buffers are the caller's (api_mod.hip) to check.
 int launch_mod(const ModArgs &a, long long n_tiles, hipStream_t st);
 

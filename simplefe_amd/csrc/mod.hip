@@ -80,8 +80,6 @@ __device__ v2f mod_sample_of_stream(const ModArgs &a, long long i)
     return acc;
 }
 
-__device__ __forceinline__ unsigned mod_q10(float x) { return (unsigned)((int)(short)(int)(x * 511.0f) + 512) & 0x3FFu; }
-
 template <bool TX10>
 __global__ __launch_bounds__(MOD_THREADS) void mod_kernel(ModArgs a)
 {
@@ -147,28 +145,9 @@ __global__ __launch_bounds__(MOD_THREADS) void mod_kernel(ModArgs a)
     for (long long i0 = S0 + 2 * tid; i0 < A1; i0 += 2 * MOD_THREADS) {
         const long long i1 = i0 + 1;
         const v2f y0 = sample(i0);
-        if (TX10) {
-            const v2f y1 = i1 < A1 ? sample(i1) : mod_sample_of_stream(a, i1);
-            const unsigned u0 = mod_q10(y0.x), u1 = mod_q10(y0.y), u2 = mod_q10(y1.x), u3 = mod_q10(y1.y);
-            const unsigned w = ((u0 >> 8) | ((u1 >> 8) << 2) | ((u2 >> 8) << 4) | ((u3 >> 8) << 6)) | ((u0 & 0xFFu) << 8) |
-                               ((u1 & 0xFFu) << 16) | ((u2 & 0xFFu) << 24);
-            unsigned char *p = static_cast<unsigned char *>(a.out) + (i0 >> 1) * 5;
-            __builtin_memcpy(p, &w, 4);
-            p[4] = (unsigned char)u3;
-        } else {
-            v2f *p = static_cast<v2f *>(a.out) + i0;
-            if (i1 < A1) {
-                const v2f y1 = sample(i1);
-                if ((reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-                    *reinterpret_cast<v4f *>(p) = v4f{y0.x, y0.y, y1.x, y1.y};
-                } else {
-                    p[0] = y0;
-                    p[1] = y1;
-                }
-            } else {
-                p[0] = y0;
-            }
-        }
+        const bool two = i1 < A1;
+        const v2f y1 = two ? sample(i1) : (TX10 ? mod_sample_of_stream(a, i1) : v2f{0.0f, 0.0f});
+        mod_store_pair<TX10>(a.out, i0, y0, y1, two);
     }
 }
 

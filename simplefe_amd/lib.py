@@ -26,6 +26,7 @@ OFDM_OUT_ZF, OFDM_OUT_MRC = 0, 1                     # sfe_dsp_ofdm_*: out_mode
 OFDM_OK, OFDM_NO_ESTIMATE, OFDM_GATED, OFDM_OUT_OF_RANGE = 0, 1, 2, 3        # sfe_dsp_ofdm_*: a burst's status
 OFDMMOD_IN_BITS, OFDMMOD_IN_SYMBOLS = 0, 1           # sfe_dsp_ofdmmod_*: in_mode
 QAM_MAP, QAM_DEMAP = 0, 1                            # sfe_dsp_qam_plan: direction
+FSK_MOD, FSK_DEMOD = 0, 1                            # sfe_dsp_fsk_plan: direction
 
 
 class TimeState(C.Structure):
@@ -237,6 +238,13 @@ SIGNATURES = {
     "sfe_dsp_qam_map_stream": (i32, [vp, vp, sz, sz, vp, sz, C.POINTER(sz), vp]),
     "sfe_dsp_qam_demap_stream": (i32, [vp, vp, sz, vp, sz, sz, vp, sz, C.POINTER(sz), vp]),
     "sfe_dsp_qam_destroy": (i32, [vp]),
+    "sfe_dsp_fsk_plan": (i32, [i32, vp, i32, f32, f32, vp, i32, i32, vp, i32, i32, i32, f32, f32, i32, i32, vp, sz, vp, vp, sz, C.c_int64, C.c_int64,
+                               vp, sz, vp, vp, vp, C.POINTER(i32), C.POINTER(i32), vp, C.POINTER(f32)]),
+    "sfe_dsp_fsk_create": (i32, [i32, vp, i32, f32, f32, vp, i32, i32, vp, i32, i32, i32, f32, f32, i32, i32, i32, C.POINTER(vp)]),
+    "sfe_dsp_fsk_set_input_format": (i32, [vp, i32]),
+    "sfe_dsp_fsk_mod_stream": (i32, [vp, vp, sz, sz, C.c_int64, C.c_int64, vp, sz, C.POINTER(sz), vp]),
+    "sfe_dsp_fsk_demod_stream": (i32, [vp, vp, sz, sz, vp, sz, vp, sz, sz, C.c_int64, C.c_int64, vp, sz, vp, sz, vp, vp, sz, C.POINTER(sz), vp]),
+    "sfe_dsp_fsk_destroy": (i32, [vp]),
 }
 
 # the diagnostic library only (simplefe_amd/csrc/diag/sfe_dsp_diag.h; scripts/ load it by pointing LIB_PATH at it): bound when present

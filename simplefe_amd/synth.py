@@ -1516,3 +1516,80 @@ def qam_reference(sym, order, amp=1.0, scale=1.0, perm=None, csi=None, csi_index
         scattered[:, p] = out
         out = scattered
     return out
+
+
+# ------------------------------------------------------------------------------------------------ 2-(G)FSK (sfe_dsp_fsk_*)
+def gfsk_pulse(bt, sps, span):
+    """The GFSK frequency pulse: a Gaussian of bandwidth-time product bt convolved with a one-symbol rectangle, span * sps
+    float32 taps centred on the span, normalised to sum 1 (float64 sum, rounded once per tap)."""
+    import math
+    n = int(span) * int(sps)
+    t = (np.arange(n) - (n - 1) / 2.0) / float(sps)            # in symbols
+    k = 2.0 * math.pi * float(bt) / math.sqrt(math.log(2.0))
+    q = lambda v: 0.5 * math.erfc(v / math.sqrt(2.0))
+    g = np.array([q(k * (v - 0.5)) - q(k * (v + 0.5)) for v in t], np.float64)
+    return (g / g.sum()).astype(np.float32)
+
+
+def fsk_delay(n_taps, n_mf):
+    """The delay that centres a matched filter of n_mf taps on a symbol's pulse of n_taps (the discriminator's one sample
+    included)."""
+    return 1 + (int(n_taps) - int(n_mf)) // 2
+
+
+def fsk_levels(pre, data_bits):
+    """a = 1 - 2c over the preamble bits and the data bits, float64."""
+    return 1.0 - 2.0 * np.concatenate([np.asarray(pre, np.float64).ravel(), np.asarray(data_bits, np.float64).ravel()])
+
+
+def fsk_reference_mod(pre, data_bits, pulse, h, sps, amp=1.0):
+    """One frame in float64, independent of the integer law: the phase in turns is a real-valued cumulative sum of h / 2 * a *
+    g, the sample amp * exp(2 pi j phase).  F = (N + Q - 1) * sps + 1 samples, the first at phase 0."""
+    a, g, sps = fsk_levels(pre, data_bits), np.asarray(pulse, np.float64).ravel(), int(sps)
+    N, Q = a.size, -(-g.size // sps)
+    F = (N + Q - 1) * sps + 1
+    up = np.zeros(F - 1)
+    up[:N * sps:sps] = a
+    freq = np.convolve(up, g)[:F - 1] * (float(np.float32(h)) / 2.0)
+    turns = np.concatenate([[0.0], np.cumsum(freq)])
+    return float(np.float32(amp)) * np.exp(2j * np.pi * turns)
+
+
+def fsk_expected(pre, pulse, sps, mf, delay):
+    """e[k] of the preamble in float64 from the real-valued pulse (h cancels): the matched filter over the preamble's own
+    frequency waveform, data symbols taken as 0, over (sum g / sps) * sum m."""
+    a, g, m, sps = 1.0 - 2.0 * np.asarray(pre, np.float64).ravel(), np.asarray(pulse, np.float64).ravel(), np.asarray(mf, np.float64).ravel(), int(sps)
+    Lp = a.size
+    D = np.zeros((Lp - 1) * sps + g.size + int(delay) + Lp * sps + m.size)
+    for k in range(Lp):
+        D[k * sps:k * sps + g.size] += a[k] * g
+    U = g.sum() / sps * m.sum()
+    return np.array([np.dot(m, D[delay + k * sps - 1:][:m.size]) for k in range(Lp)]) / U
+
+
+def fsk_reference_demod(x, o, pre, n_bits, pulse, sps, mf, delay, rng, scale=1.0):
+    """One burst in float64: np.angle of x[n] conj(x[n-1]), dot products with the matched filter, the least-squares fit of
+    (dev, dc) on the preamble at every timing candidate, the candidate of the greatest num (the lowest among equals).
+    Returns (tau, f, dev, q, soft (n_bits,))."""
+    x, m, sps, delay, R = np.asarray(x, np.complex128).ravel(), np.asarray(mf, np.float64).ravel(), int(sps), int(delay), int(rng)
+    e = fsk_expected(pre, pulse, sps, mf, delay)
+    Lp, N = e.size, e.size + int(n_bits)
+    lo, hi = o + delay - R - 1, o + delay + R + (N - 1) * sps + m.size
+    seg = x[lo:hi]
+    v = np.angle(seg[1:] * np.conj(seg[:-1]))                   # v[i] of sample lo + 1 + i, i.e. relative index delay - R + i
+    u = lambda tau, k: np.array([np.dot(m, v[R + tau + kk * sps:][:m.size]) for kk in k])
+    se, see = e.sum(), (e * e).sum()
+    den = Lp * see - se * se
+    best = None
+    for tau in range(-R, R + 1):
+        uk = u(tau, range(Lp))
+        S1, Se = uk.sum(), (e * uk).sum()
+        num = Lp * Se - se * S1
+        if best is None or num > best[0]:
+            best = (num, tau, S1, uk)
+    num, tau, S1, uk = best
+    dev = num / den
+    dc = (S1 - dev * se) / Lp
+    q = ((uk - (dev * e + dc)) ** 2).sum() / (dev * dev * see)
+    soft = float(np.float32(scale)) * (u(tau, range(Lp, N)) - dc) / dev
+    return tau, dc / (2.0 * np.pi), dev, q, soft
