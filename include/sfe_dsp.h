@@ -2165,6 +2165,88 @@ int sfe_dsp_fsk_demod_stream(sfe_fsk_t h, const void *d_in, size_t n_in, size_t 
                              size_t *n_out, sfe_stream_t stream);
 int sfe_dsp_fsk_destroy(sfe_fsk_t h);
 
+/* ------------------------------------------------- frame check: CRC and scrambler
+ * What answers "is this payload the one that was sent": on transmit, in front of sfe_dsp_reed_*'s
+ * encoder, sfe_dsp_mod_*, sfe_dsp_ldpc_encode_stream or sfe_dsp_fsk_mod_stream, rows of P payload
+ * bytes become rows of Fb = P + w/8 frame bytes -- the payload, its CRC, and the whole frame XOR a
+ * PN sequence (append); on receive, behind sfe_dsp_vit_*, sfe_dsp_reed_process_stream,
+ * sfe_dsp_ldpc_* or sfe_dsp_fsk_demod_stream's hard bits, rows of Fb channel bytes are
+ * de-scrambled, the CRC of the first P bytes is computed and compared with the received one, and
+ * the payload is written out with a record and a status (check).  One handle, two directions.
+ * Frames are independent; nothing is carried.  Integer arithmetic only.
+ * The law is csrc/crc_law.h, one header the kernels and the host plan both compile.
+ * CRC: width w in {8, 16, 24, 32}; poly below 2^w with the top term implicit and bit 0 set; init and
+ * xorout below 2^w; reflect 0 or 1, applying to the input bytes and to the final register alike
+ * (models with refin != refout are not offered).  Bit by bit: r = init; for each byte b of the
+ * payload in order (bit-reversed when reflect) r ^= b << (w-8), then eight times
+ * r = (r & top) ? ((r << 1) ^ poly) & mask : (r << 1) & mask; at the end r is bit-reversed over w
+ * bits when reflect, then XORed with xorout.  The w/8 CRC bytes follow the payload most significant
+ * byte first when reflect = 0 and least significant first when reflect = 1: the order in which the
+ * model's residue property holds.  CRC-32/ISO-HDLC (zlib's) is (32, 0x04C11DB7, 0xFFFFFFFF, 1,
+ * 0xFFFFFFFF); CRC-16/XMODEM is (16, 0x1021, 0, 0, 0).  The serial statement is the law; the host
+ * plan runs it a byte at a time through a table, the kernels spread a frame over lanes.
+ * Scrambler (additive, frame-synchronous: it restarts at every frame): degree m in [2, 32]; taps
+ * below 2^m with bit 0 set; seed in [1, 2^m).  a[i] = bit i of seed for i < m; a[n+m] = the XOR over
+ * the set bits i of taps of a[n+i]; bytes MSB first, a[8j] is bit 7 of byte j.  (8, 0xA9, 0xFF) is
+ * the CCSDS randomiser, ff 48 0e c0 9a ...; (7, 0x09, 0x7F) gives from bit 7 on the IEEE 802.11
+ * sequence 00001110 11110010 ...  m = 0: no scrambler.  w = 0: no CRC, a scrambler-only handle with
+ * Fb = P, status 0 or 2 and record (0, 0).  Both zero is refused.
+ * Frame: P in [1, 2^20], fixed at create.  Transmit: frame = (payload || crc bytes) XOR pn[0 .. Fb).
+ * Receive, per frame b: r = channel XOR pn; P bytes r[0 .. P) at d_out + b*out_stride; two uint32
+ * words at d_rec + 2b -- the CRC computed over r[0 .. P), and the CRC received in r[P .. Fb); an
+ * int32 status at d_status + b:
+ *   0  equal
+ *   1  different; the payload is still written, as received
+ *   2  d_status_in is given and its word for this frame is not 0: no input is read, the bytes are
+ *      0, the record (0, 0) -- the convention of sfe_dsp_reed_*
+ * Promised about bytes: the same call gives the same bytes on every run; a frame's output depends
+ * on its bytes and the handle only -- never on b, n_frames, addresses, alignment or strides; the
+ * device's bytes, record and status EQUAL sfe_dsp_crc_plan's for every input, none excluded;
+ * nothing outside the slots named is written, to the byte.  Payloads and frames need no alignment;
+ * records and statuses 4 bytes.
+ * Out of scope: per-frame lengths or seeds, multiplicative (self-synchronising) scramblers, other
+ * widths and refin != refout, CRCs over bits rather than bytes, compaction of the good frames,
+ * differential encoding, in-place operation.
+ * A bad argument is SFE_EINVAL on any machine, with a message that starts with "crc: ". */
+typedef void *sfe_crc_t; /* opaque: one model, one sequence, one payload length; it owns its constants and its sequence on the device and nothing in it changes after create */
+/* Host-only: n bytes of the scrambler's sequence by the law above into out.  m = 0 is refused here.
+ * Also what makes sfe_dsp_reed_*'s `whiten`. */
+int sfe_dsp_crc_pn_bytes(int m, uint32_t taps, uint32_t seed, size_t n, uint8_t *out);
+/* Host-only (no GPU): validates what create validates and reports Fb (the pointer may be NULL).
+ * With in != NULL -- host memory laid out as d_payload of append_stream (check = 0) or as d_frame
+ * of check_stream (check = 1) -- it runs n_frames frames by the law above into out (frame b at
+ * out + b*out_stride), record [n_frames][2] and status [n_frames]; each of the three may be NULL.
+ * status_in [n_frames] or NULL; with check = 0 status_in, record and status are ignored.  The
+ * reference of the device's bytes.  Short strides are SFE_ERANGE. */
+int sfe_dsp_crc_plan(int width, uint32_t poly, uint32_t init, int reflect, uint32_t xorout,
+                     int pn_m, uint32_t pn_taps, uint32_t pn_seed, int payload_bytes, int check,
+                     const uint8_t *in, size_t in_stride, const int *status_in, size_t n_frames,
+                     uint8_t *out, size_t out_stride, uint32_t *record, int *status,
+                     int *frame_bytes);
+/* Arguments are checked before the device is touched: SFE_EINVAL for a bad one on any machine,
+ * SFE_ENODEV without a GPU.  The constants of the kernels and the sequence are made here. */
+int sfe_dsp_crc_create(int width, uint32_t poly, uint32_t init, int reflect, uint32_t xorout,
+                       int pn_m, uint32_t pn_taps, uint32_t pn_seed, int payload_bytes, int device,
+                       sfe_crc_t *out);
+/* n_frames frames each way.  d_status_in may be NULL; in check_stream d_out, d_rec and d_status
+ * may each be NULL (a verify-only call), all three NULL is SFE_EINVAL.  *n_out = n_frames;
+ * n_frames = 0 is a no-op.  A stride below the bytes a frame reads or writes (P, Fb) is SFE_ERANGE;
+ * a null d_payload or d_frame, a misaligned record or status pointer, n_frames >= 2^31, a stride
+ * that takes a buffer's byte range to 2^62, and any output byte range that overlaps an input's or
+ * another output's are SFE_EINVAL, each with a message that starts with "crc_append_stream: " or
+ * "crc_check_stream: "; nothing is launched on a refusal.  Asynchronous on `stream`; one kernel
+ * launch and nothing else: allocates nothing, does not synchronise the host, carries no state
+ * (there is no reset, and a handle has no setter), so a call on a stream under graph capture IS
+ * supported.  Every loop of the kernels runs a number of times fixed by P and w. */
+int sfe_dsp_crc_append_stream(sfe_crc_t h, const void *d_payload, size_t in_stride,
+                              size_t n_frames, void *d_frame, size_t out_stride, size_t *n_out,
+                              sfe_stream_t stream);
+int sfe_dsp_crc_check_stream(sfe_crc_t h, const void *d_frame, size_t in_stride,
+                             const void *d_status_in, size_t n_frames, void *d_out,
+                             size_t out_stride, void *d_rec, void *d_status, size_t *n_out,
+                             sfe_stream_t stream);
+int sfe_dsp_crc_destroy(sfe_crc_t h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,8 @@ Two layers, both thin:
     (sfe_dsp_iir_*); `Beam`, the multi-stream beamformer / stream-mixing bank (sfe_dsp_beam_*); `Cov`, the streaming
     spatial covariance estimator (sfe_dsp_cov_*); `Mod`, the burst modulator (sfe_dsp_mod_*); `Polar`, the FM, phase and
     envelope detector (sfe_dsp_polar_*); `Occ`, the spectrum occupancy detector over a Psd's rows (sfe_dsp_occ_*);
-    `Reed`, the interleaved Reed-Solomon outer code behind a Vit and in front of a Mod (sfe_dsp_reed_*); `Ofdm`, the OFDM burst
+    `Reed`, the interleaved Reed-Solomon outer code behind a Vit and in front of a Mod (sfe_dsp_reed_*); `Crc`, the frame
+    check outside it, CRC and scrambler (sfe_dsp_crc_*); `Ofdm`, the OFDM burst
     receiver behind a Corr (sfe_dsp_ofdm_*); `OfdmMod`, its transmit side, the OFDM burst modulator (sfe_dsp_ofdmmod_*).
 
 Everything computes on the GPU through the C ABI; numpy is only the host container.
@@ -2266,6 +2267,117 @@ class Fsk(_Block):
             for d in held:
                 d.free()
         return np.ascontiguousarray(soft), np.ascontiguousarray(by), np.ascontiguousarray(rec), np.ascontiguousarray(st)
+
+
+def pn_bytes(m, taps, seed, n):
+    """sfe_dsp_crc_pn_bytes (host only): n bytes of the additive scrambler's sequence (degree m, taps, seed), MSB first -- what
+    a Crc XORs over its frames, and what makes Reed's `whiten`."""
+    out = np.empty(int(n), np.uint8)
+    check(_l.load().sfe_dsp_crc_pn_bytes(int(m), int(taps), int(seed), out.size, out.ctypes.data if out.size else None))
+    return out
+
+
+def _crc_shape(width, poly, init, reflect, xorout, pn_m, pn_taps, pn_seed, payload_bytes):
+    """The nine shape arguments sfe_dsp_crc_plan and sfe_dsp_crc_create share."""
+    return (int(width), int(poly), int(init), int(reflect), int(xorout), int(pn_m), int(pn_taps), int(pn_seed), int(payload_bytes))
+
+
+def crc_plan(width, poly, init, reflect, xorout, pn_m=0, pn_taps=0, pn_seed=0, payload_bytes=1, data=None, verify=False, status_in=None):
+    """sfe_dsp_crc_plan (host only, no GPU): validates and, without data, returns frame_bytes.  With data and not verify (the C ABI's check = 0) --
+    (n_frames, >= payload_bytes) uint8 -- it returns the frames (n_frames, frame_bytes) uint8; with data and verify (check = 1) --
+    (n_frames, >= frame_bytes) uint8 channel bytes -- it returns (bytes (n_frames, payload_bytes) uint8, record (n_frames, 2)
+    uint32 -- the CRC computed, the CRC received -- and status (n_frames,) int32).  These are the device's bytes.
+    status_in: int32 per frame or None.  Raises SfeError on arguments the block refuses."""
+    head = _crc_shape(width, poly, init, reflect, xorout, pn_m, pn_taps, pn_seed, payload_bytes)
+    L, Fb = _l.load(), C.c_int(0)
+    check(L.sfe_dsp_crc_plan(*head, int(bool(verify)), None, 0, None, 0, None, 0, None, None, C.byref(Fb)))
+    if data is None:
+        return Fb.value
+    d = np.asarray(data, dtype=np.uint8)
+    d = np.ascontiguousarray(d.reshape(1, -1) if d.ndim == 1 else d)
+    nf = d.shape[0]
+    if status_in is not None:
+        status_in = np.ascontiguousarray(status_in, dtype=np.int32).ravel()
+        if status_in.size != nf:
+            raise ValueError("crc_plan: status_in has %d entries for %d frames" % (status_in.size, nf))
+    out = np.empty((nf, head[8] if verify else Fb.value), np.uint8)
+    rec, st = np.empty((nf, 2), np.uint32), np.empty(nf, np.int32)
+    check(L.sfe_dsp_crc_plan(*head, int(bool(verify)), d.ctypes.data if d.size else None, d.shape[1],
+                              None if status_in is None else status_in.ctypes.data, nf, out.ctypes.data, out.shape[1], rec.ctypes.data,
+                              st.ctypes.data, None))
+    return (out, rec, st) if verify else out
+
+
+class Crc(_Block):
+    """Frame check (sfe_dsp_crc_*): append_stream turns payload_bytes bytes per frame into frame_bytes = payload_bytes + width / 8
+    bytes -- the payload, its CRC, the whole XOR the scrambler's sequence -- in front of a Reed / Ldpc encoder, a Mod or an Fsk;
+    check_stream de-scrambles channel bytes -- what a Vit, a Reed, an Ldpc or an Fsk wrote -- and writes the payload with a record
+    (CRC computed, CRC received) and a status per frame.  width 0: a scrambler alone.  The device's bytes are crc_plan's."""
+    _prefix = "crc"
+
+    def __init__(self, width, poly, init, reflect, xorout, pn_m=0, pn_taps=0, pn_seed=0, payload_bytes=1, device=0):
+        head = _crc_shape(width, poly, init, reflect, xorout, pn_m, pn_taps, pn_seed, payload_bytes)
+        self._create(*head, device)
+        self.width, self.payload_bytes, self.frame_bytes = head[0], head[8], head[8] + head[0] // 8
+
+    def append_stream(self, d_payload, n_frames, d_frame, in_stride=None, out_stride=None, stream=None):
+        """d_*: DeviceArray or raw device pointers.  Frame b reads payload_bytes bytes at d_payload + b*in_stride (default
+        payload_bytes) and writes frame_bytes bytes at d_frame + b*out_stride (default frame_bytes).  Returns n_frames."""
+        k = C.c_size_t(0)
+        check(self._fn("append_stream")(self._h, self._ptr(d_payload), self.payload_bytes if in_stride is None else int(in_stride), int(n_frames),
+                                        self._ptr(d_frame), self.frame_bytes if out_stride is None else int(out_stride), C.byref(k), stream))
+        return k.value
+
+    def check_stream(self, d_frame, n_frames, d_out=None, d_rec=None, d_status=None, d_status_in=None, in_stride=None, out_stride=None, stream=None):
+        """d_*: DeviceArray or raw device pointers.  Frame b reads frame_bytes bytes at d_frame + b*in_stride (default
+        frame_bytes) and, with d_status_in, the int32 at d_status_in + b; it writes payload_bytes bytes at d_out + b*out_stride
+        (default payload_bytes), two words at d_rec + 2b and an int32 at d_status + b; each of the three may be None, not all.
+        Returns n_frames."""
+        k = C.c_size_t(0)
+        check(self._fn("check_stream")(self._h, self._ptr(d_frame), self.frame_bytes if in_stride is None else int(in_stride),
+                                       self._ptr(d_status_in), int(n_frames), self._ptr(d_out),
+                                       self.payload_bytes if out_stride is None else int(out_stride), self._ptr(d_rec), self._ptr(d_status),
+                                       C.byref(k), stream))
+        return k.value
+
+    def reset(self):
+        raise AttributeError("Crc has no reset: it carries no state")
+
+    def append(self, data):
+        """Host convenience, computed on the GPU: data is (n_frames, payload_bytes) uint8; returns (n_frames, frame_bytes)."""
+        d = np.asarray(data, dtype=np.uint8)
+        d = np.ascontiguousarray(d.reshape(1, -1) if d.ndim == 1 else d)
+        nf = d.shape[0]
+        held = [DeviceArray.from_bytes(d), DeviceArray(max(1, (nf * self.frame_bytes + 3) // 4))]
+        try:
+            if nf:
+                self.append_stream(held[0], nf, held[1], in_stride=d.shape[1])
+            raw = held[1].to_numpy().view(np.uint8)[:nf * self.frame_bytes].reshape(nf, self.frame_bytes)
+        finally:
+            for x in held:
+                x.free()
+        return np.ascontiguousarray(raw)
+
+    def check(self, frames, status_in=None):
+        """Host convenience, computed on the GPU: frames is (n_frames, frame_bytes) uint8; returns what crc_plan returns."""
+        d = np.asarray(frames, dtype=np.uint8)
+        d = np.ascontiguousarray(d.reshape(1, -1) if d.ndim == 1 else d)
+        nf, P = d.shape[0], self.payload_bytes
+        held = [DeviceArray.from_bytes(d), DeviceArray(max(1, (nf * P + 3) // 4)), DeviceArray(max(1, 2 * nf)), DeviceArray(max(1, nf))]
+        try:
+            d_si = None
+            if status_in is not None:
+                d_si = DeviceArray.from_numpy(np.ascontiguousarray(status_in, dtype=np.int32).reshape(nf).view(np.float32))
+                held.append(d_si)
+            if nf:
+                self.check_stream(held[0], nf, held[1], held[2], held[3], d_si, in_stride=d.shape[1])
+            by = held[1].to_numpy().view(np.uint8)[:nf * P].reshape(nf, P)
+            rec = held[2].to_numpy(2 * nf).view(np.uint32).reshape(nf, 2)
+            st = held[3].to_numpy(nf).view(np.int32)
+        finally:
+            for x in held:
+                x.free()
+        return np.ascontiguousarray(by), np.ascontiguousarray(rec), np.ascontiguousarray(st)
 
 
 def rs_plan(state, upsample, n_in, out_len, rate):

@@ -33,15 +33,16 @@ ARCH = "gfx950"
 # ofdm.hip: its u8 and cf32 instantiations must hand the transform the same floats, and its sums are explicit fmaf chains;
 # ofdmmod.hip: as polar.hip with ofdmmod_law.h, whose fused operations are the explicit fmaf of the complex product;
 # qam.hip: as polar.hip with qam_law.h, whose one fused operation is the explicit fmaf of |H|^2;
-# fsk.hip: as polar.hip with fsk_law.h and polar_law.h: explicit fmaf chains, the host plan compiles the same headers)
+# fsk.hip: as polar.hip with fsk_law.h and polar_law.h: explicit fmaf chains, the host plan compiles the same headers;
+# crc.hip: as reed.hip, integer work only, with crc_law.h)
 EXACT_SOURCES = ("polyphase.hip", "util.hip", "chan.hip", "combine.hip", "ddc.hip", "psd.hip", "corr.hip", "iir.hip", "beam.hip",
                  "cov.hip", "mvdr.hip", "eig.hip", "burst.hip", "vit.hip", "mod.hip", "polar.hip", "occ.hip", "reed.hip", "ldpc.hip", "ofdm.hip",
-                 "ofdmmod.hip", "qam.hip", "fsk.hip")
+                 "ofdmmod.hip", "qam.hip", "fsk.hip", "crc.hip")
 TICKET_SOURCES = ("fir_fft.hip", "poly_fft.hip")
 # host side only (handles, plans, launch choices, device groups):
 # not part of the kernel-source hash
 HOST_SOURCES = ("api.hip", "api_plans.hip", "api_fir.hip", "api_rs.hip", "api_pipe.hip", "api_chan.hip", "api_combine.hip", "api_ddc.hip",
-                "api_psd.hip", "api_corr.hip", "api_iir.hip", "api_beam.hip", "api_cov.hip", "api_mvdr.hip", "api_eig.hip", "api_burst.hip", "api_vit.hip", "api_mod.hip", "api_polar.hip", "api_occ.hip", "api_reed.hip", "api_ldpc.hip", "api_ofdm.hip", "api_ofdmmod.hip", "api_qam.hip", "api_fsk.hip", "group.hip", "host.h", "block.h",
+                "api_psd.hip", "api_corr.hip", "api_iir.hip", "api_beam.hip", "api_cov.hip", "api_mvdr.hip", "api_eig.hip", "api_burst.hip", "api_vit.hip", "api_mod.hip", "api_polar.hip", "api_occ.hip", "api_reed.hip", "api_ldpc.hip", "api_ofdm.hip", "api_ofdmmod.hip", "api_qam.hip", "api_fsk.hip", "api_crc.hip", "group.hip", "host.h", "block.h",
                 "call_checks.h", "beam_view.h", "vit_code.h", "rs_plan.h", "fir_plan.h")
 
 
@@ -73,7 +74,8 @@ KERNEL_FILES = {"fir": ("fir_fft.hip", "fft16.h", "common.h"), "resample": ("pol
                 "ofdm": ("ofdm.hip", "ofdm.h", "fft16.h", "common.h"),
                 "ofdmmod": ("ofdmmod.hip", "ofdmmod.h", "ofdmmod_law.h", "ofdm.h", "common.h"),
                 "qam": ("qam.hip", "qam.h", "qam_law.h", "common.h"),
-                "fsk": ("fsk.hip", "fsk.h", "fsk_law.h", "polar_law.h", "mod.h", "vit.h", "burst.h", "eig.h", "common.h")}
+                "fsk": ("fsk.hip", "fsk.h", "fsk_law.h", "polar_law.h", "mod.h", "vit.h", "burst.h", "eig.h", "common.h"),
+                "crc": ("crc.hip", "crc.h", "crc_law.h", "common.h")}
 
 
 def csrc_hash(kind=None):
@@ -155,7 +157,7 @@ SCRATCH_FREE = {"chan.hip": "channelizer", "combine.hip": "combiner", "ddc.hip":
                 "corr.hip": "correlator", "iir.hip": "IIR", "beam.hip": "beamformer", "cov.hip": "covariance", "mvdr.hip": "weight-solver", "eig.hip": "eigen-solver",
                 "burst.hip": "burst-demodulator", "vit.hip": "Viterbi-decoder", "mod.hip": "burst-modulator", "polar.hip": "detector",
                 "occ.hip": "occupancy-detector", "reed.hip": "Reed-Solomon", "ldpc.hip": "LDPC", "ofdm.hip": "OFDM-receiver",
-                "ofdmmod.hip": "OFDM-modulator", "qam.hip": "QAM-mapper", "fsk.hip": "FSK-modem"}
+                "ofdmmod.hip": "OFDM-modulator", "qam.hip": "QAM-mapper", "fsk.hip": "FSK-modem", "crc.hip": "frame-check"}
 
 FIR_TEMPLATE_ARGS = "IN_C OUT_C IN_U8 PAIR OUT_TX10 DMA DIAG ACC WP HCH".split()
 
@@ -192,7 +194,7 @@ def check_resources(res):
             if r.get("ScratchSize", 0) or r.get("VGPRs Spill", 0) or r.get("SGPRs Spill", 0):
                 bad.append("%s: %s kernel touches scratch: %s" % (k[:200], noun, r))
     if bad:
-        raise RuntimeError("FIR kernels of the default path and the channelizer, combiner, down-converter, spectrum-estimator, correlator, IIR, beamformer, covariance, weight-solver, eigen-solver, burst-demodulator, Viterbi-decoder, burst-modulator, detector, occupancy-detector, Reed-Solomon, LDPC, OFDM-receiver, OFDM-modulator, QAM-mapper and FSK-modem kernels "
+        raise RuntimeError("FIR kernels of the default path and the channelizer, combiner, down-converter, spectrum-estimator, correlator, IIR, beamformer, covariance, weight-solver, eigen-solver, burst-demodulator, Viterbi-decoder, burst-modulator, detector, occupancy-detector, Reed-Solomon, LDPC, OFDM-receiver, OFDM-modulator, QAM-mapper, FSK-modem and frame-check kernels "
                            "must not touch scratch; "
                            "the FIR ones must keep "
                            "4 workgroups per CU:\n  " + "\n  ".join(bad))

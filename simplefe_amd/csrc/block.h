@@ -3,7 +3,7 @@
 // the FIR and resample / decimate handles), the device scope of a create, the handle cast,
 // the table of the unit circle, the opening of every process_stream and the format setter.  The checks of a call's buffers need no HIP and live in call_checks.h, which
 // this includes: the pieces (Span, span_bytes, refuse_*), the one check each of five families of blocks -- rows
-// (api_vit.hip, api_reed.hip, api_ldpc.hip), windows (api_burst.hip, api_ofdm.hip), frames (api_mod.hip, api_ofdmmod.hip),
+// (api_vit.hip, api_reed.hip, api_ldpc.hip, api_crc.hip), windows (api_burst.hip, api_ofdm.hip), frames (api_mod.hip, api_ofdmmod.hip),
 // streams (api_chan.hip, api_ddc.hip, api_psd.hip, api_iir.hip, api_polar.hip, api_beam.hip, api_cov.hip), channels
 // (api_fir.hip, api_rs.hip) -- and the byte
 // ranges of the four that keep their own sequence (api_combine.hip, api_corr.hip, api_mvdr.hip, api_eig.hip).  The FIR, resampler and pipe handles (host.h, api_pipe.hip) and every block's api_*.hip use it.  HOST CODE

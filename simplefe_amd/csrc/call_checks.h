@@ -1,6 +1,6 @@
 // call_checks.h -- the argument checks a process_stream makes before it launches anything: what stands between a caller's
 // bad stride and an out-of-bounds kernel.  The pieces every block uses (Span, span_bytes, refuse_*), the rules of the burst
-// chain's windows and frames (check_starts, check_place), one check per family of blocks: rows (vit, reed, ldpc), windows
+// chain's windows and frames (check_starts, check_place), one check per family of blocks: rows (vit, reed, ldpc, crc), windows
 // (burst, ofdm), frames (mod, ofdmmod), streams (chan, ddc, psd, iir, polar, beam, cov), channels (fir, fir_calibrate, rs),
 // and the byte ranges of the four entry points that fit no family (combine, corr, mvdr, eig).  Every byte range comes from span_bytes, so a stride that would wrap
 // one is refused, never multiplied out.  HOST CODE ONLY, plain C++17 and no HIP: block.h includes it, and
@@ -159,7 +159,8 @@ inline int check_place(const char *who, int F, bool tx10, bool even_starts, size
 
 // ---- rows: a codec that reads one row of `in_row` elements of `esz` bytes and writes one of `out_row` bytes per item, with
 // an optional status in, record (rec_bytes a row) and status out.  The SFE_ERANGE sentence reads "in_stride S < the R
-// <in_row>, or out_stride S < <out_lead>R<out_tail>".
+// <in_row>, or out_stride S < <out_lead>R<out_tail>".  out_optional (crc's check): d_out may be null like the record and the
+// status -- an output of no bytes, whose stride is not looked at.
 struct RowNouns {
     const char *count;                  // "n_bursts"
     const char *in_row;                 // "elements of a burst's row"
@@ -169,7 +170,7 @@ struct RowNouns {
 };
 inline int check_rows(const char *who, const RowNouns &nn, size_t n, const void *d_in, size_t in_stride, size_t in_row, size_t esz,
                       const void *d_status_in, const void *d_out, size_t out_stride, size_t out_row, const void *d_rec, const void *d_status,
-                      bool *go)
+                      bool *go, bool out_optional = false)
 {
     *go = false;
     if (n >= ((size_t)1 << 31)) {
@@ -177,15 +178,15 @@ inline int check_rows(const char *who, const RowNouns &nn, size_t n, const void 
         return SFE_EINVAL;
     }
     if (n == 0) return SFE_OK;
-    int rc = refuse_null(who, {d_in, d_out});
+    int rc = out_optional ? refuse_null(who, {d_in}) : refuse_null(who, {d_in, d_out});
     if (rc != SFE_OK) return rc;
-    if (in_stride < in_row || out_stride < out_row) {
+    if (in_stride < in_row || (d_out && out_stride < out_row)) {
         set_error("%s: in_stride %zu < the %zu %s, or out_stride %zu < %s%zu%s", who, in_stride, in_row, nn.in_row, out_stride, nn.out_lead,
                   out_row, nn.out_tail);
         return SFE_ERANGE;
     }
     size_t in_b = 0, ou_b = 0;
-    if (!span_bytes(n - 1, in_stride, in_row, esz, &in_b) || !span_bytes(n - 1, out_stride, out_row, 1, &ou_b)) {
+    if (!span_bytes(n - 1, in_stride, in_row, esz, &in_b) || (d_out && !span_bytes(n - 1, out_stride, out_row, 1, &ou_b))) {
         set_error("%s: a stride is so large that its buffer's byte range reaches 2^62", who);
         return SFE_EINVAL;
     }

@@ -27,13 +27,14 @@ OFDM_OK, OFDM_NO_ESTIMATE, OFDM_GATED, OFDM_OUT_OF_RANGE = 0, 1, 2, 3        # s
 OFDMMOD_IN_BITS, OFDMMOD_IN_SYMBOLS = 0, 1           # sfe_dsp_ofdmmod_*: in_mode
 QAM_MAP, QAM_DEMAP = 0, 1                            # sfe_dsp_qam_plan: direction
 FSK_MOD, FSK_DEMOD = 0, 1                            # sfe_dsp_fsk_plan: direction
+CRC_OK, CRC_MISMATCH, CRC_UPSTREAM = 0, 1, 2         # sfe_dsp_crc_*: a frame's status
 
 
 class TimeState(C.Structure):
     _fields_ = [("pos", C.c_int32), ("mu", C.c_float), ("leftover", C.c_int32)]
 
 
-vp, sz, i32, f32 = C.c_void_p, C.c_size_t, C.c_int, C.c_float
+vp, sz, i32, f32, u32 = C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_uint32
 fp = C.POINTER(C.c_float)
 
 # name -> (restype, argtypes): every symbol include/sfe_dsp.h declares
@@ -245,6 +246,12 @@ SIGNATURES = {
     "sfe_dsp_fsk_mod_stream": (i32, [vp, vp, sz, sz, C.c_int64, C.c_int64, vp, sz, C.POINTER(sz), vp]),
     "sfe_dsp_fsk_demod_stream": (i32, [vp, vp, sz, sz, vp, sz, vp, sz, sz, C.c_int64, C.c_int64, vp, sz, vp, sz, vp, vp, sz, C.POINTER(sz), vp]),
     "sfe_dsp_fsk_destroy": (i32, [vp]),
+    "sfe_dsp_crc_pn_bytes": (i32, [i32, u32, u32, sz, vp]),
+    "sfe_dsp_crc_plan": (i32, [i32, u32, u32, i32, u32, i32, u32, u32, i32, i32, vp, sz, vp, sz, vp, sz, vp, vp, C.POINTER(i32)]),
+    "sfe_dsp_crc_create": (i32, [i32, u32, u32, i32, u32, i32, u32, u32, i32, i32, C.POINTER(vp)]),
+    "sfe_dsp_crc_append_stream": (i32, [vp, vp, sz, sz, vp, sz, C.POINTER(sz), vp]),
+    "sfe_dsp_crc_check_stream": (i32, [vp, vp, sz, vp, sz, vp, sz, vp, vp, C.POINTER(sz), vp]),
+    "sfe_dsp_crc_destroy": (i32, [vp]),
 }
 
 # the diagnostic library only (simplefe_amd/csrc/diag/sfe_dsp_diag.h; scripts/ load it by pointing LIB_PATH at it): bound when present

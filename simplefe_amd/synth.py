@@ -1593,3 +1593,69 @@ def fsk_reference_demod(x, o, pre, n_bits, pulse, sps, mf, delay, rng, scale=1.0
     q = ((uk - (dev * e + dc)) ** 2).sum() / (dev * dev * see)
     soft = float(np.float32(scale)) * (u(tau, range(Lp, N)) - dc) / dev
     return tau, dc / (2.0 * np.pi), dev, q, soft
+
+
+# ------------------------------------------------------------------ frame check: CRC and scrambler (sfe_dsp_crc_*)
+def pn_reference(m, taps, seed, n):
+    """n bytes of the additive scrambler's sequence, bit by bit as include/sfe_dsp.h states it: a[i] = bit i of seed for
+    i < m, a[k + m] = the xor of a[k + i] over the set bits i of taps; a[8 j] is bit 7 of byte j."""
+    m, nbits = int(m), 8 * int(n)
+    a = [(int(seed) >> i) & 1 for i in range(m)]
+    at = [i for i in range(m) if (int(taps) >> i) & 1]
+    for k in range(max(0, nbits - m)):
+        v = 0
+        for i in at:
+            v ^= a[k + i]
+        a.append(v)
+    return np.packbits(np.array(a[:nbits], np.uint8))          # MSB first
+
+
+def _crc_bits(width, poly, init, reflect, xorout, rows):
+    """The CRC of every row of `rows` (n_frames, n) uint8, one shift of the register at a time, all frames at once."""
+    w = int(width)
+    nf = rows.shape[0]
+    if w == 0:
+        return np.zeros(nf, np.uint32)
+    mask, top = np.uint64((1 << w) - 1), np.uint64(1 << (w - 1))
+    r = np.full(nf, int(init), np.uint64)
+    bits = np.unpackbits(rows, axis=1, bitorder="little" if reflect else "big")          # the order in which a byte's bits enter
+    for j in range(bits.shape[1]):
+        # a message bit enters at the register's top; a one leaving the top folds the polynomial in
+        out = ((r & top) != 0) ^ (bits[:, j] != 0)
+        r = (r << np.uint64(1)) & mask
+        r[out] ^= np.uint64(int(poly))
+    if reflect:
+        rev = np.zeros(nf, np.uint64)
+        for i in range(w):
+            rev |= ((r >> np.uint64(i)) & np.uint64(1)) << np.uint64(w - 1 - i)
+        r = rev
+    return (r ^ np.uint64(int(xorout))).astype(np.uint32)
+
+
+def crc_reference(width, poly, init, reflect, xorout, pn_m=0, pn_taps=0, pn_seed=0, payload_bytes=1, data=None, verify=False, status_in=None):
+    """The law of sfe_dsp_crc_* (include/sfe_dsp.h) restated in numpy, what api.crc_plan returns: without verify, payloads
+    (n_frames, P) -> frames (n_frames, P + width / 8); with verify, channel bytes (n_frames, Fb) -> (bytes, record (n_frames, 2)
+    uint32, status (n_frames,) int32).  The register takes one message bit per shift (the bit-at-a-time form of the
+    byte-at-a-time sentence), over all frames at once."""
+    P, nt = int(payload_bytes), int(width) // 8
+    Fb = P + nt
+    d = np.asarray(data, np.uint8)
+    d = d.reshape(1, -1) if d.ndim == 1 else d
+    nf = d.shape[0]
+    pn = pn_reference(pn_m, pn_taps, pn_seed, Fb) if pn_m else np.zeros(Fb, np.uint8)
+    order = range(nt) if reflect else range(nt - 1, -1, -1)                             # the tail's bytes as shifts of the CRC
+    if not verify:
+        crc = _crc_bits(width, poly, init, reflect, xorout, d[:, :P])
+        tail = np.stack([(crc >> np.uint32(8 * s)).astype(np.uint8) for s in order], axis=1) if nt else np.zeros((nf, 0), np.uint8)
+        return np.concatenate([d[:, :P], tail], axis=1) ^ pn[None, :]
+    r = d[:, :Fb] ^ pn[None, :]
+    crc = _crc_bits(width, poly, init, reflect, xorout, r[:, :P])
+    got = np.zeros(nf, np.uint32)
+    for k, s in enumerate(order):
+        got |= r[:, P + k].astype(np.uint32) << np.uint32(8 * s)
+    by, rec = np.ascontiguousarray(r[:, :P]), np.stack([crc, got], axis=1).astype(np.uint32)
+    st = (crc != got).astype(np.int32)
+    if status_in is not None:
+        up = np.asarray(status_in).ravel() != 0
+        by[up], rec[up], st[up] = 0, 0, 2
+    return by, rec, st
